@@ -24,8 +24,20 @@ at any N: with N > 1 the launcher's plumbing -- rendezvous, barrier, max-reduce 
 id to the other ranks -- is a localhost socket (quadruped-robot_amd/rendezvous.py; the ranks find each other through RANK / WORLD_SIZE /
 MASTER_ADDR / MASTER_PORT as torch.distributed.run or this program's own launcher set them).  Rank 0 prints ONE JSON line.
 
+A plain run does only what `value` and `ms_per_step` need: set up, warm up, time the K steps, print the line.  Its untimed steps are W per
+draw, D * W in all (D = min(--draws, K // 5), at least 1: 160 at the defaults, tens of milliseconds at 0.2-0.3 ms a step), so the time a
+run spends outside (K + W) timed steps includes (D - 1) * W steps besides set-up and exit.  Everything else is measured
+with --full: the CPU baseline and the error against it, the comparison with the reference's solver, the roofline block (kernel times from
+HIP events, executed flop counts, imbalance) and the side measurements of config (slot-order dispatch, K12 off, replayed batch, ticks not
+overlapped, tick latency, serial tick, scaling prediction, PCIe, 8f kernels).  In the other modes --full adds their CPU figures.
+
+  --dump-outputs DIR   after the timed steps, what the last timed step handed its caller (forces, torques, joint targets, status words,
+                       the orientation task's memory; at N > 1 the gathered torques too; in the 8f modes their kernel's outputs) as
+                       DIR/<name>.npy, float32 (float64 for fp64 state and integer status words), robot on the last axis, at most 64 MB
+                       in all; the inputs are seeded, so two builds can be compared array by array
+
   python bench.py --mode single     the drop-in boundary's single-robot latency (qrgpu_mpc_solve1 / qrgpu_wbc_run1, and both through the C++
-                                    adapters): p50 / p99 over 1000 calls at h = 5, 10, 16 beside the reference's solver on the same QPs
+                                    adapters): p50 / p99 over 1000 calls at h = 5, 10, 16 (with --full beside the reference's solver on the same QPs)
 """
 import argparse
 import importlib.util
@@ -50,6 +62,7 @@ PEAK_F64_VECTOR_TFLOPS = 78.6                    # MI355X FP64 vector peak (spec
                                                  # v_fma_f64 at two waves per SIMD
 PEAK_HBM_GBS = 8000.0
 EST_IN_ROWS, EST_OUT_ROWS = 54, 42                # QRGPU_EST_IN_ROWS / QRGPU_EST_OUT_ROWS (include/qrgpu.h)
+DUMP_LIMIT_BYTES = 64 << 20                       # --dump-outputs: at most this much in all
 
 
 def _load_pkg():
@@ -140,6 +153,23 @@ def reference_solver(pkg, O, b, horizon, sample=24):
                                       "%d QPs of the bench batch, one thread (the port's time includes its fp32 assembly)" % idx.size)
 
 
+def dump_outputs(path, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: one PATH/<name>.npy per array, float32, or float64 for fp64 state and integer words (exact).  The robot is the last axis; when the
+    arrays exceed `limit` bytes in all, a fixed, seeded sample of robots is written instead, its indices as robot_index.npy."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v, np.float64 if np.asarray(v).dtype.kind in "iu" or np.asarray(v).dtype == np.float64 else np.float32)
+              for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit:
+        n = next(iter(arrays.values())).shape[-1]
+        m = max(1, (limit - 4096) // (total // n + 8))         # (4 kB for the .npy headers)
+        idx = np.sort(np.random.default_rng(0).choice(n, m, replace=False))
+        arrays = {k: a[..., idx] for k, a in arrays.items()}
+        arrays["robot_index"] = idx.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a))
+
+
 class Dev:
     """Device-buffer helpers over the package's own allocator (qrgpu_malloc / qrgpu_memcpy_*): what torch used to be asked for."""
 
@@ -177,6 +207,7 @@ def side_mode(args, pkg, ctx):
         d_f, d_t = D_.zeros((12, n)), D_.zeros((12, n))
         d_s = D_.zeros((n,), np.int32)
         step = lambda: ctx.vmc_force_batch(n, d_in, d_q, d_f, d_t, d_s)
+        outputs = dict(force=d_f, tau=d_t, status=d_s)
         cpu = lambda i: O.vmc_solve(cfg, geom, vin[i], q[i])
         alg_bytes = (37 + 12 + 12 + 12 + 1) * 4
         metric, unit, kernel = "force-balance QP solves/s (batched robots)", "solves/s", "qr_vmc_kernel"
@@ -190,6 +221,7 @@ def side_mode(args, pkg, ctx):
         d_state = D_.zeros((S_, n), np.float64)
         d_out = D_.zeros((EST_OUT_ROWS, n))          # QRGPU_EST_OUT_ROWS of include/qrgpu.h
         step = lambda: ctx.estimator_update_batch(n, cfg, d_in, d_tick, d_state, d_out)
+        outputs = dict(estimator_out=d_out, estimator_state=d_state)
         seq = np.repeat(xs[0][None, :1], 200, 0)[:, 0]
         cpu_all = lambda: O.estimator_run(cfg, seq, (1000 + 2 * np.arange(200)).astype(np.uint32))
         cpu = None
@@ -203,6 +235,7 @@ def side_mode(args, pkg, ctx):
         d_traj, d_gait = D_.zeros((12 * h, n)), D_.zeros((4 * h, n))
         d_cmd, d_u = D_.zeros((67, n)), D_.zeros((n,), np.int32)
         step = lambda: ctx.mpc_frontend_batch(n, d_in, d_st, d_traj, d_gait, d_cmd, d_u)
+        outputs = dict(traj=d_traj, gait=d_gait, wbc_cmd=d_cmd, mpc_update=d_u)
         cpu = lambda i: O.mpc_frontend(h, 2, vin[i], st[i])
         alg_bytes = (64 + 8 + 8 + 16 * h + 19 + 1) * 4
         metric, unit, kernel = "MPC front-end robot-ticks/s (batched robots)", "robot-ticks/s", "qr_frontend_kernel"
@@ -218,17 +251,23 @@ def side_mode(args, pkg, ctx):
     ctx.sync()
     elapsed = time.perf_counter() - t0
     kernel_ms = ctx.mark_elapsed_ms(0, 1) / args.steps
-    # CPU restatement, one thread, bounded sample
-    m = min(n, 2000)
-    c0 = time.perf_counter()
-    if cpu is None:
-        for _ in range(10):
-            cpu_all()
-        m = 2000
-    else:
-        for i in range(m):
-            cpu(i)
-    cpu_rate = m / (time.perf_counter() - c0)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {k: a.download() for k, a in outputs.items()})
+    # CPU restatement, one thread, bounded sample (--full)
+    cpu_baseline_ = None
+    if args.full:
+        m = min(n, 2000)
+        c0 = time.perf_counter()
+        if cpu is None:
+            for _ in range(10):
+                cpu_all()
+            m = 2000
+        else:
+            for i in range(m):
+                cpu(i)
+        cpu_rate = m / (time.perf_counter() - c0)
+        cpu_baseline_ = {"value": cpu_rate, "unit": unit, "cores": 1, "kind": "port",
+                         "sample": "%d robot-ticks through the oracle's C++ restatement via ctypes, one thread" % m}
     gbs = alg_bytes * n / (kernel_ms * 1e-3) / 1e9
     out = {"metric": metric, "value": n * args.steps / elapsed, "unit": unit, "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
            "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -238,9 +277,9 @@ def side_mode(args, pkg, ctx):
                       "robots_per_gpu": n},
            "roofline": {"bound": "hbm", "kernel": kernel, "achieved": gbs, "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": gbs / PEAK_HBM_GBS, "traffic": None,
                         "kernel_ms": kernel_ms, "algorithmic_bytes_per_robot": alg_bytes, "algorithmic_flop_per_robot": alg_flop,
-                        "note": "launch- and latency-bound at this batch size, not bandwidth-bound"},
-           "cpu_baseline": {"value": cpu_rate, "unit": unit, "cores": 1, "kind": "port",
-                            "sample": "%d robot-ticks through the oracle's C++ restatement via ctypes, one thread" % m}}
+                        "note": "launch- and latency-bound at this batch size, not bandwidth-bound"}}
+    if cpu_baseline_ is not None:
+        out["cpu_baseline"] = cpu_baseline_
     return out
 
 
@@ -256,7 +295,7 @@ def single_mode(args, pkg):
     per call, p50 / p99 over `--steps` calls (>= 1000) at h = 5 (the reference's hard-coded planning horizon,
     qr_mpc_stance_leg_controller.cpp:42), 10 and 16: (a) through the Python mirror of the reference interface (ctypes: a few us of
     interpreter per call on top), (b) through the C++ adapters of include/qrgpu_adapters.hpp in a compiled program (tests/stubs/adapter_demo
-    --latency), which is what a maintainer's build would run.  Beside them the reference's own solver (qpOASES 3.2.0 from the reference tree, as
+    --latency), which is what a maintainer's build would run.  With --full, beside them the reference's own solver (qpOASES 3.2.0 from the reference tree, as
     called) and the port's CPU tick on the same inputs, one thread."""
     import subprocess
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -304,25 +343,26 @@ def single_mode(args, pkg):
             w = line.split()
             if w and w[0] in ("latency_mpc_us", "latency_wbc_us"):
                 r["adapters_%s" % w[0][8:11]] = dict(p50_us=float(w[1]), p99_us=float(w[2]), mean_us=float(w[3]), min_us=float(w[4]), calls=calls)
-        # the CPU side on the same 16 QPs, one thread
-        A = O.mpc_constraint_matrix(h, float(cfg[1]))
-        t_ref = t_port = t_wbc = 0.0
-        capped = 0
-        for i in range(16):
-            H, g, ub = O.mpc_assemble(cfg, h, b["mpc_state"][i], b["traj"][i], b["gait"][i])
-            if O.ref() is not None:
+        # the CPU side on the same 16 QPs, one thread (--full)
+        if args.full:
+            A = O.mpc_constraint_matrix(h, float(cfg[1]))
+            t_ref = t_port = t_wbc = 0.0
+            capped = 0
+            for i in range(16):
+                H, g, ub = O.mpc_assemble(cfg, h, b["mpc_state"][i], b["traj"][i], b["gait"][i])
+                if O.ref() is not None:
+                    t0 = time.perf_counter()
+                    x, info = O.ref_qpoases_mpc(H.astype(np.float64), g.astype(np.float64), A, np.zeros(20 * h), ub.astype(np.float64), 100)
+                    t_ref += time.perf_counter() - t0
+                    capped += int(info["nWSR"] >= 100 or info["init_rc"] != 0)
                 t0 = time.perf_counter()
-                x, info = O.ref_qpoases_mpc(H.astype(np.float64), g.astype(np.float64), A, np.zeros(20 * h), ub.astype(np.float64), 100)
-                t_ref += time.perf_counter() - t0
-                capped += int(info["nWSR"] >= 100 or info["init_rc"] != 0)
-            t0 = time.perf_counter()
-            O.mpc_solve(cfg, h, b["mpc_state"][i], b["traj"][i], b["gait"][i])
-            t_port += time.perf_counter() - t0
-            t0 = time.perf_counter()
-            O.wbc_run(md, b["fb_state"][i], b["wbc_cmd"][i], dtype=np.float32)
-            t_wbc += time.perf_counter() - t0
-        r["cpu"] = dict(reference_qpoases_as_called_ms=(1e3 * t_ref / 16) if O.ref() is not None else None, reference_hit_nwsr_100=capped,
-                        port_mpc_assemble_solve_ms=1e3 * t_port / 16, port_wbc_tick_ms=1e3 * t_wbc / 16)
+                O.mpc_solve(cfg, h, b["mpc_state"][i], b["traj"][i], b["gait"][i])
+                t_port += time.perf_counter() - t0
+                t0 = time.perf_counter()
+                O.wbc_run(md, b["fb_state"][i], b["wbc_cmd"][i], dtype=np.float32)
+                t_wbc += time.perf_counter() - t0
+            r["cpu"] = dict(reference_qpoases_as_called_ms=(1e3 * t_ref / 16) if O.ref() is not None else None, reference_hit_nwsr_100=capped,
+                            port_mpc_assemble_solve_ms=1e3 * t_port / 16, port_wbc_tick_ms=1e3 * t_wbc / 16)
         res["h%d" % h] = r
     a10 = res["h10"]["adapters_mpc"]
     out = {"metric": "single-robot MPC solve latency through the drop-in adapters, h = 10 (p50)", "value": a10["p50_us"], "unit": "us", "n_gpus": 1,
@@ -432,7 +472,15 @@ def main():
                     help="K4 arithmetic: f32 = exact fp32 matrix instruction (default); bf16x3 = three-limb bf16 on the bf16 matrix cores (BASELINE.json configs[4])")
     ap.add_argument("--mixed", action="store_true",
                     help="BASELINE.json configs[4] per GPU: A1 and Lite3 interleaved (type_id per robot), usually with --horizon 16; mode tick only")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: CPU baseline, reference comparison, roofline, side measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (every mode but single)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.mode == "single":
+        ap.error("--dump-outputs: --mode single has no batched outputs")
 
     launched = "WORLD_SIZE" in os.environ
     if not launched and args.gpus > 1:
@@ -639,8 +687,8 @@ def main():
     # HIP events around the two kernels of every 8th step (every 4th / 2nd in shorter runs; on the context's stream).  Around every step they
     # cost 17 us of a 0.29 ms step (3.50 against 3.73 M ticks/s with none: QRGPU_BENCH_KERNEL_TIMING=0 / 1 / N for the A/B; every 4th 3.65, every
     # 8th 3.69 M)
-    # -- and only around timed steps (the warm-up steps of a draw start cold)
-    ktime = int(os.environ.get("QRGPU_BENCH_KERNEL_TIMING", "8" if args.steps >= 160 else "4"))
+    # -- and only around timed steps (the warm-up steps of a draw start cold); only the roofline block of --full reads them
+    ktime = int(os.environ.get("QRGPU_BENCH_KERNEL_TIMING", ("8" if args.steps >= 160 else "4") if args.full else "0"))
     ctx.enable_timing(0)
     if ktime:
         ctx.enable_timing(ktime); ctx.enable_timing(-1)        # the event pool is made here, paused: nothing of it inside a draw's barrier-to-barrier region
@@ -665,6 +713,18 @@ def main():
         own = d_tau_all.download()[rank]
         if not np.array_equal(own, d_tau2[last_slot()].download()):
             raise RuntimeError("rank %d: all-gathered torques differ from the local ones" % rank)
+    if args.dump_outputs and rank == 0:
+        # the last timed step's outputs, before anything of --full writes those arrays again
+        sl_ = last_slot()
+        dumped = {"tau": d_tau2[sl_].download(), "status": d_status2[sl_].download()}
+        if args.mode != "wbc":
+            dumped["force"] = d_force2[sl_].download()
+        if args.mode != "mpc":
+            dumped["qdes"] = d_qdes2[sl_].download()
+            dumped["prev_ori"] = d_prev.download()
+        if world > 1 or comm_on:
+            dumped["tau_all_ranks"] = d_tau_all.download()
+        dump_outputs(args.dump_outputs, dumped)
     mpc_ms, mpc_cnt = ctx.get_timing(0)
     wbc_ms, wbc_cnt = ctx.get_timing(1)
     if not mpc_cnt and not wbc_cnt: mpc_ms = wbc_ms = float("nan")            # (QRGPU_BENCH_KERNEL_TIMING=0)
@@ -722,7 +782,7 @@ def main():
 
     # executed arithmetic of the MPC kernel (qrgpu_enable_flop_count): four more, untimed, steps on draw 0 with the counters on
     flop = None
-    if args.mode != "wbc":
+    if args.full and args.mode != "wbc":
         timed(2, args.warmup, 0)
         ctx.enable_flop_count(True)
         acc = {}
@@ -764,7 +824,7 @@ def main():
                                  "the dominant launch's slot-time that is empty (coarse bin packing: ~2 rounds of solves of 40-140 us)"}
 
     side = {}
-    if world == 1 and not args.no_side and args.mode == "tick":
+    if args.full and world == 1 and not args.no_side and args.mode == "tick":
         ks = max(10, args.steps // 4)
         side["ticks_per_s_slot_order_dispatch"] = n * ks / timed(ks, 3, 0, lpt=False)          # no scheduling history at all
         side["ticks_per_s_without_k12"] = n * ks / timed(ks, args.warmup, 0, k12=False)
@@ -843,7 +903,9 @@ def main():
         # SURVEY 8(d)'s dense count with the change count this run measured (mean over the draws' last steps; a cold start takes 20.3)
         flop_dense = FLOP_K4_HESSIAN + FLOP_K4_GRADIENT + FLOP_K6_FACTOR + it_mean * FLOP_K6_PER_ITER
         traffic, traffic_src = committed_traffic("qr_mpc_kernel" if args.mode != "wbc" else "qr_wbc_kernel", n, h)
-        if args.mode == "wbc":
+        if not args.full:
+            roof = None
+        elif args.mode == "wbc":
             dom_ms, dom_name = wbc_ms, "qr_wbc_kernel"
             roof = {"bound": "latency", "kernel": dom_name, "achieved": FLOP_WBC * n / (dom_ms * 1e-3) / 1e12, "peak": PEAK_F64_VECTOR_TFLOPS, "unit": "TFLOP/s",
                     "frac": FLOP_WBC * n / (dom_ms * 1e-3) / 1e12 / PEAK_F64_VECTOR_TFLOPS, "traffic": traffic, "traffic_source": traffic_src,
@@ -916,10 +978,12 @@ def main():
                                        "`value` is a rate of ticks in flight -- config.tick_latency_ms is one tick on its own, config.ticks_per_s_no_tick_overlap the "
                                        "rate with every tick behind its predecessor's join" if overlap_on else ""),
                        "tick_overlap": bool(overlap_on),
+                       "full": bool(args.full),
                        **side},
-            "roofline": roof,
         }
-        if world == 1 and not args.no_cpu_baseline and args.mixed and args.mode == "tick":
+        if roof is not None:
+            out["roofline"] = roof
+        if args.full and world == 1 and not args.no_cpu_baseline and args.mixed and args.mode == "tick":
             # configs[4] per GPU: the CPU restatement type by type (it has one parameter set per call), and the error of this run's
             # arithmetic against the exact fp32 path on the same batch
             sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -956,7 +1020,7 @@ def main():
             cfgo["max_rel_force_err_vs_cpu"] = float((np.abs(fg - f_cpu).max(1) / np.maximum(1.0, np.abs(f_cpu).max(1)))[ok].max())
             cfgo["max_rel_torque_err_vs_fp32_path"] = float((np.abs(tg - res["f32"][1]) / np.maximum(1.0, np.abs(res["f32"][1]))).max())
             cfgo["robots_compared_with_cpu"] = int(ok.sum())
-        if world == 1 and not args.no_cpu_baseline and not args.mixed and args.mode != "wbc":
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.mixed and args.mode != "wbc":
             b0 = host0[0]
             out["cpu_baseline"] = cpu_baseline(pkg, b0, h, mode=0 if args.mode == "mpc" else 1)
             # BASELINE's metric quotes the torque error beside the rate: one more (untimed) call on draw 0's first batch from fresh WBC

@@ -229,7 +229,7 @@ int  qrgpu_set_tick_pipeline(qrgpu_ctx *ctx, int on);
  *       checks this: a tick that reuses any output array of its predecessor, or changes n or prev_ori, or follows any other launch of this
  *       context, is simply not chained -- it waits for the context's stream (an event) and runs as the pipelined tick always did.
  * Throughput, not latency: a chained tick completes LATER after its call than an unchained one (its join waits for a launch that shares the
- * machine with the next tick); bench.py prints both beside `value` (config.tick_latency_ms, config.ticks_per_s_no_tick_overlap).
+ * machine with the next tick); bench.py --full prints both beside `value` (config.tick_latency_ms, config.ticks_per_s_no_tick_overlap).
  * Call it AFTER the context's types are set up: the stream sets are made for the horizon the context has at the call (h <= 11: two lanes on the
  * whole machine; h > 11, from 3.5 robots per CU on: two lanes on a machine split by CU masks -- the main pass two to a CU on 192 CUs, the robots
  * that need a whole CU on 64 reserved ones); a context whose horizon changes class afterwards runs plain pipelined ticks until

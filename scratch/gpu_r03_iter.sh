@@ -5,7 +5,7 @@ OUT=gpurun_out/${1:-r03i}
 mkdir -p $OUT
 timeout -k 10 600 python -m pytest tests -m gpu -q -x > $OUT/pytest_gpu.log 2>&1; echo "pytest rc=$?"; tail -4 $OUT/pytest_gpu.log
 timeout -k 10 200 python scratch/diag_mpc_phases.py 1024 > $OUT/phases.txt 2>&1; echo "phases rc=$?"; head -12 $OUT/phases.txt
-timeout -k 10 400 python bench.py --no-cpu-baseline ${BENCH_ARGS:-} > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
+timeout -k 10 400 python bench.py --full --no-cpu-baseline ${BENCH_ARGS:-} > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
 python - <<PY
 import json
 d=json.load(open("$OUT/bench.json")); r=d["roofline"]; c=d["config"]

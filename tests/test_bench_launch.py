@@ -6,6 +6,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
 
@@ -89,3 +91,54 @@ def test_the_json_line_is_alone_on_stdout_even_when_a_library_writes_there():
         lines = [l for l in r.stdout.decode().splitlines() if l.strip()]
         assert len(lines) == 1 and json.loads(lines[0])["dry"] is True, lines
         assert b"banner on file descriptor 1" in r.stderr
+
+
+def test_dump_outputs_writes_float_arrays_and_keeps_under_the_cap(tmp_path):
+    """--dump-outputs: one .npy per array, float32 (float64 for fp64 state and integer words), robot on the last axis; over the cap a fixed,
+    seeded sample of robots with its indices -- the same sample on every run."""
+    import runpy
+    import numpy as np
+    dump = runpy.run_path(BENCH, run_name="bench")["dump_outputs"]
+    rng = np.random.default_rng(1)
+    small = {"tau": rng.random((12, 16), np.float32), "status": np.arange(16, dtype=np.int32), "state": rng.random((3, 16))}
+    dump(str(tmp_path / "a"), small)
+    got = {k: np.load(str(tmp_path / "a" / (k + ".npy"))) for k in small}
+    assert got["tau"].dtype == np.float32 and got["status"].dtype == np.float64 and got["state"].dtype == np.float64
+    assert all(np.array_equal(got[k], small[k]) for k in small)
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == ["state.npy", "status.npy", "tau.npy"]
+    big = {"tau": rng.random((12, 8192), np.float32), "status": np.arange(8192, dtype=np.int32)}
+    for d in ("b", "c"):
+        dump(str(tmp_path / d), big, limit=1 << 17)
+    files = list((tmp_path / "b").iterdir())
+    assert sum(p.stat().st_size for p in files) <= 1 << 17
+    idx = np.load(str(tmp_path / "b" / "robot_index.npy")).astype(np.int64)
+    assert 0 < idx.size < 8192 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(np.load(str(tmp_path / "b" / "tau.npy")), big["tau"][:, idx])
+    assert np.array_equal(np.load(str(tmp_path / "b" / "status.npy")), idx.astype(np.float64))
+    assert all(np.array_equal(np.load(str(p)), np.load(str(tmp_path / "c" / p.name))) for p in files)
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_asked_for_and_dumps_its_last_step(tmp_path):
+    """A plain run on the GPU: one JSON line with the headline keys and `steps` as asked, nothing of --full in it; --dump-outputs holds the
+    last timed step's outputs, and a second run with the same arguments writes the same arrays."""
+    import numpy as np
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "QRGPU_BENCH_DRY"):
+        env.pop(k, None)
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "10", "--warmup", "2", "--dump-outputs", str(tmp_path / d)], env=env,
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+        assert r.returncode == 0, r.stderr.decode()[-3000:]
+        lines = [l for l in r.stdout.decode().splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        out = json.loads(lines[0])
+        assert all(k in out for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"))
+        assert out["steps"] == 10 and out["warmup"] == 2 and out["value"] > 0 and out["ms_per_step"] > 0
+        assert "roofline" not in out and "cpu_baseline" not in out and out["config"]["full"] is False
+    n = out["config"]["robots_per_gpu"]
+    for k, shape in (("force", (12, n)), ("tau", (12, n)), ("qdes", (24, n)), ("status", (n,)), ("prev_ori", (3, n))):
+        a, b = np.load(str(tmp_path / "a" / (k + ".npy"))), np.load(str(tmp_path / "b" / (k + ".npy")))
+        assert a.shape == shape and a.dtype in (np.float32, np.float64) and np.all(np.isfinite(a)), k
+        assert np.array_equal(a, b), k
+    assert np.abs(np.load(str(tmp_path / "a" / "tau.npy"))).max() > 0

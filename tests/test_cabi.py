@@ -3,6 +3,8 @@ No compute call is made here (there is no GPU); creating a context must fail lou
 import ctypes as C
 import os
 import re
+import subprocess
+import sys
 
 import numpy as np
 
@@ -41,8 +43,12 @@ def test_no_cpu_fallback(pkg, monkeypatch):
     with pytest.raises(pkg.MissingExtension):
         pkg.qrgpu.load_library()
     monkeypatch.undo()
-    import torch
-    if not torch.cuda.is_available():
+    # torch is asked in a child process: it brings a HIP runtime of its own, and once that is up in this process the library's runtime
+    # cannot open the device -- every GPU test after this one in the same session would fail with NO_DEVICE
+    r = subprocess.run([sys.executable, "-c", "import torch; print(int(torch.cuda.is_available()))"], stdout=subprocess.PIPE,
+                       stderr=subprocess.PIPE, timeout=300)
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    if r.stdout.split()[-1] == b"0":
         with pytest.raises(pkg.QrgpuError):
             pkg.Context(device_id=0, max_batch=4)
 

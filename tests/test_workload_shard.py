@@ -72,7 +72,10 @@ def _gloo_worker(rank, world, port, n_total, q):
 
 @pytest.mark.parametrize("n_total", [64, 37])
 def test_allgather_torques_world2_gloo(n_total):
-    import torch.multiprocessing as mp
+    # the standard library's spawn context, not torch's: the workers import torch in fresh interpreters, and this process must not load it --
+    # torch brings a HIP runtime of its own (the same soname as the one libqrgpu.so links), and in a session that also runs the GPU tests the
+    # two clash (a bad free() when the process exits)
+    import multiprocessing as mp
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
