@@ -203,7 +203,7 @@ int  qrgpu_set_planned_list(qrgpu_ctx *ctx, int on, int big_nls);
 /* Rescue pass of the batched MPC solve (default on).  A working set that outgrows the 64 lanes of the four-wave loop is handed over
  * in place to the single-wave loop (up to 96 rows) -- that needs no switch.  What remains are robots limited by LDS (an all-stance inverse
  * Hessian at h = 10 leaves room for 56 rows): they are re-solved by the same kernel with the whole CU's LDS in a second, normally
- * empty launch, at most 64 robots per call (the rest keep QRGPU_ST_MPC_OVERFLOW), h <= 11 and the two-workgroups-per-CU main pass of h > 11 (otherwise at h = 16 such robots keep S^-1 in a global scratch instead).
+ * empty launch, at most 64 robots per call (the rest keep QRGPU_ST_MPC_OVERFLOW), h <= 11 and the two-workgroups-per-CU main pass of h > 11 (otherwise at h > 11 such robots keep S^-1 in a global scratch instead).
  * A robot nothing can hold keeps QRGPU_ST_MPC_OVERFLOW. */
 int  qrgpu_set_rescue_pass(qrgpu_ctx *ctx, int on);
 /* Pipelined tick (default on; batches of 64 robots and more): qrgpu_tick_batch queues its WBC launch on a stream of the context's own

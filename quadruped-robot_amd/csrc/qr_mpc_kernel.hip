@@ -487,7 +487,9 @@ __device__ __forceinline__ void mpc_solve_robot(const MpcLaunch &P, const MpcIO 
             if (P.sinv_spill && m_fits) { Sinv = (SinvPtr)(P.sinv_spill + (size_t)rid * (size_t)tri(QR_QH)); qcap = want; spilled = true; }
             else qcap = 0;                      // (to the list launches, below)
         } else {
-            if (P.sinv_spill && m_fits && qcap < want && qcap < 64) { Sinv = (SinvPtr)(P.sinv_spill + (size_t)rid * (size_t)tri(QR_QH)); qcap = want; spilled = true; }
+            // (whenever the LDS behind M holds fewer rows than the robot may need: the one-workgroup-per-CU main pass of h > 11 has no list launch
+            //  behind it, so a working set that outgrew an LDS-held S^-1 of 64..95 rows -- h = 15 all stance: 68 -- was left flagged, unsolved)
+            if (P.sinv_spill && m_fits && qcap < want) { Sinv = (SinvPtr)(P.sinv_spill + (size_t)rid * (size_t)tri(QR_QH)); qcap = want; spilled = true; }
         }
     }
     // What is left behind S^-1 caches W_A = M N_A, one 3*nls vector per working-set position (the `w` of the iteration that added it),

@@ -36,12 +36,11 @@ def _ulp_close(a, b, ulps=1):
     return np.all(np.abs(a - b) <= ulps * np.spacing(np.maximum(np.abs(a), np.abs(b))))
 
 
-@pytest.mark.parametrize("h,L", [(10, 2), (5, 2), (16, 3)])
-def test_frontend_parity(gpu_ctx, pkg, oracle, h, L):
-    setup_a1(gpu_ctx, pkg, h)
-    n = 1000                                   # not a multiple of the block size: ragged tail
-    fe, st = pkg.workload.make_frontend_batch(n, seed=h)
-    g = _run_gpu(gpu_ctx, pkg, fe, st, h, L)
+def frontend_parity(ctx, pkg, oracle, h, L, n=1000, seed=None):
+    """Every robot of one qrgpu_mpc_frontend_batch call against the oracle: bit-exact but for the sin rows (1 ulp)."""
+    setup_a1(ctx, pkg, h)
+    fe, st = pkg.workload.make_frontend_batch(n, seed=h if seed is None else seed)
+    g = _run_gpu(ctx, pkg, fe, st, h, L)
     exact_cmd = [r for r in list(range(15)) + [63, 64, 65, 66] if r not in SIN_CMD_ROWS]
     exact_traj = [c for c in range(12) if c not in SIN_TRAJ_COLS]
     n_upd = 0
@@ -63,6 +62,11 @@ def test_frontend_parity(gpu_ctx, pkg, oracle, h, L):
         else:
             assert np.isnan(tg).all()                                   # no re-plan: trajectory left alone
     assert 0 < n_upd < n
+
+
+@pytest.mark.parametrize("h,L", [(10, 2), (5, 2), (16, 3)])
+def test_frontend_parity(gpu_ctx, pkg, oracle, h, L):
+    frontend_parity(gpu_ctx, pkg, oracle, h, L, n=1000)          # (1000: not a multiple of the block size, a ragged tail)
 
 
 def test_frontend_sequence_feeds_tick(gpu_ctx, pkg, oracle):

@@ -443,6 +443,13 @@ def test_plan_survives_single_robot_and_small_calls_in_between(gpu_ctx, pkg, ora
 
 @pytest.mark.parametrize("h,n,mixed", [(10, 256, False), (16, 1024, True)])
 def test_bf16x3_solve_vs_oracle_on_its_own_hessian(gpu_ctx, pkg, oracle, h, n, mixed):
+    """BASELINE.json configs[4]'s arithmetic, held by bf16x3_vs_oracle (below); the mode really is another arithmetic: more than half the Hessians
+    differ from the exact fp32 assembly."""
+    differs = bf16x3_vs_oracle(gpu_ctx, pkg, oracle, h, n, mixed)
+    assert differs > n // 2                                                      # (it really is another arithmetic)
+
+
+def bf16x3_vs_oracle(gpu_ctx, pkg, oracle, h, n, mixed):
     """BASELINE.json configs[4]'s arithmetic ("fp32 QP + bf16 Hessian MFMA"): the Hessian contraction of qr_mpc_interface.cpp:396-412 on
     v_mfma_f32_16x16x32_bf16 with three bf16 limbs per fp32 operand, on the configs[4] per-GPU shard (512 A1 + 512 Lite3 interleaved, h = 16)
     and on configs[1]'s size (256 A1, h = 10).  The mode is ANOTHER ROUNDING of H -- within an ulp or two of the exact fp32 assembly, not
@@ -489,9 +496,9 @@ def test_bf16x3_solve_vs_oracle_on_its_own_hessian(gpu_ctx, pkg, oracle, h, n, m
             et = np.abs(out["tau"][i] - tau_o) / np.maximum(1.0, np.abs(tau_o))
             worst_t = max(worst_t, et.max())
             assert np.all(et <= 1e-4), (i, et.max(), st)
-        assert differs > n // 2                                                      # (it really is another arithmetic)
         print("bf16x3 h=%d n=%d: worst rel force %.2e, worst rel full-tick torque %.2e vs the oracle on the mode's own (H, g); %d of %d Hessians differ "
               "from the exact fp32 assembly" % (h, n, worst_f, worst_t, differs, n))
+        return differs
     finally:
         gpu_ctx.set_hessian_mode("f32")
         gpu_ctx.set_torque_epilogue(False, False)

@@ -51,20 +51,43 @@ def _dense_float64_qp(cfg, h, s, traj, gait):
     return H, g
 
 
+def _gait_mix(b):
+    """The gait classes whose QPs differ in shape: robot 0 keeps its drawn (trot) table, then all stance, three legs, flight, and flight now /
+    stance later (first-step forces 0, the QP not empty; at h = 1 that robot is in flight too)."""
+    n, h = b["n"], b["horizon"]
+    g = b["gait"].reshape(n, h, 4).copy()
+    g[1] = 1.0
+    g[2] = 1.0; g[2, :, 2] = 0.0
+    g[3] = 0.0
+    g[4] = 0.0; g[4, (h + 1) // 2:, :] = 1.0
+    b["gait"] = g.reshape(n, 4 * h)
+    return b
+
+
+def _check_assembly_vs_float64(oracle, pkg, h, seed):
+    cfg = pkg.mpc_cfg("a1")
+    b = pkg.make_batch(3, h, "a1", seed=seed)
+    for i in range(3):
+        H, g, ub = oracle.mpc_assemble(cfg, h, b["mpc_state"][i], b["traj"][i], b["gait"][i])
+        H64, g64 = _dense_float64_qp(cfg, h, b["mpc_state"][i], b["traj"][i], b["gait"][i])
+        assert np.abs(H - H64).max() <= 3e-6 * np.abs(H64).max()
+        assert np.abs(g - g64).max() <= 3e-6 * np.abs(g64).max()
+        # literal fp32 route (Pade expm + repeated products) agrees to fp32 rounding as well
+        Hl, gl, _ = oracle.mpc_assemble(cfg, h, b["mpc_state"][i], b["traj"][i], b["gait"][i], literal=True)
+        assert np.abs(Hl - H64).max() <= 5e-6 * np.abs(H64).max()
+        assert np.array_equal(ub.reshape(-1, 5)[:, 4], b["gait"][i] * cfg[2]) and np.all(ub.reshape(-1, 5)[:, :4] == np.float32(5e10))
+
+
 def test_assembly_matches_float64_dense_formula(oracle, pkg):
     """Closed-form fp32 assembly == literal dense float64 evaluation (expm + powers) to fp32 rounding."""
-    cfg = pkg.mpc_cfg("a1")
     for h, seed in ((10, 5), (5, 6), (16, 7)):
-        b = pkg.make_batch(3, h, "a1", seed=seed)
-        for i in range(3):
-            H, g, ub = oracle.mpc_assemble(cfg, h, b["mpc_state"][i], b["traj"][i], b["gait"][i])
-            H64, g64 = _dense_float64_qp(cfg, h, b["mpc_state"][i], b["traj"][i], b["gait"][i])
-            assert np.abs(H - H64).max() <= 3e-6 * np.abs(H64).max()
-            assert np.abs(g - g64).max() <= 3e-6 * np.abs(g64).max()
-            # literal fp32 route (Pade expm + repeated products) agrees to fp32 rounding as well
-            Hl, gl, _ = oracle.mpc_assemble(cfg, h, b["mpc_state"][i], b["traj"][i], b["gait"][i], literal=True)
-            assert np.abs(Hl - H64).max() <= 5e-6 * np.abs(H64).max()
-            assert np.array_equal(ub.reshape(-1, 5)[:, 4], b["gait"][i] * cfg[2]) and np.all(ub.reshape(-1, 5)[:, :4] == np.float32(5e10))
+        _check_assembly_vs_float64(oracle, pkg, h, seed)
+
+
+@pytest.mark.parametrize("h", range(1, 17))
+def test_assembly_matches_float64_dense_formula_every_horizon(oracle, pkg, h):
+    """The same at every horizon the C ABI accepts (other draws than above)."""
+    _check_assembly_vs_float64(oracle, pkg, h, 0x400 + h)
 
 
 def test_golden_mpc_vs_reference_qpoases(oracle, pkg):
@@ -155,6 +178,27 @@ def test_live_qpoases_symmetric(ref, pkg):
         x, info = ref.ref_qpoases_mpc(0.5 * (Hd + Hd.T), g.astype(np.float64), A, np.zeros(200), ub, nWSR=2000)
         assert info["init_rc"] == 0 and rc == 0
         assert np.abs(u - x).max() <= 1e-7 * max(1.0, np.abs(x).max())
+
+
+@pytest.mark.parametrize("h", range(1, 17))
+def test_solve_vs_qpoases_every_horizon(ref, pkg, h):
+    """The oracle's solver against the compiled qpOASES on the symmetrised data (nWSR 2000), at every horizon, over trot, all stance, three
+    legs, flight and flight now / stance later: the bound of test_live_qpoases_symmetric, the friction pyramid and zero swing forces."""
+    cfg = pkg.mpc_cfg("a1")
+    b = _gait_mix(pkg.make_batch(5, h, "a1", seed=0x500 + h))
+    A = ref.mpc_constraint_matrix(h, float(cfg[1]))
+    for i in range(5):
+        H, g, ub = ref.mpc_assemble(cfg, h, b["mpc_state"][i], b["traj"][i], b["gait"][i])
+        u, st, rc = ref.mpc_solve(cfg, h, b["mpc_state"][i], b["traj"][i], b["gait"][i])
+        Hd = H.astype(np.float64)
+        x, info = ref.ref_qpoases_mpc(0.5 * (Hd + Hd.T), g.astype(np.float64), A, np.zeros(20 * h), ub, nWSR=2000)
+        assert info["init_rc"] == 0 and rc == 0, (h, i, info, rc)
+        assert np.abs(u - x).max() <= 1e-7 * max(1.0, np.abs(x).max()), (h, i, np.abs(u - x).max())
+        f = u.reshape(4 * h, 3); gt = b["gait"][i]
+        assert np.all(f[gt == 0] == 0)
+        assert np.all(f[:, 2] >= -1e-9) and np.all(f[:, 2] <= np.float64(cfg[2]) * gt + 1e-7)
+        assert np.all(np.abs(f[:, 0]) <= 0.45 * f[:, 2] + 1e-7) and np.all(np.abs(f[:, 1]) <= 0.45 * f[:, 2] + 1e-7)
+    assert np.all(b["gait"][3] == 0) and np.all(b["gait"][1] == 1)
 
 
 def test_swing_variables_are_zero_and_constraints_hold(oracle, pkg):
