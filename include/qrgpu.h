@@ -448,6 +448,74 @@ void qrgpu_foothold_desc_default(qrgpu_foothold_desc *d);
 int qrgpu_footholds_batch(qrgpu_ctx *ctx, int n, const qrgpu_foothold_desc *desc, const float *d_fh_in, const float *d_gait_state,
                           const float *d_gait_out, float *d_swing_in);
 
+/* Swing-leg controller of the walk and position modes, and the lift-off memory of all four modes (qrRaibertSwingLegController::Reset /
+ * Update / GetAction, QS/controllers/qr_swing_leg_controller.cpp:60-101,104-229,241-461, with qrFootholdPlanner::Reset / UpdateOnce,
+ * QS/planner/qr_foothold_planner.cpp:49-109, and qrFootStepper's gap-crossing plan, QS/planner/qr_foot_stepper.cpp:31-202,483-525).
+ * Modes are LocomotionMode: VELOCITY 0, POSITION 1, WALK 2, ADVANCED_TROT 3; terrains TerrainType: PLANE 0, PLUM_PILES 1, STAIRS 2,
+ * SLOPE 3, ROUGH 4 (config/qr_enum_types.h:62-92).
+ * Inputs are the arrays the device already holds: est_in (quat_wxyz rows 6-9, motor angles 17-28), est_out (footPositionsInBaseFrame
+ * rows 12-23, basePosition 36-38) and the gait generator's output: for WALK the [QRGPU_WALK_OUT_ROWS][n] output of
+ * qrgpu_walk_gait_update_batch, for the other modes the [24][n] output of qrgpu_gait_update_batch with its [QRGPU_GAIT_STATE_FLOATS][n]
+ * state (allowSwitchLegState; read by the position mode's action only).  Both outputs keep desiredLegState in rows 8-11, legState in
+ * 12-15, curLegState in 16-19 and normalizedPhase in 4-7; the walk output's detectedLegState is rows 20-23.
+ * d_swing_state [QRGPU_SWING_STATE_FLOATS][n] is the controller's memory:
+ *   0-11  phaseSwitchFootLocalPos (3*leg+axis)        12-23 phaseSwitchFootGlobalPos      24-35 footHoldInWorldFrame
+ *   36-47 walk trajectory source                      48-59 walk trajectory target        60-63 walk trajectory height (stepParams.height)
+ *   64    walk trajectory built, bit per leg          65-76 last joint angle targets      77-88 last joint velocity targets
+ *   89    swingJointAnglesVelocities entry, bit per leg                                   90-101 desiredFootholdsOffset (3*leg+axis)
+ *   102   stepper flags: 1 generatorFlag, 2 gaitFlag  103 / 104 plan queue head / tail    105-... plan queue, 4 floats per step
+ * d_swing_flags: one word per robot of QRGPU_SW_* bits (not the tick's status word), cleared by a reset, OR-ed by both calls: the cases in
+ * which the reference is undefined or ends the process.  The plan keeps the steps made before QRGPU_SW_PLAN_EXIT / _FULL; a -1 shift on an
+ * empty plan shifts the planning position only.
+ * Deliberate readings: the unqualified abs on floats (qr_foot_trajectory_generator.cpp:100,105,123,298, qr_foot_stepper.cpp:150) is
+ * std::abs(float); CheckSolution's QP is QuadProg++'s Goldfarb-Idnani iteration for one variable, step for step; MAXIMUM_STEP = 0.001
+ * (config/qr_config.h:43) is kept, so every step that meets a gap returns -1 or -2 as in the reference. */
+#define QRGPU_MODE_VELOCITY 0
+#define QRGPU_MODE_POSITION 1
+#define QRGPU_MODE_WALK 2
+#define QRGPU_MODE_ADVANCED_TROT 3
+#define QRGPU_SWING_MAX_GAPS 8
+#define QRGPU_SWING_MAX_PLAN 32
+#define QRGPU_SWING_STATE_FLOATS (105 + 4 * QRGPU_SWING_MAX_PLAN)
+#define QRGPU_SWING_OUT_ROWS 52
+#define QRGPU_SW_NO_TRAJECTORY 0x1   /* a WALK leg swings before a lift-off built its trajectory (the reference reads an unset generator) */
+#define QRGPU_SW_PHASE_RANGE   0x2   /* a WALK phase outside [-1e-3, 1 + 1e-3): GenerateTrajectory fails and GetAction throws (:352-354) */
+#define QRGPU_SW_PLAN_EXIT     0x4   /* StepGenerator returned -2: exit(-1) in GetOptimalFootholdsOffset (:501-503) */
+#define QRGPU_SW_PLAN_EMPTY    0x8   /* a -1 cross-gait shift before any step was planned: steps.back() on an empty queue (:505-507) */
+#define QRGPU_SW_PLAN_FULL     0x10  /* the plan needs more than QRGPU_SWING_MAX_PLAN steps */
+typedef struct {
+    int   mode, terrain, is_sim;      /* controlParams["mode"]; TerrainType after the ground estimator's Reset
+                                         (qr_ground_surface_estimator.cpp:73-100: POSITION forces PLUM_PILES); robot->isSim */
+    float foothold_delta;             /* qrFootStepper defaultFootholdDelta: 0.10 (qr_foothold_planner.cpp:44) */
+    int   n_gaps;                     /* terrain.yaml gaps, read on PLUM_PILES only (a1_sim: 0.51, 1.31, 1.91, gap_width 0.14) */
+    float gap_distance[QRGPU_SWING_MAX_GAPS], gap_width;
+} qrgpu_swing_mode_desc;
+/* mode's defaults for config/a1_sim: POSITION on PLUM_PILES with a1_sim's gaps, WALK on SLOPE (terrain.yaml), VELOCITY on SLOPE,
+ * ADVANCED_TROT on STAIRS; is_sim 1 */
+void qrgpu_swing_mode_desc_default(qrgpu_swing_mode_desc *d, int mode);
+/* Reset (reset: 2 = as constructed, 1 = Reset(), which keeps the stepper's plan and flags and the walk trajectories, 0 = carry on) and
+ * Update for one control tick.  The first call on a state array must use reset = 2 (the plan queue's head and tail are clamped to the
+ * array, so an uninitialised one gives wrong footholds, not a wrong address).  Lift-off triggers: POSITION SWING / USERDEFINED_SWING from STANCE, WALK TRUE_SWING / USERDEFINED_SWING
+ * from UNLOAD_FORCE (both not while robot_stop), VELOCITY / ADVANCED_TROT a change to SWING.  POSITION plans the footholds of all legs at
+ * leg 0's lift-off (the gap plan is made once per constructed controller), WALK builds the leg's B-spline (source and target in the world
+ * frame when is_sim, else in the base frame).  For VELOCITY and ADVANCED_TROT, when given, the rows the existing kernels read receive the
+ * lift-off point at every reset and lift-off: d_swing_in rows 12-23 (phaseSwitchFootGlobalPos = baseRMat * local, no translation, as
+ * :186 has it), d_swing_vel_in rows 8-19 (phaseSwitchFootLocalPos) and d_fe_in rows 62-63 (firstSwingBaseState x, y: at a reset, and at
+ * ADVANCED_TROT lift-offs); other rows are left alone.  d_gait_state is not read (may be NULL). */
+int qrgpu_swing_update_batch(qrgpu_ctx *ctx, int n, const qrgpu_swing_mode_desc *desc, int reset, int robot_stop, const float *d_est_in,
+                             const float *d_est_out, const float *d_gait_out, const float *d_gait_state, float *d_swing_state,
+                             float *d_swing_in, float *d_swing_vel_in, float *d_fe_in, int *d_swing_flags);
+/* GetAction of the POSITION and WALK modes (VELOCITY and ADVANCED_TROT have qrgpu_swing_velocity_batch / qrgpu_swing_targets_batch):
+ * swing-leg selection (:204-229), POSITION's XY-linear / Z-parabola between the world lift-off point and footHoldInWorldFrame at the
+ * warped phase, WALK's B-spline at normalizedPhase (velocity per unit phase, as the reference's), the frame change RigidTransform, leg IK
+ * and J^-1 v (a NaN angle keeps the current one), and the command loop over the swingJointAnglesVelocities entries (:427-459).
+ * d_out [QRGPU_SWING_OUT_ROWS][n]: foot position in the base frame[12], foot velocity in the base frame[12], joint angle targets[12],
+ * joint velocity targets[12] (3*leg+axis), command flags[4].  The flags are written for every leg; the other rows for the legs this call
+ * computed (rows 0-47) or commands (rows 24-47: an entry of an earlier swing re-emits its last targets).  geom: leg lengths and hip offsets. */
+int qrgpu_swing_action_batch(qrgpu_ctx *ctx, int n, const qrgpu_swing_mode_desc *desc, const qrgpu_estimator_desc *geom, int robot_stop,
+                             const float *d_est_in, const float *d_est_out, const float *d_gait_out, const float *d_gait_state,
+                             float *d_swing_state, float *d_out, int *d_swing_flags);
+
 /* The tick's state arrays from the estimator's inputs and outputs: what SolveDenseMPC (qr_mpc_stance_leg_controller.cpp:385-399:
  * pos, baseVInWorldFrame, quat, baseWInWorldFrame, foot2ComInWorldFrame = baseRMat (footPositionsInBaseFrame - comOffset), rpy) and
  * qrWbcLocomotionController::UpdateModel (qr_wbc_locomotion_controller.cpp:136-156) read.  d_rpy [3][n] = GetBaseRollPitchYaw.

@@ -187,6 +187,16 @@ struct GaitDesc {
 // Velocity-mode swing action parameters (qrgpu_swing_velocity_desc)
 struct SwingVelDesc { float hip_pos_com[12], stance_duration[4], swing_kp[3], desired_height; };
 
+// Swing-leg controller of the walk and position modes, and the lift-off memory of every mode (qrgpu_swing_mode_desc)
+#define QR_SWING_MAX_GAPS 8
+#define QR_SWING_MAX_PLAN 32
+struct SwingModeDesc {
+    int mode, terrain, is_sim;
+    float foothold_delta;
+    int n_gaps;
+    float gap_distance[QR_SWING_MAX_GAPS], gap_width;
+};
+
 // Walk gait generator parameters after the constructor's bookkeeping (qrgpu_walk_gait_desc -> qrgpu_api.hip)
 struct WalkDesc {
     float duty_factor[4], initial_leg_phase[4], full[4];

@@ -375,18 +375,7 @@ __global__ void __launch_bounds__(64) qr_swing_kernel(int n, EstimatorDesc D, co
             for (int r = 0; r < 3; ++r) g_tgt_world[(size_t)(3 * leg + r) * N + i] = (R[r][0] * tg[0] + R[r][1] * tg[1] + R[r][2] * tg[2]) + bp[r];
         }
         float pw[3] = {0.f, 0.f, 0.f};
-        if (!((double)phase < 0.0 - 1e-3) && !((double)phase >= 0.0 + 1.0 + 1e-3)) {
-            pw[0] = (1 - phase) * st[0] + phase * tg[0];
-            pw[1] = (1 - phase) * st[1] + phase * tg[1];
-            const float mid = (tg[2] > st[2] ? tg[2] : st[2]) + 0.1f;
-            if (!(phase < 0.f)) {
-                const float d1 = mid - st[2], d2 = tg[2] - st[2];
-                const float d3 = (float)(0.25 - 0.5);
-                const float ca = (d1 - d2 * 0.5f) / d3;
-                const float cb = (float)(((double)d2 * 0.25 - (double)d1) / (double)d3);
-                pw[2] = (float)((double)ca * ((double)phase * (double)phase) + (double)(cb * phase) + (double)st[2]);
-            }
-        }
+        swing_parabola_point(phase, st, tg, pw);
         float vb[3] = {0.f, 0.f, 0.f};
         if ((double)phase < 1.0) {
 #pragma unroll
@@ -402,23 +391,9 @@ __global__ void __launch_bounds__(64) qr_swing_kernel(int n, EstimatorDesc D, co
         }
         if (g_qdes) {
             const float sh = D.hip_l * ((leg & 1) ? 1.f : -1.f);
-            const float x = pw[0] - D.hip_offset[3 * leg], y = pw[1] - D.hip_offset[3 * leg + 1], z = pw[2] - D.hip_offset[3 * leg + 2];
-            const float lu = D.upper_l, ll = D.lower_l;
-            const float tK = -acosf(((x * x + y * y + z * z) - (sh * sh + lu * lu + ll * ll)) / (2 * ll * lu));
-            const float l = sqrtf(lu * lu + ll * ll + 2 * lu * ll * cosf(tK));
-            const float tH = asinf(-x / l) - tK / 2;
-            const float c1 = sh * y - l * cosf(tH + tK / 2) * z;
-            const float s1 = l * cosf(tH + tK / 2) * y + sh * z;
-            const float tA = atan2f(s1, c1);
-            const float ang[3] = {tA, tH, tK};
-            float J[3][3];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) leg_jacobian_column(j, tA, tH, tK, sh, lu, ll, J[0][j], J[1][j], J[2][j]);
-            const float det = J[0][0] * (J[1][1] * J[2][2] - J[1][2] * J[2][1]) - J[0][1] * (J[1][0] * J[2][2] - J[1][2] * J[2][0]) + J[0][2] * (J[1][0] * J[2][1] - J[1][1] * J[2][0]);
-            const float id = 1.f / det;
-            const float Ji[3][3] = {{(J[1][1] * J[2][2] - J[1][2] * J[2][1]) * id, (J[0][2] * J[2][1] - J[0][1] * J[2][2]) * id, (J[0][1] * J[1][2] - J[0][2] * J[1][1]) * id},
-                                    {(J[1][2] * J[2][0] - J[1][0] * J[2][2]) * id, (J[0][0] * J[2][2] - J[0][2] * J[2][0]) * id, (J[0][2] * J[1][0] - J[0][0] * J[1][2]) * id},
-                                    {(J[1][0] * J[2][1] - J[1][1] * J[2][0]) * id, (J[0][1] * J[2][0] - J[0][0] * J[2][1]) * id, (J[0][0] * J[1][1] - J[0][1] * J[1][0]) * id}};
+            float ang[3], Ji[3][3];
+            leg_ik(pw, &D.hip_offset[3 * leg], sh, D.upper_l, D.lower_l, ang);
+            leg_jacobian_inverse(ang, sh, D.upper_l, D.lower_l, Ji);
 #pragma unroll
             for (int r = 0; r < 3; ++r) {
                 float a = ang[r];
@@ -875,43 +850,16 @@ __global__ void __launch_bounds__(64) qr_swing_velocity_kernel(int n, EstimatorD
         }
         const float st[3] = {IN(8 + 3 * leg), IN(9 + 3 * leg), IN(10 + 3 * leg)};
         const float inputPhase = IN(4 + leg);
-        float phase;
-        if (inputPhase <= 0.5f) phase = (float)(0.8 * sin((double)inputPhase * 3.14159265358979323846));
-        else phase = (float)(0.8 + ((double)inputPhase - 0.5) * 0.4);
+        const float phase = swing_warp_phase(inputPhase);
         float pw[3] = {0.f, 0.f, 0.f};
-        if (!((double)phase < 0.0 - 1e-3) && !((double)phase >= 0.0 + 1.0 + 1e-3)) {
-            pw[0] = (1 - phase) * st[0] + phase * tg[0];
-            pw[1] = (1 - phase) * st[1] + phase * tg[1];
-            const float mid = (tg[2] > st[2] ? tg[2] : st[2]) + 0.1f;
-            if (!(phase < 0.f)) {
-                const float d1 = mid - st[2], d2 = tg[2] - st[2];
-                const float d3 = (float)(0.25 - 0.5);
-                const float ca = (d1 - d2 * 0.5f) / d3;
-                const float cb = (float)(((double)d2 * 0.25 - (double)d1) / (double)d3);
-                pw[2] = (float)((double)ca * ((double)phase * (double)phase) + (double)(cb * phase) + (double)st[2]);
-            }
-        }
+        swing_parabola_point(phase, st, tg, pw);
 #pragma unroll
         for (int r = 0; r < 3; ++r) { g_out[(size_t)(3 * leg + r) * N + i] = tg[r]; g_out[(size_t)(12 + 3 * leg + r) * N + i] = pw[r]; }
         const float sh = D.hip_l * ((leg & 1) ? 1.f : -1.f);
-        const float x = pw[0] - D.hip_offset[3 * leg], y = pw[1] - D.hip_offset[3 * leg + 1], z = pw[2] - D.hip_offset[3 * leg + 2];
-        const float lu = D.upper_l, ll = D.lower_l;
-        const float tK = -acosf(((x * x + y * y + z * z) - (sh * sh + lu * lu + ll * ll)) / (2 * ll * lu));
-        const float l = sqrtf(lu * lu + ll * ll + 2 * lu * ll * cosf(tK));
-        const float tH = asinf(-x / l) - tK / 2;
-        const float c1 = sh * y - l * cosf(tH + tK / 2) * z;
-        const float s1 = l * cosf(tH + tK / 2) * y + sh * z;
-        const float tA = atan2f(s1, c1);
-        const float ang[3] = {tA, tH, tK};
+        float ang[3], Ji[3][3];
+        leg_ik(pw, &D.hip_offset[3 * leg], sh, D.upper_l, D.lower_l, ang);
         // J^-1 * (the generator's zero velocity): zero, or NaN where the Jacobian is (an unreachable target), as the reference's product is
-        float J[3][3];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) leg_jacobian_column(j, tA, tH, tK, sh, lu, ll, J[0][j], J[1][j], J[2][j]);
-        const float det = J[0][0] * (J[1][1] * J[2][2] - J[1][2] * J[2][1]) - J[0][1] * (J[1][0] * J[2][2] - J[1][2] * J[2][0]) + J[0][2] * (J[1][0] * J[2][1] - J[1][1] * J[2][0]);
-        const float id = 1.f / det;
-        const float Ji[3][3] = {{(J[1][1] * J[2][2] - J[1][2] * J[2][1]) * id, (J[0][2] * J[2][1] - J[0][1] * J[2][2]) * id, (J[0][1] * J[1][2] - J[0][2] * J[1][1]) * id},
-                                {(J[1][2] * J[2][0] - J[1][0] * J[2][2]) * id, (J[0][0] * J[2][2] - J[0][2] * J[2][0]) * id, (J[0][2] * J[1][0] - J[0][0] * J[1][2]) * id},
-                                {(J[1][0] * J[2][1] - J[1][1] * J[2][0]) * id, (J[0][1] * J[2][0] - J[0][0] * J[2][1]) * id, (J[0][0] * J[1][1] - J[0][1] * J[1][0]) * id}};
+        leg_jacobian_inverse(ang, sh, D.upper_l, D.lower_l, Ji);
 #pragma unroll
         for (int r = 0; r < 3; ++r) {
             float a = ang[r];

@@ -84,4 +84,61 @@ __device__ __forceinline__ void leg_jacobian_column(int j, float t0, float t1, f
     }
 }
 
+// ---- swing-leg helpers shared by the swing kernels (qr_estimator_kernel.hip, qr_swing_modes_kernel.hip); fp32, contraction off -------
+
+// SwingFootTrajectory::GenerateTrajectoryPoint's phase warp (phaseModule = true), qr_foot_trajectory_generator.cpp:328-335
+__device__ __forceinline__ float swing_warp_phase(float inputPhase)
+{
+#pragma clang fp contract(off)
+    if (inputPhase <= 0.5f) return (float)(0.8 * sin((double)inputPhase * 3.14159265358979323846));
+    return (float)(0.8 + ((double)inputPhase - 0.5) * 0.4);
+}
+
+// qrFootParabolaPatternGenerator::GenerateTrajectory with height 0.1 (qr_foot_trajectory_generator.cpp:187-215, qr_geometry.cpp:157-190):
+// XY linear, Z parabola through max(z_start, z_end) + 0.1 at phase 0.5.  pw is left untouched outside [-1e-3, 1 + 1e-3) and z for phase < 0.
+__device__ __forceinline__ void swing_parabola_point(float phase, const float st[3], const float tg[3], float pw[3])
+{
+#pragma clang fp contract(off)
+    if (!((double)phase < 0.0 - 1e-3) && !((double)phase >= 0.0 + 1.0 + 1e-3)) {
+        pw[0] = (1 - phase) * st[0] + phase * tg[0];
+        pw[1] = (1 - phase) * st[1] + phase * tg[1];
+        const float mid = (tg[2] > st[2] ? tg[2] : st[2]) + 0.1f;
+        if (!(phase < 0.f)) {
+            const float d1 = mid - st[2], d2 = tg[2] - st[2];
+            const float d3 = (float)(0.25 - 0.5);
+            const float ca = (d1 - d2 * 0.5f) / d3;
+            const float cb = (float)(((double)d2 * 0.25 - (double)d1) / (double)d3);
+            pw[2] = (float)((double)ca * ((double)phase * (double)phase) + (double)(cb * phase) + (double)st[2]);
+        }
+    }
+}
+
+// Leg inverse kinematics, qrRobot::FootPositionInHipFrameToJointAngle (quadruped/src/robots/qr_robot.cpp:106-124) of the foot position p
+// in the base frame minus the hip offset ho; sh = hipLength * (-1 for right legs, +1 for left legs)
+__device__ __forceinline__ void leg_ik(const float p[3], const float ho[3], float sh, float lu, float ll, float ang[3])
+{
+#pragma clang fp contract(off)
+    const float x = p[0] - ho[0], y = p[1] - ho[1], z = p[2] - ho[2];
+    const float tK = -acosf(((x * x + y * y + z * z) - (sh * sh + lu * lu + ll * ll)) / (2 * ll * lu));
+    const float l = sqrtf(lu * lu + ll * ll + 2 * lu * ll * cosf(tK));
+    const float tH = asinf(-x / l) - tK / 2;
+    const float c1 = sh * y - l * cosf(tH + tK / 2) * z;
+    const float s1 = l * cosf(tH + tK / 2) * y + sh * z;
+    ang[0] = atan2f(s1, c1); ang[1] = tH; ang[2] = tK;
+}
+
+// AnalyticalLegJacobian(...).inverse() (qr_robot.cpp:148-172, 200-219): the adjugate over the determinant
+__device__ __forceinline__ void leg_jacobian_inverse(const float ang[3], float sh, float lu, float ll, float Ji[3][3])
+{
+#pragma clang fp contract(off)
+    float J[3][3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) leg_jacobian_column(j, ang[0], ang[1], ang[2], sh, lu, ll, J[0][j], J[1][j], J[2][j]);
+    const float det = J[0][0] * (J[1][1] * J[2][2] - J[1][2] * J[2][1]) - J[0][1] * (J[1][0] * J[2][2] - J[1][2] * J[2][0]) + J[0][2] * (J[1][0] * J[2][1] - J[1][1] * J[2][0]);
+    const float id = 1.f / det;
+    Ji[0][0] = (J[1][1] * J[2][2] - J[1][2] * J[2][1]) * id; Ji[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) * id; Ji[0][2] = (J[0][1] * J[1][2] - J[0][2] * J[1][1]) * id;
+    Ji[1][0] = (J[1][2] * J[2][0] - J[1][0] * J[2][2]) * id; Ji[1][1] = (J[0][0] * J[2][2] - J[0][2] * J[2][0]) * id; Ji[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) * id;
+    Ji[2][0] = (J[1][0] * J[2][1] - J[1][1] * J[2][0]) * id; Ji[2][1] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) * id; Ji[2][2] = (J[0][0] * J[1][1] - J[0][1] * J[1][0]) * id;
+}
+
 }  // namespace qrgpu

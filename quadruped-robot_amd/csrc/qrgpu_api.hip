@@ -68,6 +68,10 @@ __global__ void qr_walk_gait_kernel(int n, WalkDesc D, float currentTime, int st
                                     float *g_vmc_in);
 __global__ void qr_swing_kernel(int n, EstimatorDesc D, const float *g_in, float *g_cmd, float *g_tgt_world, float *g_qdes);
 __global__ void qr_foothold_kernel(int n, FootholdDesc D, const float *g_in, const float *g_gait_state, const float *g_gait_out, float *g_swing);
+__global__ void qr_swing_update_kernel(int n, SwingModeDesc M, int reset, int stop, const float *g_est_in, const float *g_est_out, const float *g_gait_out,
+                                       float *g_st, float *g_swing_in, float *g_swing_vel_in, float *g_fe_in, int *g_flags);
+__global__ void qr_swing_action_kernel(int n, SwingModeDesc M, EstimatorDesc D, int stop, const float *g_est_in, const float *g_est_out, const float *g_gait_out,
+                                       const float *g_gait_state, float *g_st, float *g_out, int *g_flags);
 __global__ void qr_pack_state_kernel(int n, float c0, float c1, float c2, const float *g_in, const float *g_est, const float *g_rpy, float *g_mpc, float *g_fb);
 __global__ void qr_estimator_kernel(int n, EstimatorDesc D, const float *g_in, const unsigned *g_tick, double *st, float *g_out);
 __global__ void qr_vmc_kernel(VmcLaunch P, const int *type_id, const float *g_in, const float *g_q, float *g_force, float *g_tau, int *g_status);
@@ -1194,6 +1198,62 @@ int qrgpu_swing_targets_batch(qrgpu_ctx *c, int n, const qrgpu_estimator_desc *d
     D.hip_l = desc->hip_l; D.upper_l = desc->upper_l; D.lower_l = desc->lower_l;
     memcpy(D.hip_offset, desc->hip_offset, sizeof(D.hip_offset));
     hipLaunchKernelGGL(qr_swing_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, n, D, d_swing_in, d_wbc_cmd, d_foot_target_world, d_qdes);
+    HIPCHK(c, hipGetLastError());
+    return QRGPU_OK;
+}
+
+void qrgpu_swing_mode_desc_default(qrgpu_swing_mode_desc *d, int mode)
+{   // config/a1_sim: terrain.yaml (terrain_type 3, gaps 0.51 1.31 1.91, gap_width 0.14) after qrGroundSurfaceEstimator::Reset (:73-100)
+    if (!d) return;
+    memset(d, 0, sizeof(*d));
+    d->mode = mode; d->is_sim = 1; d->foothold_delta = 0.10f;
+    d->terrain = mode == QRGPU_MODE_POSITION ? 1 : mode == QRGPU_MODE_ADVANCED_TROT ? 2 : 3;
+    d->gap_width = 0.14f;
+    if (mode == QRGPU_MODE_POSITION) { d->n_gaps = 3; d->gap_distance[0] = 0.51f; d->gap_distance[1] = 1.31f; d->gap_distance[2] = 1.91f; }
+}
+
+static bool swing_mode_desc(const qrgpu_swing_mode_desc *d, SwingModeDesc &M)
+{
+    if (!d || d->mode < 0 || d->mode > 3 || d->n_gaps < 0 || d->n_gaps > QRGPU_SWING_MAX_GAPS) return false;
+    static_assert(QRGPU_SWING_MAX_GAPS == QR_SWING_MAX_GAPS && QRGPU_SWING_MAX_PLAN == QR_SWING_MAX_PLAN, "swing state layout");
+    memset(&M, 0, sizeof(M));
+    M.mode = d->mode; M.terrain = d->terrain; M.is_sim = d->is_sim; M.foothold_delta = d->foothold_delta;
+    M.n_gaps = d->terrain == 1 ? d->n_gaps : 0;                // the stepper copies gaps on PLUM_PILES only (qr_foot_stepper.cpp:31-38)
+    memcpy(M.gap_distance, d->gap_distance, sizeof(M.gap_distance)); M.gap_width = d->gap_width;
+    return true;
+}
+
+int qrgpu_swing_update_batch(qrgpu_ctx *c, int n, const qrgpu_swing_mode_desc *desc, int reset, int robot_stop, const float *d_est_in,
+                             const float *d_est_out, const float *d_gait_out, const float *d_gait_state, float *d_swing_state,
+                             float *d_swing_in, float *d_swing_vel_in, float *d_fe_in, int *d_swing_flags)
+{
+    (void)d_gait_state;
+    SwingModeDesc M;
+    if (!c || n <= 0 || n > c->max_batch || !swing_mode_desc(desc, M) || reset < 0 || reset > 2) return QRGPU_ERR_BAD_ARG;
+    if (!d_est_in || !d_est_out || !d_gait_out || !d_swing_state || !d_swing_flags) return QRGPU_ERR_BAD_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipLaunchKernelGGL(qr_swing_update_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, n, M, reset, robot_stop ? 1 : 0, d_est_in, d_est_out, d_gait_out,
+                       d_swing_state, d_swing_in, d_swing_vel_in, d_fe_in, d_swing_flags);
+    HIPCHK(c, hipGetLastError());
+    return QRGPU_OK;
+}
+
+int qrgpu_swing_action_batch(qrgpu_ctx *c, int n, const qrgpu_swing_mode_desc *desc, const qrgpu_estimator_desc *geom, int robot_stop,
+                             const float *d_est_in, const float *d_est_out, const float *d_gait_out, const float *d_gait_state,
+                             float *d_swing_state, float *d_out, int *d_swing_flags)
+{
+    SwingModeDesc M;
+    if (!c || n <= 0 || n > c->max_batch || !swing_mode_desc(desc, M) || !geom) return QRGPU_ERR_BAD_ARG;
+    if (M.mode != QRGPU_MODE_POSITION && M.mode != QRGPU_MODE_WALK) return QRGPU_ERR_BAD_ARG;      // the other two have kernels of their own
+    if (!d_est_in || !d_est_out || !d_gait_out || !d_swing_state || !d_out || !d_swing_flags) return QRGPU_ERR_BAD_ARG;
+    if (M.mode == QRGPU_MODE_POSITION && !d_gait_state) return QRGPU_ERR_BAD_ARG;                   // allowSwitchLegState
+    HIPCHK(c, hipSetDevice(c->device));
+    EstimatorDesc D;
+    memset(&D, 0, sizeof(D));
+    D.hip_l = geom->hip_l; D.upper_l = geom->upper_l; D.lower_l = geom->lower_l;
+    memcpy(D.hip_offset, geom->hip_offset, sizeof(D.hip_offset));
+    hipLaunchKernelGGL(qr_swing_action_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, n, M, D, robot_stop ? 1 : 0, d_est_in, d_est_out, d_gait_out,
+                       d_gait_state, d_swing_state, d_out, d_swing_flags);
     HIPCHK(c, hipGetLastError());
     return QRGPU_OK;
 }

@@ -85,6 +85,33 @@ class swing_velocity_desc_struct(C.Structure):
     _fields_ = [("hip_position_com", C.c_float * 12), ("stance_duration", C.c_float * 4), ("swing_kp", C.c_float * 3), ("desired_height", C.c_float)]
 
 
+MAX_GAPS = 8
+SWING_MAX_PLAN = 32
+SWING_STATE_FLOATS = 105 + 4 * SWING_MAX_PLAN
+SWING_OUT_ROWS = 52
+MODE_VELOCITY, MODE_POSITION, MODE_WALK, MODE_ADVANCED_TROT = 0, 1, 2, 3
+SW_NO_TRAJECTORY, SW_PHASE_RANGE, SW_PLAN_EXIT, SW_PLAN_EMPTY, SW_PLAN_FULL = 0x1, 0x2, 0x4, 0x8, 0x10
+
+
+class swing_mode_desc_struct(C.Structure):
+    _fields_ = [("mode", C.c_int), ("terrain", C.c_int), ("is_sim", C.c_int), ("foothold_delta", C.c_float), ("n_gaps", C.c_int),
+                ("gap_distance", C.c_float * MAX_GAPS), ("gap_width", C.c_float)]
+
+
+def swing_mode_desc(mode, terrain=None, is_sim=None, foothold_delta=None, gaps=None, gap_width=None):
+    """qrgpu_swing_mode_desc: the library's defaults for `mode` (config/a1_sim), with any field overridden."""
+    d = swing_mode_desc_struct()
+    load_library().qrgpu_swing_mode_desc_default(C.byref(d), int(mode))
+    if terrain is not None: d.terrain = int(terrain)
+    if is_sim is not None: d.is_sim = int(bool(is_sim))
+    if foothold_delta is not None: d.foothold_delta = float(foothold_delta)
+    if gap_width is not None: d.gap_width = float(gap_width)
+    if gaps is not None:
+        d.n_gaps = len(gaps)
+        for k, g in enumerate(list(gaps)[:MAX_GAPS]): d.gap_distance[k] = float(g)
+    return d
+
+
 EPILOGUE_HIP_COMP, EPILOGUE_CLIP = 1, 2
 COMM_ID_BYTES = 128
 
@@ -114,7 +141,7 @@ EXPORTS = ["qrgpu_model_desc_default", "qrgpu_create", "qrgpu_destroy", "qrgpu_s
            "qrgpu_allgather_tau", "qrgpu_allgather_tau_of_tick", "qrgpu_allgather_fence", "qrgpu_allgather_wait", "qrgpu_comm_sync", "qrgpu_set_warm_start", "qrgpu_set_planned_list",
            "qrgpu_enable_flop_count", "qrgpu_mpc_flop_counts", "qrgpu_mpc_set_hessian_mode", "qrgpu_wbc_inspect_batch", "qrgpu_host_alloc", "qrgpu_host_free",
            "qrgpu_memcpy_async", "qrgpu_memset_async", "qrgpu_mark", "qrgpu_mark_elapsed_ms", "qrgpu_set_tick_pipeline", "qrgpu_set_tick_overlap",
-           "qrgpu_tick_fence", "qrgpu_tick_overlap_stats"]
+           "qrgpu_tick_fence", "qrgpu_tick_overlap_stats", "qrgpu_swing_mode_desc_default", "qrgpu_swing_update_batch", "qrgpu_swing_action_batch"]
 
 
 def load_library():
@@ -182,6 +209,9 @@ def load_library():
     lib.qrgpu_foothold_desc_default.argtypes = [C.POINTER(foothold_desc_struct)]; lib.qrgpu_foothold_desc_default.restype = None
     lib.qrgpu_footholds_batch.argtypes = [vp, ip, C.POINTER(foothold_desc_struct), vp, vp, vp, vp]
     lib.qrgpu_pack_state_batch.argtypes = [vp, ip, fp, vp, vp, vp, vp, vp]
+    lib.qrgpu_swing_mode_desc_default.argtypes = [C.POINTER(swing_mode_desc_struct), ip]; lib.qrgpu_swing_mode_desc_default.restype = None
+    lib.qrgpu_swing_update_batch.argtypes = [vp, ip, C.POINTER(swing_mode_desc_struct), ip, ip] + [vp] * 9
+    lib.qrgpu_swing_action_batch.argtypes = [vp, ip, C.POINTER(swing_mode_desc_struct), C.POINTER(estimator_desc_struct), ip] + [vp] * 7
     lib.qrgpu_vmc_force1.argtypes = [vp, ip, fp, fp, fp, fp, C.POINTER(ip)]
     lib.qrgpu_mpc_frontend_batch.argtypes = [vp, ip, ip, C.c_float, C.c_float] + [vp] * 6
     lib.qrgpu_fb_debug_batch.argtypes = [vp, ip, vp, vp, vp]
@@ -517,6 +547,23 @@ class Context:
         d.hip_l, d.upper_l, d.lower_l = (float(v) for v in cfg20[:3])
         for i in range(12): d.hip_offset[i] = float(cfg20[7 + i])
         self._chk(self._lib.qrgpu_swing_targets_batch(self._h, n, C.byref(d), _dp(swing_in), _dp(wbc_cmd), _dp(foot_target_world), _dp(qdes)))
+
+    def swing_update_batch(self, n, desc, est_in, est_out, gait_out, swing_state, swing_flags, gait_state=None, swing_in=None, swing_vel_in=None,
+                           fe_in=None, reset=0, stop=False):
+        """qrRaibertSwingLegController::Reset (reset: 2 = constructed, 1 = Reset(), 0 = carry on) + Update of n robots: the lift-off memory
+        of every mode, the footholds and walk trajectories (qr_swing_leg_controller.cpp:60-196).  desc = swing_mode_desc(mode, ...)."""
+        self._chk(self._lib.qrgpu_swing_update_batch(self._h, n, C.byref(desc), int(reset), int(bool(stop)), _dp(est_in), _dp(est_out), _dp(gait_out),
+                                                     _dp(gait_state), _dp(swing_state), _dp(swing_in), _dp(swing_vel_in), _dp(fe_in), _dp(swing_flags)))
+
+    def swing_action_batch(self, n, desc, cfg20, est_in, est_out, gait_out, swing_state, out, swing_flags, gait_state=None, stop=False):
+        """GetAction of the position and walk modes (qr_swing_leg_controller.cpp:204-229, 311-359, 407-459).  cfg20 = workload.estimator_cfg()
+        (geometry part); out [52][n]."""
+        d = estimator_desc_struct()
+        cfg20 = np.asarray(cfg20, np.float32)
+        d.hip_l, d.upper_l, d.lower_l = (float(v) for v in cfg20[:3])
+        for i in range(12): d.hip_offset[i] = float(cfg20[7 + i])
+        self._chk(self._lib.qrgpu_swing_action_batch(self._h, n, C.byref(desc), C.byref(d), int(bool(stop)), _dp(est_in), _dp(est_out), _dp(gait_out),
+                                                     _dp(gait_state), _dp(swing_state), _dp(out), _dp(swing_flags)))
 
     def pack_state_batch(self, n, com_offset, est_in, est_out, rpy, mpc_state=None, fb_state=None):
         """mpc_state[28] / fb_state[37] from the estimator's inputs and outputs (SolveDenseMPC :385-399, UpdateModel :136-156)."""
