@@ -70,8 +70,8 @@
  *   fe_state  [8][n]  : in/out controller memory: xVelDes, yVelDes, yawTurnRate, yawDesTrue, posDesiredinWorld[3], iterationCounter
  *
  * ENVIRONMENT SWITCHES.  These are the supported ones (read once per process).  qrgpu_create warns once about any other QRGPU_* variable it
- * finds: the alternative launch shapes and thresholds rounds 1-3 measured with are laboratory switches, ignored unless QRGPU_LAB=1 is set
- * (LAB_NOTES.md lists them with what each measured).
+ * finds: the launch forms kept for a test or a profiling run are laboratory switches, ignored unless QRGPU_LAB=1 is set (LAB_NOTES.md A.1
+ * lists them, and the retired ones with what each measured).
  *   name                    default  effect
  *   QRGPU_TICK_PIPELINE     1        0: qrgpu_tick_batch queues the WBC launch behind the MPC launches (the serial tick) whatever qrgpu_set_tick_pipeline says
  *   QRGPU_PIPE_GATE_MS      50       bound of the gate in front of a pipelined tick's WBC launch; one that gives up turns the tick into the serial one

@@ -2023,19 +2023,13 @@ void qr_mpc_persist_kernel(MpcLaunch P, MpcIO io)
 }
 template __global__ void qr_mpc_persist_kernel<2, false, 512>(MpcLaunch, MpcIO);
 template __global__ void qr_mpc_persist_kernel<5, true, 512>(MpcLaunch, MpcIO);
-template __global__ void qr_mpc_persist_kernel<9, true, 256>(MpcLaunch, MpcIO);     // h <= 16 on four waves (no parked waves: every wave is in the active set)
-template __global__ void qr_mpc_persist_kernel<9, true, 256, 2>(MpcLaunch, MpcIO);  // the same within 256 registers: two workgroups per CU (QRGPU_H16_TWO)
 #endif
 
 template __global__ void qr_mpc_kernel<2, false, false, 512>(MpcLaunch, MpcIO);     // h <= 11, main pass: eight waves build and sweep (128 VGPRs), four solve
-template __global__ void qr_mpc_kernel<4, false, false, 256>(MpcLaunch, MpcIO);     // h <= 11, main pass on four waves (QRGPU_MAIN_THREADS=256, A/B)
 template __global__ void qr_mpc_kernel<4, true, true, 256>(MpcLaunch, MpcIO);       // h <= 11, list launches (whole CU's LDS, 96 rows)
 template __global__ void qr_mpc_kernel<9, true, true, 256>(MpcLaunch, MpcIO);       // h <= 16, list launches (whole CU's LDS, 96 rows)
 template __global__ void qr_mpc_kernel<4, true, true, 256, 2, true>(MpcLaunch, MpcIO);   // h <= 11, list launches of an OVERLAPPED tick: half a CU's LDS, S^-1 (96 rows) in the global scratch
-template __global__ void qr_mpc_kernel<9, true, false, 256>(MpcLaunch, MpcIO);      // h <= 16, four waves (QRGPU_H16_THREADS=256, A/B)
-template __global__ void qr_mpc_kernel<9, true, false, 256, 2>(MpcLaunch, MpcIO);   // h <= 16, four waves within 256 registers: two workgroups per CU (QRGPU_H16_TWO)
 template __global__ void qr_mpc_kernel<5, true, false, 512>(MpcLaunch, MpcIO);      // h <= 16: eight waves build and sweep (256 VGPRs, one workgroup per CU)
-template __global__ void qr_mpc_kernel<2, false, false, 512, 4, true>(MpcLaunch, MpcIO);
 template __global__ void qr_mpc_kernel<2, true, false, 512, 4, true>(MpcLaunch, MpcIO);   // h <= 16 two to a CU: a trotting robot (<= 42 stance leg-steps) on eight waves within 128 registers
 template __global__ void qr_mpc_kernel<2, true, false, 512>(MpcLaunch, MpcIO);      // h <= 11, planned list: one robot per workgroup, whole CU's LDS, 96 rows, eight waves build and sweep
 

@@ -16,10 +16,6 @@
 
 #include "qrgpu_ctx.h"
 
-namespace qrgpu {
-__global__ void qr_gate_kernel(int *counter, int expected_total, long long max_ticks, int *timed_out, int timed_out_value, int *bump);   // qr_mpc_kernel.hip
-}
-
 namespace {
 
 // How the streams of a context learn of a gather.  Two forms:
@@ -32,7 +28,7 @@ namespace {
 //          tests/test_gpu_comm.py, bench.py QRGPU_BENCH_FORCE_COMM=1) and opt-in for more: QRGPU_COMM_EVENTS=0.  (QRGPU_COMM_EVENTS=1: events always.)
 bool comm_polls(const qrgpu_ctx *c)
 {
-    static const int ev = [] { const char *e = getenv("QRGPU_COMM_EVENTS"); return e ? atoi(e) : -1; }();
+    const int ev = qr_env().comm_events;
     if (ev >= 0) return ev == 0;
     return !(c && c->comm_nranks > 1);
 }

@@ -1,7 +1,9 @@
-// Internal: the context behind the opaque qrgpu_ctx of include/qrgpu.h (shared by qrgpu_api.hip and qrgpu_comm.hip).
+// Internal: the context behind the opaque qrgpu_ctx of include/qrgpu.h, the environment switches and the declarations the host files share
+// (qrgpu_api.hip, qrgpu_mpc.hip, qrgpu_tick.hip, qrgpu_comm.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdlib>
+#include <cstring>
 #include <string>
 #include <utility>
 #include <vector>
@@ -10,6 +12,21 @@
 #include "qr_device_types.h"
 
 using namespace qrgpu;
+
+// The MPC kernel variants the host launches (the table with their functions, workgroup sizes and persistent forms: qrgpu_mpc.hip).
+enum MpcVar {
+    MPC_MAIN11,            // h <= 11 main pass: <2, ., ., 512>, eight waves build and sweep (two blocks per thread, 128 VGPRs), two workgroups per CU
+    MPC_LIST11,            // h <= 11 list launches: <4, BIG, LIST, 256> striding over a list, whole CU's LDS, 96 rows
+    MPC_ONE11,             // h <= 11 one robot per workgroup on a whole CU: <2, BIG, ., 512> (planned list; main pass of batches below 64 robots)
+    MPC_HALF_LIST11,       // h <= 11 list launches of an overlapped tick on HALF a CU: <4, BIG, LIST, 256, 2, H16>, S^-1 in the global scratch
+    MPC_MAIN16,            // h <= 16 main pass: <5, BIG, ., 512>, one workgroup per CU (also the planned list's one robot per workgroup)
+    MPC_LIST16,            // h <= 16 list launches: <9, BIG, LIST, 256>
+    MPC_TWO16,             // h <= 16 two to a CU: <2, BIG, ., 512, 4, H16> (also one listed robot per half CU in an overlapped tick at h <= 11)
+    MPC_PERSIST11,         // persistent form of MPC_MAIN11 (QRGPU_PERSIST=2)
+    MPC_PERSIST16,         // persistent form of MPC_MAIN16
+    MPC_VAR_COUNT,
+    MPC_VAR_NONE = -1
+};
 
 // One "lane" of MPC launch scheduling: everything a sequence of MPC launches on ONE stream carries from launch to launch -- the longest-first
 // order, the rescue and planned lists with their ping-pong parities and pinned length hints, the cumulative counters its gates poll, the
@@ -98,12 +115,11 @@ struct qrgpu_ctx {
     // pipelined tick (qrgpu_set_tick_pipeline, default on): the WBC launch of a tick runs on wbc_stream beside that tick's MPC launches
     bool pipeline = true;
     hipStream_t wbc_stream = nullptr;
-    hipEvent_t ev_wbc_fork = nullptr, ev_wbc_join = nullptr;
     int *d_main_started = nullptr;            // main-pass workgroups started, ever (the WBC launch's gate); never cleared
     unsigned main_started_total = 0;
     unsigned tick_epoch = 0;
-    int main_slots[16][2] = {};               // resident workgroups per CU of each main-pass variant at the LDS size it was last configured for (0: not asked yet)
-    int main_slots_lds[16][2] = {};
+    int main_slots[MPC_VAR_COUNT] = {};       // resident workgroups per CU of each persistent variant at the LDS size it was last configured for (0: not asked yet)
+    int main_slots_lds[MPC_VAR_COUNT] = {};
     int *d_tick_done = nullptr;               // pipelined ticks complete (bumped by their joins), ever: what qrgpu_allgather_tau_of_tick's gate polls
     unsigned tick_done_total = 0;
     bool last_tick_piped = false;             // the context's most recent qrgpu_tick_batch was a pipelined one with a polling join
@@ -135,8 +151,6 @@ struct qrgpu_ctx {
     // overlapped ticks at h > 11: a tenth of a mixed shard wants a whole CU per robot, which a machine that is never empty does not offer -- so the
     // machine is split in space: ov16_side_cus CUs (a multiple of 32 on 256: every XCD's share a multiple of four, or the LDS a queue may use per CU
     // drops to ~100 KB) are reserved for the whole-CU launches (planned list, trailing launch), the main passes run on the others
-    hipStream_t wbc_stream_16 = nullptr;      // ... and the WBC launches too (a WBC workgroup waiting on a reserved CU for a planned robot's forces would keep
-                                              //     the whole-CU workgroup that computes them from ever starting there)
     int ov16_side_cus = 0;
     uint32_t mask16_main[16] = {}, mask16_side[16] = {};
     // a chained tick waits for what the caller had queued on the context's stream when it made the PREVIOUS tick call (its predecessor's predecessor's
@@ -149,10 +163,7 @@ struct qrgpu_ctx {
     unsigned *d_wbc_done = nullptr;           // [max_batch] ... whose WBC pass has left the orientation task's memory (prev_ori) in memory
     int *d_tlr = nullptr;                     // diagnostic: [4][max_batch] per-robot WBC moments of the last pipelined tick
     long long *d_timeline = nullptr;          // diagnostic (qrgpu_debug_timeline): [64][8], or null
-    int *d_ftime = nullptr;                   // [max_batch] when each robot's solve ended in the last pipelined tick (100 MHz clock, low word)
-    int *d_wbc_order = nullptr;               // [2][max_batch] the WBC launch's slot -> robot map from those times, ping-pong: a tick's WBC launch reads one
-    int wbc_order_parity = 0;                 //   half while the launch behind its main pass writes the other
-    int wbc_order_n = 0;                      // batch size the half to be read next was written for (0: none)
+    int *d_ftime = nullptr;                   // diagnostic, with d_tlr: [max_batch] when each robot's solve ended in the last pipelined tick (100 MHz clock, low word)
     bool lpt = true;
     bool rescue = true;
     int epilogue = 0;             // QRGPU_EPILOGUE_* bits
@@ -186,10 +197,10 @@ struct qrgpu_ctx {
     std::vector<hipEvent_t> marks;   // qrgpu_mark: caller-indexed events on the context stream
 };
 
-// Environment switches.  The SUPPORTED ones are listed in include/qrgpu.h (name, default, effect) and read with getenv.  Everything else that
-// rounds 1-3 measured with -- alternative launch shapes, event / polling forms of each hand-over, thresholds -- is a LABORATORY switch: read
-// through lab_env, which answers only when QRGPU_LAB=1 is set, so that a product run cannot be steered by a leftover of an experiment.
-// qrgpu_create warns once per process about any other QRGPU_* variable it finds in the environment.
+// Environment switches.  The SUPPORTED ones are listed in include/qrgpu.h (name, default, effect) and read with getenv.  The LABORATORY ones --
+// launch forms kept for a test or a profiling run, LAB_NOTES.md A.1 -- are read through lab_env, which answers only when QRGPU_LAB=1 is set, so
+// that a product run cannot be steered by a leftover of an experiment.  qrgpu_create warns once per process about any other QRGPU_* variable
+// it finds in the environment.
 inline const char *lab_env(const char *name)
 {
     static const bool lab = [] { const char *e = getenv("QRGPU_LAB"); return e && atoi(e) != 0; }();
@@ -198,7 +209,33 @@ inline const char *lab_env(const char *name)
 #define QRGPU_SUPPORTED_ENV "QRGPU_TICK_PIPELINE", "QRGPU_PIPE_GATE_MS", "QRGPU_PLAN_GO_MS", "QRGPU_PIPE_WAIT_US", "QRGPU_OV_WAIT_US", "QRGPU_OV_FAULT", "QRGPU_OV_PLAN_HOLD", "QRGPU_OV16", \
                             "QRGPU_COMM_EVENTS", "QRGPU_SINGLE_COPIES", "QRGPU_PERSIST", "QRGPU_H16_TWO", "QRGPU_H16_TWO_HOLD", "QRGPU_H16_BIG_US", "QRGPU_H16_BIG_STAY_US", \
                             "QRGPU_LIB", "QRGPU_EXTRA_FLAGS", "QRGPU_LAB"
-#define QRGPU_LAB_ENV "QRGPU_WBC_ORDER", "QRGPU_WARM_UTHR", "QRGPU_TINY_WHOLE_CU", "QRGPU_SIDE_PRIORITY", "QRGPU_PLAN_SYNC", "QRGPU_PLANNED_WAVES", "QRGPU_PLANNED_MODE", "QRGPU_PLANNED_JOIN", "QRGPU_PLANNED_GATE", "QRGPU_PLANNED_FORK", "QRGPU_PLANNED_EXTRA", "QRGPU_PIPE_JOIN", "QRGPU_PIPE_FORK", "QRGPU_PIPE_EARLY", "QRGPU_OWN_STREAM", "QRGPU_OV_WBC_PRIORITY", "QRGPU_NO_WCACHE", "QRGPU_NO_BLOCK_DROP", "QRGPU_MAIN_WGS", "QRGPU_MAIN_THREADS", "QRGPU_H16_TWO_WAVES", "QRGPU_H16_THREADS", "QRGPU_COST_EMA", "QRGPU_BIG_MARGIN", "QRGPU_OV16_SIDE_CUS", "QRGPU_OV16_DEBUG", "QRGPU_OV16_LINGER", "QRGPU_OV16_WBC_MASK", "QRGPU_OV16_COST", "QRGPU_WBC_CHUNKS"
+#define QRGPU_LAB_ENV "QRGPU_WBC_CHUNKS", "QRGPU_PLANNED_FORK"
+
+// Every switch the library reads, read ONCE per process, at the first call that asks (qr_env): the only getenv / lab_env calls of the host code
+// besides lab_env's own.  Times are in ticks of the 100 MHz clock the kernels' bounded waits count.
+struct QrEnv {
+    static int num(const char *e, int dflt) { return e ? atoi(e) : dflt; }
+    static long long ms(const char *e) { return 100000LL * (e ? atoll(e) : 50LL); }
+    static long long us(const char *e, long long dflt_ticks) { return e ? 100LL * atoll(e) : dflt_ticks; }
+    int tick_pipeline = num(getenv("QRGPU_TICK_PIPELINE"), 1);                   // 0 keeps every tick serial
+    long long pipe_gate_ticks = ms(getenv("QRGPU_PIPE_GATE_MS"));                // bound of the gate in front of a pipelined tick's WBC launch
+    long long plan_go_ticks = ms(getenv("QRGPU_PLAN_GO_MS"));                    // bound of the planned launch's wait for the "go" of the context's stream
+    long long pipe_wait_ticks = us(getenv("QRGPU_PIPE_WAIT_US"), 400000LL);      // bound of a WBC workgroup's wait for its robot's forces (4 ms)
+    long long ov_wait_ticks = us(getenv("QRGPU_OV_WAIT_US"), 2000000LL);         // bound of an overlapped tick's per-robot waits for its predecessor (20 ms)
+    int ov_fault = num(getenv("QRGPU_OV_FAULT"), 0);                             // fault injection of the give-up tests: 1 chained ticks wait for an epoch nobody writes, 2 nobody lingers
+    int ov_plan_hold = num(getenv("QRGPU_OV_PLAN_HOLD"), 31);                    // plain ticks after a lane of an overlapped context found a plan (h <= 11)
+    bool ov16 = num(getenv("QRGPU_OV16"), 1) != 0;                               // overlapped ticks at h > 11
+    int comm_events = num(getenv("QRGPU_COMM_EVENTS"), -1);                      // (-1: by the communicator's size, qrgpu_comm.hip)
+    bool single_copies = num(getenv("QRGPU_SINGLE_COPIES"), 0) != 0;             // device staging and copies for the single-robot calls
+    int persist = num(getenv("QRGPU_PERSIST"), 1);                               // 0 never, 1 the h > 11 main pass, 2 the h <= 11 one too
+    int h16_two = num(getenv("QRGPU_H16_TWO"), 1);                               // 0 never two to a CU at h > 11, 2 from 64 robots on
+    int h16_two_hold = num(getenv("QRGPU_H16_TWO_HOLD"), 31);                    // calls on one workgroup per CU after the list outgrew 45 % of the batch
+    int h16_big_us = num(getenv("QRGPU_H16_BIG_US"), 450);                       // the cost rule of the h > 11 planned list: onto a whole CU from this cost on ...
+    int h16_big_stay_us = num(getenv("QRGPU_H16_BIG_STAY_US"), 300);             // ... and off it below this one
+    int wbc_chunks = num(lab_env("QRGPU_WBC_CHUNKS"), 0);                        // laboratory: the WBC launch of a large batch in launches of 1024 workgroups (LAB_NOTES A.7)
+    int planned_fork = num(lab_env("QRGPU_PLANNED_FORK"), 0);                    // laboratory: 1 = the planned launch forks and joins through stream events (counter-collection runs)
+};
+inline const QrEnv &qr_env() { static const QrEnv env{}; return env; }
 
 #define HIPCHK(ctx, call)                                                                    \
     do {                                                                                     \
@@ -209,3 +246,98 @@ inline const char *lab_env(const char *name)
         }                                                                                    \
     } while (0)
 
+
+// ---------------------------------------------------------------------------------------------
+// Shared by the host files
+// ---------------------------------------------------------------------------------------------
+namespace qrgpu {
+struct MpcIO {
+    const int *type_id;
+    const float *g_state, *g_traj, *g_gait, *g_q;
+    float *g_force, *g_tau;
+    int *g_status;
+    float *dbgH, *dbgG, *g_force_wbc;
+    int force_stride;
+    long long *dbgT;
+};
+// (qr_mpc_kernel.hip)
+__global__ void qr_gate_kernel(int *counter, int expected_total, long long max_ticks, int *timed_out, int timed_out_value, int *bump);
+}
+
+inline int ready_mask(const bool *r) { int m = 0; for (int t = 0; t < QR_MAX_TYPES; ++t) if (r[t]) m |= 1 << t; return m; }
+
+// Brackets a launch with a pair of events while timing is on (qrgpu_enable_timing): kernel 0 = the MPC main pass, 1 = the WBC launch.
+struct TimerScope {
+    qrgpu_ctx *c; int k; bool on; hipStream_t s;
+    TimerScope(qrgpu_ctx *ctx, int kernel, hipStream_t stream = nullptr, bool enabled = true) : c(ctx), k(kernel), on(ctx->timing && enabled), s(stream ? stream : ctx->stream)
+    {
+        if (on && ctx->timing_every > 1 && (ctx->ev_calls[kernel]++ % (unsigned)ctx->timing_every) != 0) on = false;
+        if (!on) return;
+        if (c->ev_used[k] == c->ev[k].size()) {
+            hipEvent_t a, b;
+            if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) { on = false; return; }
+            c->ev[k].push_back({a, b});
+        }
+        hipEventRecord(c->ev[k][c->ev_used[k]].first, s);
+    }
+    ~TimerScope()
+    {
+        if (!on) return;
+        hipEventRecord(c->ev[k][c->ev_used[k]].second, s);
+        c->ev_used[k]++;
+    }
+};
+
+// What an overlapped tick adds to its MPC launches (qrgpu_tick_batch): the epoch its solves leave in d_solved, whether they wait -- per robot -- for
+// the previous tick's (chained), and the cost buffers they read and write.
+struct OvLaunch { unsigned epoch; bool chained; unsigned prev_epoch; bool plan_tick; int *prev_started; unsigned prev_started_total; };
+
+// The optional part of an MPC launch: everything but the context, the batch size and the arrays (MpcIO; dbgH / dbgG set: an inspection launch).
+struct MpcOpts {
+    int epilogue = 0;                 // QRGPU_EPILOGUE_* bits applied by the MPC kernel itself (the MPC-only entry point)
+    bool piped = false;               // part of a pipelined tick: the solves raise per-robot flags for the WBC launch running beside them
+    int lane_id = 0;
+    const OvLaunch *ov = nullptr;     // ... of an overlapped one
+};
+// ... and of a WBC launch: everything but the context, the batch size and the arrays every launch has.
+struct WbcOpts {
+    float *dbg = nullptr;             // inspection output of qrgpu_fb_debug_batch (the launch then needs no command, memory or torque array)
+    int merge = 0, status_or = 0;     // the tick's stance / swing merge into d_tau, status words OR-ed into what the MPC launch left
+    const float *fr = nullptr;        // Fr_des rows: the force array the MPC launch has just written
+    int epilogue = 0;
+    float *qp = nullptr;              // inspection output of qrgpu_wbc_inspect_batch
+    hipStream_t stream = nullptr;     // (null: the context's)
+    WbcPipe pipe{};                   // pipelined tick; all zero: every other launch
+    int grid_wgs = 0;                 // > 0: one of the launches a large batch's WBC launch is cut into (WbcPipe::slot_base)
+    bool timed = true;
+};
+inline MpcIO mpc_io(const int *type_id, const float *state, const float *traj, const float *gait, const float *q, float *force, float *tau, int *status)
+{
+    MpcIO io{};
+    io.type_id = type_id; io.g_state = state; io.g_traj = traj; io.g_gait = gait; io.g_q = q; io.g_force = force; io.g_tau = tau; io.g_status = status;
+    return io;
+}
+int launch_mpc(qrgpu_ctx *c, int n, const MpcIO &arrays, const MpcOpts &opt = MpcOpts{});                                  // qrgpu_mpc.hip
+int launch_wbc(qrgpu_ctx *c, int n, const int *d_type, const float *d_state, const float *d_cmd, float *d_prev, float *d_tau, float *d_qdes, int *d_status,
+               const WbcOpts &opt = WbcOpts{});                                                                            // qrgpu_api.hip
+hipError_t create_side_stream(hipStream_t *s);                                                                            // qrgpu_api.hip
+int lane_create(qrgpu_ctx *c, Lane &L, bool own_stream, bool masked = false);                                             // qrgpu_api.hip
+
+// The scheduling rules that both the MPC launch and the tick decide by: one definition each.
+// The lane has a plan for a batch of n: the list launches are on and its last trailing launch listed somebody (the length comes back through pinned memory).
+inline bool lane_has_plan(const qrgpu_ctx *c, const Lane &L, int n)
+{
+    return c->planned && c->rescue && c->lpt && L.plan_n == n && L.h_pre_count[L.rescue_parity] > 0;
+}
+// The list the host last saw for a batch of n is more than 45 % of it: a shard in which most robots stand.
+inline bool list_exceeds_45_percent(const Lane &L, int n)
+{
+    return L.plan_n == n && 20 * (long long)L.h_pre_count[L.rescue_parity] > 9 * (long long)n;
+}
+// h > 11 may run two workgroups to a CU for a batch of n: 3.5 robots per CU and more (QRGPU_H16_TWO=0: never, =2: from 64 robots on), and it needs
+// the list launches -- a robot of the big class has nowhere else to go -- and the cost words that carry the plan.
+inline bool h16_two_allowed(const qrgpu_ctx *c, int n)
+{
+    const int two = qr_env().h16_two;
+    return two != 0 && n >= (two >= 2 ? 64 : 7 * c->num_cu / 2) && c->rescue && c->planned && c->lpt;
+}

@@ -121,8 +121,8 @@ def test_error_returns(gpu_ctx, pkg):
 
 def test_supported_environment_switches_are_listed_in_the_header():
     """include/qrgpu.h carries the table of supported environment switches; csrc/qrgpu_ctx.h the list the library checks the environment against
-    (anything else named QRGPU_* is reported once by qrgpu_create).  Every getenv of the host code names a supported switch -- laboratory
-    switches go through lab_env and answer only under QRGPU_LAB=1 -- and every supported switch is in the header's table."""
+    (anything else named QRGPU_* is reported once by qrgpu_create).  Every getenv of the host code -- every qrgpu_*.hip and qrgpu_*.h -- names a
+    supported switch, laboratory switches go through lab_env and answer only under QRGPU_LAB=1, and every supported switch is in the header's table."""
     import os, re
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     ctxh = open(os.path.join(root, "quadruped-robot_amd", "csrc", "qrgpu_ctx.h")).read()
@@ -133,7 +133,22 @@ def test_supported_environment_switches_are_listed_in_the_header():
     assert supported and lab and not (supported & lab)
     for name in supported:
         assert re.search(r"^ \*   %s\b" % name, header, re.M), name
-    for f in ("qrgpu_api.hip", "qrgpu_comm.hip"):
-        src = open(os.path.join(root, "quadruped-robot_amd", "csrc", f)).read()
-        assert set(re.findall(r'[^_]getenv\("(QRGPU_\w+)"\)', src)) <= supported, f
-        assert set(re.findall(r'lab_env\("(QRGPU_\w+)"\)', src)) <= lab | {"QRGPU_LAB"}, f
+    import glob
+    csrc = os.path.join(root, "quadruped-robot_amd", "csrc")
+    host = sorted(glob.glob(os.path.join(csrc, "qrgpu_*.hip")) + glob.glob(os.path.join(csrc, "qrgpu_*.h")))
+    assert len(host) >= 5, host                  # (api, mpc, tick, comm and the context header)
+    read, read_lab = set(), set()
+    for f in host:
+        src = open(f).read()
+        got = set(re.findall(r'[^_]getenv\("(QRGPU_\w+)"\)', src))
+        got_lab = set(re.findall(r'lab_env\("(QRGPU_\w+)"\)', src))
+        assert got <= supported, f
+        assert got_lab <= lab | {"QRGPU_LAB"}, f
+        # no call site reads the environment with a name the scan cannot see: every getenv / lab_env of the host code takes a literal
+        # (lab_env's own forwarding getenv(name) in the context header is the one exception)
+        stray = re.findall(r'\b(?:getenv|lab_env)\((?!"QRGPU_\w+"\))[^)]*\)', src)
+        assert stray in ([], ["lab_env(const char *name)", "getenv(name)"]), (f, stray)
+        read |= got; read_lab |= got_lab
+    # ... and the scan is not vacuous: the library does read its switches, laboratory ones included
+    assert read >= {"QRGPU_LAB", "QRGPU_TICK_PIPELINE", "QRGPU_OV_PLAN_HOLD", "QRGPU_H16_TWO_HOLD", "QRGPU_COMM_EVENTS"}, read
+    assert read_lab - {"QRGPU_LAB"} == lab, (read_lab, lab)

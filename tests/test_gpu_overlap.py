@@ -64,11 +64,10 @@ def _run_sequence(pkg, seq, h, n, mode, sync_every_tick, same_outputs=False, pla
         ctx.close()
 
 
-def _compare(pkg, seq, a, b_, h, what):
-    """Robots the main pass solves on both sides are bit-identical; robots that see a list launch on either side (all-stance / three-leg gaits, the
-    class whose inverse Hessian leaves no room for S^-1 in half a CU, and whoever outgrows 58 rows) agree to the solver's tolerance."""
-    n = a[0]["tau"].shape[0]
-    exact_all = np.ones(n, bool)
+def _compare_ticks(a, b_, what):
+    """Tick by tick: nobody timed out, the same robots flagged on both sides (within two), clean robots within the solver's tolerance.
+    -> which robots are bit-identical in every tick"""
+    exact_all = np.ones(a[0]["tau"].shape[0], bool)
     for k, (x, y) in enumerate(zip(a, b_)):
         assert np.all(G.flags(y["status"]) & 0x02000000 == 0), (what, k, "a per-robot wait gave up")
         assert np.array_equal(G.flags(x["status"]) != 0, G.flags(y["status"]) != 0) or np.sum((G.flags(x["status"]) != 0) != (G.flags(y["status"]) != 0)) <= 2, (what, k)
@@ -78,6 +77,14 @@ def _compare(pkg, seq, a, b_, h, what):
         ef = np.abs(x["force"] - y["force"]).max(1) / np.maximum(1.0, np.abs(x["force"]).max(1))
         et = (np.abs(x["tau"] - y["tau"]) / np.maximum(1.0, np.abs(x["tau"]))).max(1)
         assert ef[ok].max() <= 1e-6 and et[ok].max() <= 1e-5, (what, k, ef[ok].max(), et[ok].max())
+    return exact_all
+
+
+def _compare(pkg, seq, a, b_, h, what):
+    """Robots the main pass solves on both sides are bit-identical; robots that see a list launch on either side (all-stance / three-leg gaits, the
+    class whose inverse Hessian leaves no room for S^-1 in half a CU, and whoever outgrows 58 rows) agree to the solver's tolerance."""
+    n = a[0]["tau"].shape[0]
+    exact_all = _compare_ticks(a, b_, what)
     # a trotting robot (at most 28 of the 40 leg-steps of the contact table in stance: neither all-stance nor three-leg) never needs a list launch
     # inside the 8d ranges: bit for bit
     trot = np.all(np.stack([np.asarray(b["gait"]).reshape(n, -1).sum(1) <= 28 for b in seq]), 0)
@@ -113,7 +120,7 @@ def test_overlapped_ticks_with_robots_on_the_list_launches(pkg, oracle):
     """A population with plenty of robots beyond the main pass's rows (30 % all stance, 1.5 x the ranges).  The first ticks are chained, their
     rescued robots re-solved by the half-CU list kernel (S^-1 in the global scratch) with the robots' WBC workgroups waiting on through the
     "on the list pass" flag for it (an overlapped tick has no second WBC pass); then a lane finds a plan and the context goes back to the plain
-    pipelined tick (qrgpu_api.hip: QRGPU_OV_PLAN_HOLD).  Every robot of every tick within the solver's tolerance of the serial tick, no robot
+    pipelined tick (qrgpu_tick.hip: QRGPU_OV_PLAN_HOLD).  Every robot of every tick within the solver's tolerance of the serial tick, no robot
     unsolved (poisoned outputs), nobody timed out, the last tick against the oracle."""
     h, n = 10, 512
     seq = pkg.make_batch_sequence(n, h, "a1", seed=0x91BE, steps=6, frac_all_stance=0.3, excite=1.5)
@@ -384,3 +391,70 @@ def test_h16_hand_overs_nobody_takes_are_never_silent():
     r = subprocess.run([sys.executable, "-c", _OV16_GIVE_UP % dict(root=ROOT)], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert "LOST" in r.stdout
+
+
+_HOLD11 = r"""
+import os, sys
+sys.path.insert(0, os.path.join(%(root)r, "tests"))
+import numpy as np
+import conftest, gpu_helpers as G
+import test_gpu_overlap as T
+pkg = conftest.load_pkg()
+h, n, K = 10, 512, 14
+seq = pkg.make_batch_sequence(n, h, "a1", seed=0x91BE, steps=K, frac_all_stance=0.3, excite=1.5)
+ser, _, _, _ = T._run_sequence(pkg, seq, h, n, "serial", True)
+ovl, _, _, stats = T._run_sequence(pkg, seq, h, n, "overlap", False)
+print("STATS", stats)
+for k, (x, y) in enumerate(zip(ser, ovl)):
+    assert np.all(np.isfinite(y["tau"])) and np.all(np.isfinite(y["force"])), k
+    assert np.all(G.flags(y["status"]) & 0x02000000 == 0), k
+    ok = (G.flags(x["status"]) == 0) & (G.flags(y["status"]) == 0)
+    ef = np.abs(x["force"] - y["force"]).max(1) / np.maximum(1.0, np.abs(x["force"]).max(1))
+    et = (np.abs(x["tau"] - y["tau"]) / np.maximum(1.0, np.abs(x["tau"]))).max(1)
+    print("TICK", k, ok.mean(), ef[ok].max(), et[ok].max())
+    assert ok.mean() > 0.97, (k, ok.mean())
+    assert ef[ok].max() <= 1e-6 and et[ok].max() <= 1e-5, (k, ef[ok].max(), et[ok].max())
+assert stats[0] + stats[1] < K, stats          # some ticks really were held
+print("HOLD11_OK")
+"""
+
+
+def test_overlap_hold_arms_expires_and_rearms():
+    """The h <= 11 hold of an overlapped context (a process of its own: QRGPU_OV_PLAN_HOLD=3 is read once): the population of
+    test_overlapped_ticks_with_robots_on_the_list_launches for 14 ticks -- a lane finds a plan, three calls run as plain pipelined ticks, the
+    context looks again, overlaps or re-arms.  Every tick against the serial tick with that test's tolerances, and fewer than 14 ticks overlapped."""
+    env = dict(os.environ, QRGPU_OV_PLAN_HOLD="3", GPU_MAX_HW_QUEUES="8")
+    r = subprocess.run([sys.executable, "-c", _HOLD11 % dict(root=ROOT)], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert "HOLD11_OK" in r.stdout
+
+
+_HOLD16 = r"""
+import os, sys
+sys.path.insert(0, os.path.join(%(root)r, "tests"))
+import numpy as np
+import conftest, gpu_helpers as G
+import test_gpu_overlap as T
+pkg = conftest.load_pkg()
+h, n, K = 16, 256, 14
+seq = pkg.make_batch_sequence(n, h, "a1", seed=0x16AD, steps=K, frac_all_stance=0.6, excite=1.0)
+listed = np.mean([(np.asarray(b["gait"]).reshape(n, -1).sum(1) >= 43).mean() for b in seq])
+print("LISTED", listed)
+assert listed > 0.45                 # the class that cannot share a CU is more than 45 %% of the batch: the two-to-a-CU form goes on hold
+ser, _, _, _ = T._run_sequence(pkg, seq, h, n, "serial", True)
+pip, _, _, _ = T._run_sequence(pkg, seq, h, n, "piped", False)
+T._compare_ticks(ser, pip, "piped vs serial across the two-to-a-CU hold")
+print("HOLD16_OK")
+"""
+
+
+def test_h16_two_to_a_cu_hold_arms_expires_and_rearms():
+    """The h > 11 hold of the two-to-a-CU main pass (a process of its own: QRGPU_H16_TWO=2 lets 256 robots run two to a CU, QRGPU_H16_TWO_HOLD=3
+    shortens the hold): 60 % of the robots stand, so the planned list outgrows 45 % of the batch, the calls go back to one workgroup per CU for
+    three calls, probe, and re-arm -- several times in 14 ticks.  The pipelined tick against the serial tick, tick by tick, with _compare's
+    tolerances: nobody timed out, the same robots flagged on both sides (within two), clean robots within 1e-6 / 1e-5.  (excite = 1.0: the CPU
+    oracle alone leaves every robot of this population clean in all 14 ticks, so a flagged robot here is the GPU's doing.)"""
+    env = dict(os.environ, QRGPU_H16_TWO="2", QRGPU_H16_TWO_HOLD="3", GPU_MAX_HW_QUEUES="8")
+    r = subprocess.run([sys.executable, "-c", _HOLD16 % dict(root=ROOT)], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert "HOLD16_OK" in r.stdout
