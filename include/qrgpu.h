@@ -135,7 +135,12 @@ typedef enum {
 #define QRGPU_ST_WBC_INFEAS    0x20
 #define QRGPU_ST_VMC_MAXITER   0x40
 #define QRGPU_ST_VMC_INFEAS    0x80   /* QuadProg++ would have returned +inf (e.g. the 1e-7 window of a swing foot, qr_qp_torque_optimizer.cpp:79-81);
-                                         the force is the iterate QuadProg++ stops at, which is what the reference goes on to use (:281-297) */
+                                         the force is the iterate QuadProg++ stops at, which is what the reference goes on to use (:281-297).
+                                         On up to 0.7 % of the ticks of a measured batch (three stance feet on a pitched normal, friction 0.55
+                                         and more; none in 3 000 ticks at the default 0.5, none in 2 000 on level ground at 0.9) that iterate
+                                         is decided by the rounding inside QuadProg++ and can be 1e6 .. 5e9 N: there only this flag is
+                                         guaranteed, and the force returned is finite and of the order of the robot's weight (DESIGN.md 4.6,
+                                         LAB_NOTES A.9, tests/golden/vmc_grid_golden.npz well_posed) */
 
 /* What BuildDynamicModel reads from YAML plus what the WBC controller hard-codes.
  * Defaults (qrgpu_model_desc_default) are the A1 values. */
@@ -152,7 +157,10 @@ typedef struct {
 void qrgpu_model_desc_default(qrgpu_model_desc *d);
 
 /* Per-type constants of the force-balance (VMC) QP: ComputeContactForce's non-per-tick arguments.  Defaults: A1 + the header defaults
- * (QI/controllers/balance_controller/qr_qp_torque_optimizer.h:144-153), acc_weight of config/a1_sim/stance_leg_controller.yaml. */
+ * (QI/controllers/balance_controller/qr_qp_torque_optimizer.h:144-153), acc_weight of config/a1_sim/stance_leg_controller.yaml.
+ * friction: 0.5 is the control-frame overload's default (:144-153).  The world-frame overload's own default is 0.6
+ * (qr_qp_torque_optimizer.h:171-182), and TorqueStanceLegController::GetAction passes none (qr_torque_stance_leg_controller.cpp:496-498):
+ * a type that stands for that call is set up with friction = 0.6. */
 typedef struct {
     float mass;                           /* robot->totalMass */
     float inertia[9];                     /* robot->totalInertia, Eigen column-major (the YAML list as mapped by MatrixXf::Map) */
@@ -309,6 +317,9 @@ int qrgpu_mpc_frontend_batch(qrgpu_ctx *ctx, int n, int num_horizon_l, float dt_
 
 /* Force-balance stance forces of n robots: contact forces in the base frame, force[3*leg+axis] (the 3x4 matrix ComputeContactForce
  * returns, column-major) and, when d_q and d_tau are given, the joint torques J^T f of MapContactForceToJointTorques. */
+/* d_type_id [n] may be NULL: every robot is then of type 0 (QRGPU_ERR_NOT_SETUP if type 0 was not set up).  With d_type_id, a robot whose
+ * id is outside the table or names a type that was never set up is computed with the first type that was, and carries QRGPU_ST_BAD_TYPE
+ * (QRGPU_ERR_NOT_SETUP if no type was set up at all).  The same holds for qrgpu_vmc_force_world_batch. */
 int qrgpu_vmc_setup(qrgpu_ctx *ctx, int type_id, const qrgpu_vmc_desc *desc);
 int qrgpu_vmc_force_batch(qrgpu_ctx *ctx, int n, const int *d_type_id, const float *d_vmc_in, const float *d_q /*[12][n], may be NULL*/,
                           float *d_force, float *d_tau /*may be NULL*/, int *d_status /*may be NULL*/);
@@ -316,7 +327,8 @@ int qrgpu_vmc_force_batch(qrgpu_ctx *ctx, int n, const int *d_type_id, const flo
  * user_parameters.yaml computeForceInWorldFrame is true, qr_torque_stance_leg_controller.cpp:490-498): the same QP with, in d_vmc_in,
  * Rcb := rotMat (base -> world, quaternionToRotationMatrix(quat)^T), gvec := (0, 0, 9.8), normal := (0, 0, 1) -- the tangents are then the
  * world x and y axes, as GetAction passes them -- and per-leg force-window ratios d_ratio [8][n] = fMinRatio[4], fMaxRatio[4] (the Vec4
- * members that the walk mode changes per tick, :128-152).  Forces come back in the base frame, as RigidTransform(0, quat, X^T) returns them. */
+ * members that the walk mode changes per tick, :128-152).  Forces come back in the base frame, as RigidTransform(0, quat, X^T) returns them.
+ * d_type_id may be NULL (type 0), as above.  The reference runs this overload with frictionCoef = 0.6 (see qrgpu_vmc_desc). */
 int qrgpu_vmc_force_world_batch(qrgpu_ctx *ctx, int n, const int *d_type_id, const float *d_vmc_in, const float *d_ratio, const float *d_q,
                                 float *d_force, float *d_tau, int *d_status);
 

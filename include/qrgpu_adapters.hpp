@@ -31,6 +31,7 @@ struct Global {
     double q_soln[12] = {0};          // only indices 0..11 are ever read (qr_mpc_stance_leg_controller.cpp:404)
     int status = 0;
     float prev_ori_vel[3] = {0, 0, 0};
+    bool vmc_world_set = false;       // VmcSetupWorld has filled the world-frame slot; until then VmcSetup fills it too
 };
 inline Global &global()
 {
@@ -166,6 +167,10 @@ inline int VmcContactForce(Robot *robot, const float Rcb[9], const float g3[3], 
 // The world-frame overload, ComputeContactForce(robot, desiredAcc, contacts, accWeight, normal, tangent1, tangent2, fMinRatio, fMaxRatio, ...)
 // (qr_qp_torque_optimizer.cpp:304-398) as TorqueStanceLegController::GetAction calls it with the identity's columns (:490-498):
 // rotMat = quaternionToRotationMatrix(robot->GetBaseOrientation()).transpose(), row-major; V4 ratios are the controller's Vec4 members.
+// The reference gives this overload a frictionCoef of its own (0.6, qr_qp_torque_optimizer.h:171-182; GetAction passes none), so it reads
+// its constants from a type slot of its own, filled by VmcSetupWorld.  A site that never calls VmcSetupWorld runs both overloads on
+// VmcSetup's constants: VmcSetup fills this slot as well until VmcSetupWorld has taken it over.
+constexpr int kVmcWorldType = 1;
 template <class Robot, class V6, class V4b, class V4min, class V4max, class M34>
 inline int VmcContactForceWorld(Robot *robot, const float rotMat[9], const V6 &desiredAcc, const V4b &contacts, const V4min &fMinRatio, const V4max &fMaxRatio, M34 &out)
 {
@@ -180,7 +185,7 @@ inline int VmcContactForceWorld(Robot *robot, const float rotMat[9], const V6 &d
     in[31] = 0.f; in[32] = 0.f; in[33] = 9.8f; in[34] = 0.f; in[35] = 0.f; in[36] = 1.f;
     float f[12];
     int status = 0;
-    int rc = qrgpu_vmc_force_world1(g.ctx, 0, in, ratio, nullptr, f, nullptr, &status);
+    int rc = qrgpu_vmc_force_world1(g.ctx, kVmcWorldType, in, ratio, nullptr, f, nullptr, &status);
     if (rc != QRGPU_OK) return rc;
     for (int l = 0; l < 4; ++l) for (int i = 0; i < 3; ++i) out(i, l) = f[3 * l + i];
     return status;
@@ -190,7 +195,20 @@ inline int VmcSetup(const qrgpu_vmc_desc &d)
 {
     auto &g = global();
     if (!g.ctx) return QRGPU_ERR_NO_DEVICE;
-    return qrgpu_vmc_setup(g.ctx, 0, &d);
+    int rc = qrgpu_vmc_setup(g.ctx, 0, &d);
+    if (rc != QRGPU_OK || g.vmc_world_set) return rc;
+    return qrgpu_vmc_setup(g.ctx, kVmcWorldType, &d);
+}
+
+// Constants of the world-frame overload (VmcContactForceWorld).  d.friction is the caller's: qrgpu_vmc_desc_default gives the
+// control-frame default 0.5, the reference's world-frame call runs with 0.6.
+inline int VmcSetupWorld(const qrgpu_vmc_desc &d)
+{
+    auto &g = global();
+    if (!g.ctx) return QRGPU_ERR_NO_DEVICE;
+    int rc = qrgpu_vmc_setup(g.ctx, kVmcWorldType, &d);
+    if (rc == QRGPU_OK) g.vmc_world_set = true;
+    return rc;
 }
 
 }  // namespace qrgpu_adapters

@@ -11,6 +11,12 @@
 // QX/QuadProgpp/src/main.cc:8-20.
 //
 // Convention (QuadProg++.hh:8-23):  min 1/2 x'Gx + g0'x,  CE'x + ce0 = 0,  CI'x + ci0 >= 0.
+//
+// quadprog_rounding (the force-balance QP only): the same method with every floating-point operation in the order QuadProg++
+// evaluates it, and its step rules (t2 < 0 => no primal step, |t - t2| < eps => full step).  A strictly convex QP does not need
+// that -- but a swing foot's contradictory pair n'x >= 1e-7, -n'x >= 1e-7 makes QuadProg++ return +inf with "the iterate it
+// had", and which row of the pair it tries first is decided by the sign of a 1e-14 residue of x; the two orders end 1e6 N apart.
+// The reference is deterministic there, so the oracle follows it to the bit (tests/test_oracle_vmc.py, LAB_NOTES "VMC grid").
 #include "qr_oracle.h"
 #include <limits>
 #include <algorithm>
@@ -27,6 +33,7 @@ struct GI {
     std::vector<int> A;        // active constraint ids (equalities: -(i+1); inequalities: i)
     int q = 0;
     double Rnorm = 1.0;
+    bool qpp = false;          // QuadProg++'s own rounding (qp_solve_gi's quadprog_rounding)
 
     explicit GI(int n_) : n(n_), J((size_t)n_ * n_), R((size_t)n_ * n_, 0.0), d(n_), z(n_), r(n_), u(n_ + 1), np(n_), A(n_ + 1) {}
     double &Jm(int i, int j) { return J[(size_t)i * n + j]; }
@@ -53,14 +60,23 @@ struct GI {
             r[i] = (d[i] - s) / Rm(i, i);
         }
     }
-    static double hyp(double a, double b) { return std::hypot(a, b); }
+    // qpp: |(a, b)| scaled by the larger entry, as QuadProg++ evaluates it -- std::hypot differs from that in the last bit
+    double hyp(double a, double b) const {
+        if (!qpp) return std::hypot(a, b);
+        const double a1 = std::fabs(a), b1 = std::fabs(b);
+        if (a1 > b1) { const double t = b1 / a1; return a1 * std::sqrt(1.0 + t * t); }
+        if (b1 > a1) { const double t = a1 / b1; return b1 * std::sqrt(1.0 + t * t); }
+        return a1 * std::sqrt(2.0);
+    }
+    // QuadProg++ skips a rotation when |h| < eps (and leaves d[j] where it is), not only when h == 0
+    bool no_rotation(double h) const { return qpp ? std::fabs(h) < std::numeric_limits<double>::epsilon() : h == 0.0; }
 
     bool add_constraint() {
         // Givens rotations zeroing d[n-1..q+1]; same rotations applied to J's columns.
         for (int j = n - 1; j >= q + 1; --j) {
             double cc = d[j - 1], ss = d[j];
             double h = hyp(cc, ss);
-            if (h == 0.0) continue;
+            if (no_rotation(h)) continue;
             d[j] = 0.0;
             ss /= h; cc /= h;
             if (cc < 0.0) { cc = -cc; ss = -ss; d[j - 1] = -h; } else d[j - 1] = h;
@@ -92,7 +108,7 @@ struct GI {
         for (int j = l; j < q; ++j) {
             double cc = Rm(j, j), ss = Rm(j + 1, j);
             double h = hyp(cc, ss);
-            if (h == 0.0) continue;
+            if (no_rotation(h)) continue;
             cc /= h; ss /= h;
             Rm(j + 1, j) = 0.0;
             if (cc < 0.0) { Rm(j, j) = -h; cc = -cc; ss = -ss; } else Rm(j, j) = h;
@@ -114,12 +130,15 @@ struct GI {
 }  // namespace
 
 int qp_solve_gi(int n, const double *G, const double *g0, int p, const double *CE, const double *ce0,
-                int m, const double *CI, const double *ci0, double *x, double *lambda_ineq, QpStats *st, int max_iter, double abs_tol)
+                int m, const double *CI, const double *ci0, double *x, double *lambda_ineq, QpStats *st, int max_iter, double abs_tol,
+                bool quadprog_rounding)
 {
+    const bool qpp = quadprog_rounding;
     const double inf = std::numeric_limits<double>::infinity();
     const double eps = std::numeric_limits<double>::epsilon();
     if (max_iter <= 0) max_iter = 50 * (n + m + p) + 100;
     GI s(n);
+    s.qpp = qpp;
     QpStats stats;
 
     // Cholesky G = L L^T (lower).
@@ -128,18 +147,33 @@ int qp_solve_gi(int n, const double *G, const double *g0, int p, const double *C
     for (int i = 0; i < n; ++i) c1 += G[(size_t)i * n + i];
     for (int j = 0; j < n; ++j) {
         double sum = G[(size_t)j * n + j];
+        if (qpp) for (int k = j - 1; k >= 0; --k) sum -= L[(size_t)j * n + k] * L[(size_t)j * n + k];
+        else
         for (int k = 0; k < j; ++k) sum -= L[(size_t)j * n + k] * L[(size_t)j * n + k];
         if (sum <= 0.0) return 3;   // not positive definite
         double ljj = std::sqrt(sum);
         L[(size_t)j * n + j] = ljj;
         for (int i = j + 1; i < n; ++i) {
             double v = G[(size_t)i * n + j];
+            if (qpp) for (int k = j - 1; k >= 0; --k) v -= L[(size_t)j * n + k] * L[(size_t)i * n + k];
+            else
             for (int k = 0; k < j; ++k) v -= L[(size_t)i * n + k] * L[(size_t)j * n + k];
             L[(size_t)i * n + j] = v / ljj;
         }
     }
     // J = L^-T : column j of J solves L^T J(:,j) = e_j.
     double c2 = 0.0;
+    if (qpp) {
+        // row i of J solves L z = e_i by forward elimination, in QuadProg++'s operation order
+        for (int i = 0; i < n; ++i) {
+            for (int k = 0; k < n; ++k) {
+                double v = (k == i) ? 1.0 : 0.0;
+                for (int j = 0; j < k; ++j) v -= L[(size_t)k * n + j] * s.Jm(i, j);
+                s.Jm(i, k) = v / L[(size_t)k * n + k];
+            }
+            c2 += s.Jm(i, i);
+        }
+    } else
     for (int j = 0; j < n; ++j) {
         for (int i = n - 1; i >= 0; --i) {
             double v = (i == j) ? 1.0 : 0.0;
@@ -188,8 +222,9 @@ int qp_solve_gi(int n, const double *G, const double *g0, int p, const double *C
         // Step 1: most violated inactive inequality.
         double psi = 0.0, smin = 0.0; int ip = -1;
         for (int i = 0; i < m; ++i) {
-            double v = ci0[i];
+            double v = qpp ? 0.0 : ci0[i];                          // QuadProg++ adds the offset last
             for (int k = 0; k < n; ++k) v += CI[(size_t)k * m + i] * x[k];
+            if (qpp) v += ci0[i];
             sv[i] = v;
             psi += std::min(0.0, v);
             if (!active[i] && !excluded[i] && v < smin) { smin = v; ip = i; }
@@ -215,6 +250,7 @@ int qp_solve_gi(int n, const double *G, const double *g0, int p, const double *C
             double zz = 0, znp = 0;
             for (int k = 0; k < n; ++k) { zz += s.z[k] * s.z[k]; znp += s.z[k] * s.np[k]; }
             double t2 = (std::fabs(zz) > eps) ? -sv[ip] / znp : inf;
+            if (qpp && t2 < 0.0) t2 = inf;        // z'np < 0 is the rounding of a dependent row: QuadProg++ takes no primal step
             double t = std::min(t1, t2);
             if (t >= inf) { status = 1; break; }
             if (t2 >= inf) {
@@ -229,7 +265,7 @@ int qp_solve_gi(int n, const double *G, const double *g0, int p, const double *C
             for (int k = 0; k < n; ++k) x[k] += t * s.z[k];
             for (int k = 0; k < s.q; ++k) s.u[k] -= t * s.r[k];
             s.u[s.q] += t;
-            if (t == t2) {
+            if (qpp ? std::fabs(t - t2) < eps : t == t2) {
                 // full step: ip becomes active
                 if (!s.add_constraint()) {
                     // numerically dependent on the working set: leave it out (it is satisfied to rounding)
@@ -244,8 +280,9 @@ int qp_solve_gi(int n, const double *G, const double *g0, int p, const double *C
                 active[s.A[l]] = 0;
                 s.delete_constraint(l);
                 ++stats.drops;
-                double v = ci0[ip];
+                double v = qpp ? 0.0 : ci0[ip];
                 for (int k = 0; k < n; ++k) v += CI[(size_t)k * m + ip] * x[k];
+                if (qpp) v += ci0[ip];
                 sv[ip] = v;
             }
         }

@@ -115,7 +115,8 @@ int vmc_solve(const VmcConfig &c, const VmcInput &in, float force[12], double xo
     for (int i = 0; i < 288; ++i) CC[i] = (double)CI[i];
     for (int i = 0; i < 24; ++i) bb[i] = (double)(-b[i]);
     double x[12];
-    const int rc = qp_solve_gi(12, GG, aa, 0, nullptr, nullptr, 24, CC, bb, x, nullptr, st);
+    // quadprog_rounding: on a +inf tick the iterate QuadProg++ stops at depends on its own rounding (qr_oracle_qp.cpp)
+    const int rc = qp_solve_gi(12, GG, aa, 0, nullptr, nullptr, 24, CC, bb, x, nullptr, st, 0, 0.0, true);
     bool bad = false;
     for (int i = 0; i < 12; ++i) if (std::isnan(x[i])) bad = true;
     float X[4][3];

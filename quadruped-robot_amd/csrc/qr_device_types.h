@@ -158,6 +158,7 @@ struct VmcType {
 struct VmcLaunch {
     VmcType type[QR_MAX_TYPES];
     int n;
+    int type_ready;          // bit t: type t was set up (robots naming any other type are flagged QRGPU_ST_BAD_TYPE)
     const float *ratio;      // [8][n] per-leg fMinRatio[4], fMaxRatio[4] of the world-frame overload, or null (the type's scalar ratios)
 };
 

@@ -749,10 +749,10 @@ static int launch_vmc(qrgpu_ctx *c, int n, const int *d_type_id, const float *d_
 {
     if (!c || n <= 0 || n > c->max_batch || !d_vmc_in || !d_force) return QRGPU_ERR_BAD_ARG;
     if (d_tau && !d_q) return QRGPU_ERR_BAD_ARG;
-    if (!c->vmc_ready[0]) return QRGPU_ERR_NOT_SETUP;
+    if (!(d_type_id ? ready_mask(c->vmc_ready) != 0 : c->vmc_ready[0])) return QRGPU_ERR_NOT_SETUP;
     HIPCHK(c, hipSetDevice(c->device));
     VmcLaunch P = c->vmc;
-    P.n = n; P.ratio = d_ratio;
+    P.n = n; P.ratio = d_ratio; P.type_ready = ready_mask(c->vmc_ready);
     hipLaunchKernelGGL(qr_vmc_kernel, dim3(8 * ((n + 7) / 8)), dim3(64), 0, c->stream, P, d_type_id, d_vmc_in, d_q, d_force, d_tau, d_status);
     HIPCHK(c, hipGetLastError());
     return QRGPU_OK;
@@ -893,7 +893,7 @@ static int vmc_force1(qrgpu_ctx *c, int type_id, const float vmc_in[37], const f
     int *d_type = nullptr;
     { const int rc_ = stage_in(c, in, sizeof(in) / sizeof(float), type_id, &d_type); if (rc_) return rc_; }
     VmcLaunch P = c->vmc;
-    P.n = 1; P.ratio = ratio ? c->d_in1 + 49 : nullptr;
+    P.n = 1; P.ratio = ratio ? c->d_in1 + 49 : nullptr; P.type_ready = ready_mask(c->vmc_ready);
     hipLaunchKernelGGL(qr_vmc_kernel, dim3(8), dim3(64), 0, c->stream, P, d_type, c->d_in1, q ? c->d_in1 + 37 : nullptr, c->d_out1,
                        (q && tau_out) ? c->d_out1 + 12 : nullptr, c->d_st1);
     HIPCHK(c, hipGetLastError());

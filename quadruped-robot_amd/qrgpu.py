@@ -213,6 +213,7 @@ def load_library():
     lib.qrgpu_swing_update_batch.argtypes = [vp, ip, C.POINTER(swing_mode_desc_struct), ip, ip] + [vp] * 9
     lib.qrgpu_swing_action_batch.argtypes = [vp, ip, C.POINTER(swing_mode_desc_struct), C.POINTER(estimator_desc_struct), ip] + [vp] * 7
     lib.qrgpu_vmc_force1.argtypes = [vp, ip, fp, fp, fp, fp, C.POINTER(ip)]
+    lib.qrgpu_vmc_force_world1.argtypes = [vp, ip, fp, fp, fp, fp, fp, C.POINTER(ip)]
     lib.qrgpu_mpc_frontend_batch.argtypes = [vp, ip, ip, C.c_float, C.c_float] + [vp] * 6
     lib.qrgpu_fb_debug_batch.argtypes = [vp, ip, vp, vp, vp]
     lib.qrgpu_mpc_solve1.argtypes = [vp, ip] + [fp] * 9 + [C.POINTER(C.c_double), fp, C.POINTER(ip)]
@@ -471,6 +472,15 @@ class Context:
         f = np.zeros(12, np.float32); tau = np.zeros(12, np.float32); st = C.c_int(0)
         self._chk(self._lib.qrgpu_vmc_force1(self._h, type_id, _fp(a), _fp(qa) if qa is not None else None, _fp(f),
                                              _fp(tau) if qa is not None else None, C.byref(st)))
+        return f, (tau if qa is not None else None), st.value
+
+    def vmc_force_world1(self, vmc_in, ratio, q=None, type_id=0):
+        """One robot through the world-frame overload (qrgpu_vmc_force_world1): ratio = fMinRatio[4], fMaxRatio[4]."""
+        a = np.ascontiguousarray(vmc_in, np.float32); r = np.ascontiguousarray(ratio, np.float32)
+        qa = np.ascontiguousarray(q, np.float32) if q is not None else None
+        f = np.zeros(12, np.float32); tau = np.zeros(12, np.float32); st = C.c_int(0)
+        self._chk(self._lib.qrgpu_vmc_force_world1(self._h, type_id, _fp(a), _fp(r), _fp(qa) if qa is not None else None, _fp(f),
+                                                   _fp(tau) if qa is not None else None, C.byref(st)))
         return f, (tau if qa is not None else None), st.value
 
     def estimator_state_doubles(self, window):

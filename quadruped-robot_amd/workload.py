@@ -316,7 +316,7 @@ def make_vmc_batch(n, robot="a1", seed=0xB2, sloped=0.0, excite=1.0):
     r = ROBOTS[robot]
     q = np.tile(np.array([0.0, 0.9, -1.8], f32), (n, 4)) + 0.25 * rng.standard_normal((n, 12)).astype(f32)
     vin = np.zeros((n, 37), f32)
-    hip_off = np.array([[0.1805, -0.047, 0], [0.1805, 0.047, 0], [-0.1805, -0.047, 0], [-0.1805, 0.047, 0]], f32)
+    hip_off = np.array(r["hip_offset"], f32)
     # foot positions in the base frame from the leg kinematics (qr_robot.cpp:127-146)
     for leg in range(4):
         tab, thip, tknee = q[:, 3 * leg], q[:, 3 * leg + 1], q[:, 3 * leg + 2]

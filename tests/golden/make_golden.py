@@ -178,6 +178,96 @@ def vmc_world_golden():
     print("vmc_world_golden.npz: 40 cases, %d with QuadProg++ returning +inf" % int(np.sum(infs)))
 
 
+# Force-balance QP away from the A1 defaults.  Control-frame cells: make_vmc_batch(n, robot, seed, sloped, excite) with vmc_cfg(robot, **kw);
+# world cells: make_vmc_world_batch(n, robot, seed).  `listed`: cases on which the oracle was once seen to leave QuadProg++ -- always kept.
+VMC_GRID = [
+    dict(name="a1_mu060", robot="a1", n=1000, seed=40, sloped=0.5, excite=1.0, kw=dict(friction=0.6), world=False, listed=(23, 113, 220)),
+    dict(name="a1_mu065", robot="a1", n=1000, seed=40, sloped=0.5, excite=1.0, kw=dict(friction=0.65), world=False, listed=(277,)),
+    dict(name="a1_mu070", robot="a1", n=1000, seed=40, sloped=0.5, excite=1.0, kw=dict(friction=0.7), world=False, listed=(191, 317)),
+    dict(name="a1_mu070_s15", robot="a1", n=300, seed=15, sloped=0.3, excite=1.0, kw=dict(friction=0.7), world=False, listed=(19,)),
+    dict(name="a1_mu080_fmax1", robot="a1", n=400, seed=22, sloped=0.5, excite=1.0, kw=dict(friction=0.8, fmax_ratio=1.0), world=False,
+         listed=(37, 49, 55)),
+    # (first scanned with every robot pitched, sloped = 1.0: 4 of 300 were not well-posed, over the 1 % cap.  sloped = 0.75 levels robots
+    # 225..299 and leaves the others, the listed ones among them, bit for bit as they were)
+    dict(name="a1_mu090_sloped", robot="a1", n=300, seed=13, sloped=0.75, excite=1.0, kw=dict(friction=0.9), world=False,
+         listed=(116, 151, 205)),
+    dict(name="a1_mu020_x3", robot="a1", n=300, seed=9, sloped=0.3, excite=3.0, kw=dict(friction=0.2), world=False, listed=()),
+    dict(name="a1_fmax1_x3", robot="a1", n=300, seed=10, sloped=0.3, excite=3.0, kw=dict(fmax_ratio=1.0), world=False, listed=()),
+    dict(name="a1_weights", robot="a1", n=300, seed=12, sloped=0.5, excite=2.0, kw=dict(acc_weight=(5, 5, 1, 1, 1, 20), reg_weight=1e-3),
+         world=False, listed=()),
+    dict(name="lite3", robot="lite3", n=300, seed=7, sloped=0.3, excite=1.0, kw=dict(), world=False, listed=()),
+    dict(name="a1_world_mu060", robot="a1", n=1000, seed=50, sloped=0.0, excite=1.0, kw=dict(friction=0.6), world=True, listed=()),
+    dict(name="lite3_world_mu060", robot="lite3", n=800, seed=53, sloped=0.0, excite=1.0, kw=dict(friction=0.6), world=True, listed=()),
+]
+VMC_GRID_KEEP = 48              # the first cases of every cell are kept, plus the listed and the not-well-posed ones
+# well_posed: runs, relative perturbation of the linear term a, relative perturbation of G, bar on the relative change of x, seed
+VMC_GRID_PERTURB = (8, 1e-7, 1e-12, 1e-2, 0x5EED)
+
+
+def vmc_grid_inputs(cell):
+    """-> cfg[20], geom[3], vin[n][37], q[n][12], ratio[n][8] or None: the cell's whole batch."""
+    cfg = W.vmc_cfg(cell["robot"], **cell["kw"]); geom = W.model_desc(cell["robot"])[:3]
+    if cell["world"]:
+        vin, q, ratio = W.make_vmc_world_batch(cell["n"], cell["robot"], seed=cell["seed"], excite=cell["excite"])
+    else:
+        vin, q = W.make_vmc_batch(cell["n"], cell["robot"], seed=cell["seed"], sloped=cell["sloped"], excite=cell["excite"])
+        ratio = None
+    return cfg, geom, vin, q, ratio
+
+
+def vmc_grid_scan(cell):
+    """The reference's QuadProg++ on every case of the cell, called as qr_qp_torque_optimizer.cpp:242-276 does.  -> the inputs, x_quadprog
+    [n][12], quadprog_inf [n] and well_posed [n].  well_posed is a property of the reference alone; it asks whether the iterate QuadProg++
+    stops at is a function of the problem or of rounding.  QuadProg++ is run again
+      * 8 times with the linear term scaled entrywise by 1 + 1e-7 U(-1, 1) -- below the fp32 rounding (6e-8) of what the reference assembles;
+      * 8 times with G scaled entrywise (symmetrically) by 1 + 1e-12 U(-1, 1) -- 1e4 ulps of the doubles it computes in, 1e-5 of the fp32
+        rounding of G: the optimum of a feasible tick (amplification <= 1e6, qr_oracle_vmc.cpp) moves by 1e-6 at the most, but the rounding
+        residues inside the solver are redrawn.  On a +inf tick the sign of such a residue (the 1e-14 left of a swing foot's force decides
+        which row of its 1e-7 pair is tried first; a z of pure rounding, |z|^2 > eps, is stepped along for 1e7 s) can decide between an
+        iterate of 50 N and one of 1e8 N -- another build of the reference (other flags, FMA) would stop elsewhere.
+    and its answer must not move by more than 1e-2 * max(1, |x|max) in any run.  Where it does, x_quadprog pins nothing but the flag."""
+    cfg, geom, vin, q, ratio = vmc_grid_inputs(cell)
+    runs, rel_a, rel_G, bar, seed = VMC_GRID_PERTURB
+    n = cell["n"]
+    xs = np.zeros((n, 12)); infs = np.zeros(n, bool); wp = np.zeros(n, bool)
+    rng = np.random.default_rng(seed)
+    E, e0 = np.zeros((12, 0)), np.zeros(0)
+    for i in range(n):
+        G, a, CI, b = O.vmc_assemble(cfg, vin[i], None if ratio is None else ratio[i])
+        GG, aa, CC, bb = G.T.astype(np.float64), -a.astype(np.float64), CI.astype(np.float64), -b.astype(np.float64)
+        x, f = O.ref_quadprog(GG, aa, E, e0, CC, bb)
+        worst = 0.0
+        for k in range(2 * runs):
+            if k < runs:
+                xp, _f = O.ref_quadprog(GG, aa * (1.0 + rel_a * rng.uniform(-1, 1, 12)), E, e0, CC, bb)
+            else:
+                P = np.triu(1.0 + rel_G * rng.uniform(-1, 1, (12, 12))); P = P + np.triu(P, 1).T
+                xp, _f = O.ref_quadprog(GG * P, aa, E, e0, CC, bb)
+            worst = max(worst, np.abs(xp - x).max() / max(1.0, np.abs(x).max()))
+        xs[i] = x; infs[i] = not np.isfinite(f); wp[i] = bool(np.all(np.isfinite(x))) and worst < bar
+    bad = np.flatnonzero(~wp)
+    # conditions on the inputs, not on any solver of ours: a cell that breaks them gets other inputs, never another cap
+    assert len(bad) <= 0.01 * n, (cell["name"], bad)
+    assert np.all(infs[bad]), (cell["name"], "a feasible tick is not well-posed")
+    return dict(cfg=cfg, geom=geom, vin=vin, q=q, ratio=ratio, x_quadprog=xs, quadprog_inf=infs, well_posed=wp)
+
+
+def vmc_grid_golden(path=None):
+    """vmc_grid_golden.npz: per cell of VMC_GRID the kept cases (VMC_GRID_KEEP first, listed, not well-posed) with their index in the batch."""
+    flat = {"cells": np.array([c["name"] for c in VMC_GRID])}
+    for cell in VMC_GRID:
+        s = vmc_grid_scan(cell)
+        bad = np.flatnonzero(~s["well_posed"])
+        idx = np.array(sorted(set(range(min(VMC_GRID_KEEP, cell["n"]))) | set(cell["listed"]) | set(bad.tolist())))
+        k = cell["name"] + "_"
+        flat[k + "cfg"] = s["cfg"]; flat[k + "geom"] = s["geom"]; flat[k + "idx"] = idx
+        flat[k + "scanned"] = np.array([cell["n"], len(bad), int(s["quadprog_inf"].sum())])
+        for name in ("vin", "q", "x_quadprog", "quadprog_inf", "well_posed") + (("ratio",) if cell["world"] else ()):
+            flat[k + name] = s[name][idx]
+        print("vmc_grid %-20s scanned %4d  +inf %4d  not well-posed %d  kept %d" % (cell["name"], cell["n"], s["quadprog_inf"].sum(), len(bad), len(idx)))
+    np.savez_compressed(path or os.path.join(OUT, "vmc_grid_golden.npz"), **flat)
+
+
 def ekf_golden():
     """States of the reference's TinyEKF<3,3> (compiled from /root/reference) over three 200-step sequences."""
     rng = np.random.default_rng(4004)
@@ -276,6 +366,9 @@ if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "wbc":
         save("wbc_golden.npz", wbc_cases())
         sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "vmc_grid":
+        vmc_grid_golden()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "mpc":          # only the MPC fixture and the artefacts derived from it
         rows = mpc_cases()
         save("mpc_golden.npz", rows)
@@ -289,5 +382,6 @@ if __name__ == "__main__":
     save("wbc_golden.npz", wbc_cases())
     vmc_golden()
     vmc_world_golden()
+    vmc_grid_golden()
     ekf_golden()
     save("qp_golden.npz", qp_cases())

@@ -97,19 +97,32 @@ int main(int argc, char **argv)
         float acc[6]; bool ct[4];
         for (int i = 0; i < 6; ++i) acc[i] = vin[12 + i];
         for (int i = 0; i < 4; ++i) ct[i] = vin[18 + i] != 0.f;
-        Mat34f F;
-        int vst = qrgpu_adapters::VmcContactForce(&robot, vin + 22, vin + 31, vin + 34, acc, ct, F);
-        printf("vmcstatus %d\nvmcforce", vst);
-        for (int i = 0; i < 12; ++i) printf(" %.9g", F.m[i]);
-        printf("\n");
         // world-frame overload: 8 more numbers (fMinRatio[4], fMaxRatio[4]); Rcb of the input is then rotMat
         float ratio[8];
         bool have_world = true;
         for (float &x : ratio) if (scanf("%f", &x) != 1) { have_world = false; break; }
         if (have_world) {
+            // a site that calls VmcSetup alone: the world-frame overload runs on the same constants (friction 0.5)
             Mat34f FW;
             int wst = qrgpu_adapters::VmcContactForceWorld(&robot, vin + 22, acc, ct, ratio, ratio + 4, FW);
             printf("vmcwstatus %d\nvmcwforce", wst);
+            for (int i = 0; i < 12; ++i) printf(" %.9g", FW.m[i]);
+            printf("\n");
+            // then the world-frame slot gets the reference's world-frame friction.  A later VmcSetup must leave it alone, the 0.5 of the
+            // control-frame slot must not leak into it, nor its 0.6 into the control-frame result below
+            qrgpu_vmc_desc vw = vd; vw.friction = 0.6f;
+            if (qrgpu_adapters::VmcSetupWorld(vw) != 0) return 5;
+            if (qrgpu_adapters::VmcSetup(vd) != 0) return 4;
+        }
+        Mat34f F;
+        int vst = qrgpu_adapters::VmcContactForce(&robot, vin + 22, vin + 31, vin + 34, acc, ct, F);
+        printf("vmcstatus %d\nvmcforce", vst);
+        for (int i = 0; i < 12; ++i) printf(" %.9g", F.m[i]);
+        printf("\n");
+        if (have_world) {
+            Mat34f FW;
+            int wst = qrgpu_adapters::VmcContactForceWorld(&robot, vin + 22, acc, ct, ratio, ratio + 4, FW);
+            printf("vmcw06status %d\nvmcw06force", wst);
             for (int i = 0; i < 12; ++i) printf(" %.9g", FW.m[i]);
             printf("\n");
         }

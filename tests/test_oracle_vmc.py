@@ -5,6 +5,8 @@ import os
 import numpy as np
 import pytest
 
+import golden_io
+
 GOLD = os.path.join(os.path.dirname(__file__), "golden", "vmc_golden.npz")
 
 
@@ -121,3 +123,97 @@ def test_vmc_world_golden(pkg, oracle):
         assert (rc == 1) == bool(g["quadprog_inf"][i])
         Gq, aq, CIq, bq = oracle.vmc_assemble(g["cfg"], g["vin"][i], g["ratio"][i])
         assert np.array_equal(Gq, g["G"][i]) and np.array_equal(aq, g["a"][i]) and np.array_equal(bq, g["b"][i])
+
+
+# ---- the parameter grid (tests/golden/make_golden.py VMC_GRID): friction 0.2 .. 0.9, fMaxRatio 1, other weights, Lite3, both overloads ----
+GRID = golden_io.make_golden().VMC_GRID
+
+
+def _pin(x, rc, xq, qinf):
+    """The bar of test_vmc_matches_reference_quadprog: |x - x_quadprog| <= 1e-8 max(1, |x_quadprog|), and the same +inf verdict."""
+    return np.abs(x - xq).max() <= 1e-8 * max(1.0, np.abs(xq).max()) and (rc == 1) == bool(qinf)
+
+
+@pytest.fixture(scope="module")
+def grid_scans(ref):
+    """QuadProg++ (compiled reference) on every case of every cell, once per session: cell name -> vmc_grid_scan()."""
+    M = golden_io.make_golden()
+    return {c["name"]: M.vmc_grid_scan(c) for c in GRID}
+
+
+@pytest.mark.parametrize("cell", GRID, ids=[c["name"] for c in GRID])
+def test_vmc_grid_matches_reference_quadprog(oracle, grid_scans, cell):
+    """Live, whole batch of the cell: the oracle's x is QuadProg++'s on every well-posed case (vmc_grid_scan: the reference's iterate does
+    not depend on rounding -- its own criterion, no solver of ours looked at; it also asserts the 1 % cap and that every ill-posed case is
+    a +inf tick).  The oracle follows QuadProg++'s rounding operation by operation (qr_oracle_qp.cpp quadprog_rounding), so the same bar
+    is asked of the ill-posed cases too (oracle and reference solver come from the same compiler here, and agree to the bit); a miss there
+    names the case and says so."""
+    s = grid_scans[cell["name"]]
+    n = cell["n"]
+    worst = 0.0; miss_ill = []
+    for i in range(n):
+        force, tau, x, st, rc = oracle.vmc_solve(s["cfg"], s["geom"], s["vin"][i], s["q"][i], None if s["ratio"] is None else s["ratio"][i])
+        ok = _pin(x, rc, s["x_quadprog"][i], s["quadprog_inf"][i])
+        if s["well_posed"][i]:
+            assert ok, (cell["name"], i, np.abs(x - s["x_quadprog"][i]).max(), rc)
+            worst = max(worst, np.abs(x - s["x_quadprog"][i]).max() / max(1.0, np.abs(s["x_quadprog"][i]).max()))
+        elif not ok:
+            miss_ill.append(i)
+        assert np.all(np.isfinite(force)) and np.all(np.isfinite(tau)), (cell["name"], i)
+    print("%s: %d cases, %d +inf, %d not well-posed, worst |x_oracle - x_quadprog| rel %.2e" % (
+        cell["name"], n, s["quadprog_inf"].sum(), (~s["well_posed"]).sum(), worst))
+    assert 0 < s["quadprog_inf"].sum() < n
+    for i in cell["listed"]:               # the cases on which the oracle once left QuadProg++ by 1e6 N
+        force, tau, x, st, rc = oracle.vmc_solve(s["cfg"], s["geom"], s["vin"][i], s["q"][i])
+        assert _pin(x, rc, s["x_quadprog"][i], s["quadprog_inf"][i]), (cell["name"], i)
+    assert not miss_ill, (cell["name"], "ill-posed cases off QuadProg++'s own rounding", miss_ill)
+
+
+def test_vmc_grid_golden(pkg, oracle):
+    """The same pin from the committed file (no reference needed): every kept case of every cell."""
+    cells = golden_io.load_vmc_grid()
+    assert list(cells) == [c["name"] for c in GRID]
+    for cell in GRID:
+        g = cells[cell["name"]]
+        assert set(cell["listed"]) <= set(g["idx"].tolist()) and len(g["idx"]) >= min(48, cell["n"])
+        assert int(g["scanned"][0]) == cell["n"] and int(g["scanned"][1]) <= 0.01 * cell["n"]          # the 1 % cap on ill-posed cases
+        assert np.all(g["quadprog_inf"][~g["well_posed"]])                                              # no feasible tick is ill-posed
+        assert int((~g["well_posed"]).sum()) == int(g["scanned"][1])                                    # every ill-posed case was kept
+        assert np.array_equal(g["cfg"], pkg.workload.vmc_cfg(cell["robot"], **cell["kw"]))
+        for k in range(len(g["idx"])):
+            ratio = None if g["ratio"] is None else g["ratio"][k]
+            force, tau, x, st, rc = oracle.vmc_solve(g["cfg"], g["geom"], g["vin"][k], g["q"][k], ratio)
+            assert _pin(x, rc, g["x_quadprog"][k], g["quadprog_inf"][k]), (cell["name"], int(g["idx"][k]), bool(g["well_posed"][k]))
+
+
+def test_vmc_grid_golden_is_what_the_generator_gives(ref, grid_scans, tmp_path):
+    """The committed file is what make_golden.py vmc_grid writes, run again here, and what this session's own scan (a third run of the
+    reference) holds at the kept indices: batches, QuadProg++ and the perturbation seeds are deterministic."""
+    M = golden_io.make_golden()
+    committed = golden_io.load_vmc_grid()
+    path = str(tmp_path / "grid.npz")
+    M.vmc_grid_golden(path)
+    again = golden_io.load_vmc_grid(path)
+    assert list(again) == list(committed)
+    for name, c in committed.items():
+        for k, v in c.items():
+            assert (v is None and again[name][k] is None) or np.array_equal(v, again[name][k]), (name, k)
+        s = grid_scans[name]
+        assert np.array_equal(np.flatnonzero(~s["well_posed"]), c["idx"][~c["well_posed"]]), name
+        for k in ("vin", "q", "x_quadprog", "quadprog_inf", "well_posed"):
+            assert np.array_equal(s[k][c["idx"]], c[k]), (name, k)
+
+
+def test_vmc_batches_keep_their_bits_with_the_robots_own_hip_offsets(pkg):
+    """make_vmc_batch takes the hip offsets from the robot's table: A1's batches are unchanged (pinned through the golden inputs), Lite3's
+    feet stand under Lite3's hips."""
+    W = pkg.workload
+    g = np.load(GOLD)
+    vin, q = W.make_vmc_batch(48, sloped=0.25, seed=3003)
+    assert np.array_equal(vin, g["vin"]) and np.array_equal(q, g["q"])
+    gw = np.load(WGOLD)
+    vin, q, ratio = W.make_vmc_world_batch(40, seed=3004)
+    assert np.array_equal(vin, gw["vin"]) and np.array_equal(ratio, gw["ratio"])
+    vin, q = W.make_vmc_batch(16, "lite3", seed=7)
+    fp = W._foot_positions_base(W.ROBOTS["lite3"], q.astype(np.float64)).reshape(16, 12)
+    assert np.abs(vin[:, :12] - fp).max() <= 1e-6
