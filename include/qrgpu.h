@@ -27,6 +27,12 @@
  *   qrgpu_swing_targets_batch <- qrRaibertSwingLegController::GetAction (ADVANCED_TROT)   QS/controllers/qr_swing_leg_controller.cpp:362-424
  *   qrgpu_footholds_batch  <- qrRaibertSwingLegController::Update + qrFootholdPlanner::ComputeHeuristicFootHold
  *                             QS/controllers/qr_swing_leg_controller.cpp:211-236, QS/planner/qr_foothold_planner.cpp:110-239
+ *   qrgpu_stance_update_batch <- TorqueStanceLegController::UpdateFRatio + UpdateDesCommand   QS/controllers/balance_controller/
+ *                             qr_torque_stance_leg_controller.cpp:89-172, 174-477 (with qrComAdjuster::Update, QS/planner/qr_com_adjuster.cpp:61-108,
+ *                             and qrPosePlanner::GetIntermediateBasePose, QI/planner/qr_pose_planner.h:327-365)
+ *   qrgpu_stance_command_batch <- the motor-command tail of TorqueStanceLegController::GetAction (:503-541) + qrLocomotionController::GetAction's
+ *                             merge with the swing command   QS/controllers/qr_locomotion_controller.cpp:128-147
+ *   qrgpu_stance_tick_batch <- TorqueStanceLegController::GetAction (:480-545) + that merge: front-end, force-balance QP, motor commands
  *   qrgpu_tick_batch       <- one MPC solve + one WBC tick per robot, WBC fed with that MPC's Fr_des
  *                             (QS/fsm/qr_fsm_state_locomotion.cpp:130-158 without the MPC/WBC time-slicing)
  *   qrgpu_set_torque_epilogue <- the motor-command tail of that state: abad compensation (:141-151) and the +-23 N m clip
@@ -527,6 +533,75 @@ int qrgpu_swing_update_batch(qrgpu_ctx *ctx, int n, const qrgpu_swing_mode_desc 
 int qrgpu_swing_action_batch(qrgpu_ctx *ctx, int n, const qrgpu_swing_mode_desc *desc, const qrgpu_estimator_desc *geom, int robot_stop,
                              const float *d_est_in, const float *d_est_out, const float *d_gait_out, const float *d_gait_state,
                              float *d_swing_state, float *d_out, int *d_swing_flags);
+
+/* Stance front-end and motor commands of the force-balance modes (VELOCITY, POSITION, WALK, ADVANCED_TROT without MPC):
+ * TorqueStanceLegController::UpdateFRatio / UpdateDesCommand / GetAction's command tail (QS/controllers/balance_controller/
+ * qr_torque_stance_leg_controller.cpp:89-172, 174-477, 503-541) and qrLocomotionController::GetAction's merge (qr_locomotion_controller.cpp:
+ * 128-147).  With these a force-balance tick is queued entirely on the context's stream: ground, estimator, gait, swing update, stance
+ * tick, swing action -- no host copy in between.
+ * qrgpu_stance_update_batch reads arrays the device already holds:
+ *   d_est_in     quat_wxyz rows 6-9, rpyRate 10-12 (the tick also takes the motor angles, rows 17-28, for the J^T f torque map)
+ *   d_est_out    baseVelocityInBaseFrame 6-8, footPositionsInBaseFrame 12-23, basePosition 36-38, heightInControlFrame 39
+ *   d_ground_out controlFrameRPY 6-8, controlFrameOrientation 9-12, groundRMat 13-21, baseRInControlFrame 22-30
+ *   d_rpy [3][n] GetBaseRollPitchYaw, as qrgpu_pack_state_batch takes it
+ *   d_gait_out   WALK: the [QRGPU_WALK_OUT_ROWS][n] output of qrgpu_walk_gait_update_batch (normalizedPhase 4-7, desiredLegState 8-11,
+ *                detectedLegState 20-23, moveBasePhase 28, contacts 29-32, fMinRatio 33-36, fMaxRatio 37-40: the walk branch of UpdateFRatio
+ *                is computed there); other modes: the [24][n] output of qrgpu_gait_update_batch (normalizedPhase 4-7, desiredLegState 8-11,
+ *                legState 12-15)
+ *   d_gait_state the open-loop generator's state (allowSwitchLegState, rows 20-23): needed by POSITION and ADVANCED_TROT, else may be NULL
+ *   d_stance_cmd [QRGPU_STANCE_CMD_ROWS][n], the one input that comes from the host, and changes only when the operator's command or the walk
+ *                pose plan does: row 0 stateDes(2); 1-3 stateDes 6..8; 4-6 stateDes 9..11; 7-12 the pose planner's segment source (the pose at
+ *                its last Update / ResetBasePose); 13-18 poseDest; 19-24 twist; 25-27 footholdPlanner->GetDesiredComPose().tail(3)
+ *   d_stance_state [QRGPU_STANCE_STATE_FLOATS][n] the controller's memory: row 0 heightInControlFrame, which est_out reports as NaN while no
+ *                foot is in stance and the reference then keeps; reset != 0 starts it at desc->body_height (qr_robot_pose_estimator.cpp:50)
+ * current_time and desc->pose_reset_time give the WALK pose phase while robot_stop (GetIntermediateBasePose(currentTime)); otherwise that
+ * phase is moveBasePhase.  robot_stop (:95-102) sets every contact, ratios 0.01 / 10 and N = 4 in every mode, over what the walk kernel wrote.
+ * In POSITION mode qrComAdjuster::Update runs in the kernel (erf in double); in ADVANCED_TROT the reference never calls it, so
+ * comPosInBaseFrame is the zero vector of its Reset.  Dead branches of the reference that are not built: qr_stance_kernel.hip's header.
+ * Outputs, each may be NULL:
+ *   d_vmc_in [37][n] complete: foot positions, desiredAcc, contacts and Rcb / g / surfaceNormal as the overload the mode selects builds
+ *                them -- control frame (qr_qp_torque_optimizer.cpp:202-221): identity, (0, 0, 9.8), e_z on PLANE / PLUM_PILES, else
+ *                groundRMat^T baseRMat, groundRMat^T g, (-sin pitch, 0, cos pitch); world frame (:319-336): baseRMat, (0, 0, 9.8), e_z
+ *   d_ratio [8][n]  fMinRatio[4], fMaxRatio[4]
+ *   d_stance_out [QRGPU_STANCE_OUT_ROWS][n]: stateCur[12], stateDes[12], ddqDes[6], N (row 30), moveBasePhase (31), computeForceInWorldFrame
+ *                (32: 1 = the tick needs qrgpu_vmc_force_world_batch; WALK always, ADVANCED_TROT with desc->force_in_world)
+ * qrgpu_stance_command_batch writes d_motor_cmd [QRGPU_MOTOR_CMD_ROWS][n] = p[12], Kp[12], d[12], Kd[12], tua[12] (qrMotorCommand, motor-major
+ * inside each field) from d_tau [12][n] (the QP's J^T f): {0, 0, 0, 0, tau}; in WALK {0, 0.0 kp, 0, 0.5 kd, tau} for a leg in contact (rows 18-21
+ * of d_vmc_in; the reference's 0.0 * legJointq is written as 0), {0, 0, 0, 0.0 kd, tau} when (N < 4 && moveBasePhase < 0.7) || robot_stop
+ * (rows 30, 31 of d_stance_out), else all zero.  d_swing_q [24][n] (joint angle and velocity targets) and d_swing_flag [4][n] -- rows 24-47
+ * and 48-51 of qrgpu_swing_action_batch's output for POSITION / WALK, the caller's own arrays otherwise; both NULL: no swing command --
+ * make a flagged leg's motors {q, kp, qd, kd, 0} (qr_swing_leg_controller.cpp:456-458).  d_vmc_in / d_stance_out are read in WALK only.
+ * qrgpu_stance_tick_batch: update, the QP overload the mode selects (d_type_id as in the VMC calls; joint angles from d_est_in), command:
+ * three launches on the context's stream, results those of the three calls made one by one, bit for bit.  It needs d_vmc_in, d_force,
+ * d_tau, d_motor_cmd, d_ratio for the world-frame overload and d_stance_out in WALK.
+ * QRGPU_ERR_BAD_ARG (outputs untouched): a mode or terrain outside the enums, a NULL required array, n < 1 or n > max_batch. */
+#define QRGPU_STANCE_CMD_ROWS 28
+#define QRGPU_STANCE_STATE_FLOATS 1
+#define QRGPU_STANCE_OUT_ROWS 33
+#define QRGPU_MOTOR_CMD_ROWS 60
+typedef struct {
+    int   mode, terrain;              /* LocomotionMode, TerrainType (as qrgpu_swing_mode_desc) */
+    int   force_in_world;             /* user_parameters.yaml computeForceInWorldFrame; read by ADVANCED_TROT only (VELOCITY and POSITION
+                                         clear it, WALK sets it) */
+    float kp[6], kd[6], max_ddq[6], min_ddq[6];   /* stance_leg_controller.yaml stance_leg_params of the mode */
+    float desired_height, desired_speed[3], desired_twisting_speed;   /* user_parameters.yaml: 0.27, (0, 0, 0), 0 */
+    float body_height;                /* robot->bodyHeight: 0.28 */
+    float pose_reset_time;            /* qrPosePlanner::resetTime (ResetBasePose) */
+    float motor_kp[12], motor_kd[12]; /* robot->GetMotorKps / GetMotorKdp: (100, 100, 100) / (1, 2, 2) per leg */
+} qrgpu_stance_desc;
+/* config/a1_sim for the mode; terrain as qrgpu_swing_mode_desc_default, force_in_world 1 (user_parameters.yaml:40) */
+void qrgpu_stance_desc_default(qrgpu_stance_desc *d, int mode);
+int qrgpu_stance_update_batch(qrgpu_ctx *ctx, int n, const qrgpu_stance_desc *desc, float current_time, int robot_stop, int reset,
+                              const float *d_est_in, const float *d_est_out, const float *d_ground_out, const float *d_rpy, const float *d_gait_out,
+                              const float *d_gait_state, const float *d_stance_cmd, float *d_stance_state, float *d_vmc_in, float *d_ratio,
+                              float *d_stance_out);
+int qrgpu_stance_command_batch(qrgpu_ctx *ctx, int n, const qrgpu_stance_desc *desc, int robot_stop, const float *d_vmc_in,
+                               const float *d_stance_out, const float *d_tau, const float *d_swing_q, const float *d_swing_flag, float *d_motor_cmd);
+int qrgpu_stance_tick_batch(qrgpu_ctx *ctx, int n, const qrgpu_stance_desc *desc, float current_time, int robot_stop, int reset,
+                            const int *d_type_id, const float *d_est_in, const float *d_est_out, const float *d_ground_out, const float *d_rpy,
+                            const float *d_gait_out, const float *d_gait_state, const float *d_stance_cmd, float *d_stance_state, float *d_vmc_in,
+                            float *d_ratio, float *d_stance_out, float *d_force, float *d_tau, int *d_status, const float *d_swing_q,
+                            const float *d_swing_flag, float *d_motor_cmd);
 
 /* The tick's state arrays from the estimator's inputs and outputs: what SolveDenseMPC (qr_mpc_stance_leg_controller.cpp:385-399:
  * pos, baseVInWorldFrame, quat, baseWInWorldFrame, foot2ComInWorldFrame = baseRMat (footPositionsInBaseFrame - comOffset), rpy) and

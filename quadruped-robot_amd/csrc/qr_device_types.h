@@ -198,6 +198,14 @@ struct SwingModeDesc {
     float gap_distance[QR_SWING_MAX_GAPS], gap_width;
 };
 
+// Force-balance stance controller: front-end and motor commands (qrgpu_stance_desc)
+struct StanceDesc {
+    int mode, terrain, force_in_world;
+    float kp[6], kd[6], max_ddq[6], min_ddq[6];
+    float desired_height, desired_speed[3], desired_twisting_speed, body_height, pose_reset_time;
+    float motor_kp[12], motor_kd[12];
+};
+
 // Walk gait generator parameters after the constructor's bookkeeping (qrgpu_walk_gait_desc -> qrgpu_api.hip)
 struct WalkDesc {
     float duty_factor[4], initial_leg_phase[4], full[4];

@@ -26,34 +26,6 @@ constexpr int SS_LOCAL = 0, SS_GLOBAL = 12, SS_FH = 24, SS_SRC = 36, SS_TGT = 48
 constexpr int SW_NO_TRAJ = 1, SW_PHASE = 2, SW_PLAN_EXIT = 4, SW_PLAN_EMPTY = 8, SW_PLAN_FULL = 16;
 constexpr float MAXIMUM_STEP = 0.001f;                                       // config/qr_config.h:43
 
-// Eigen::Quaternion<float>::toRotationMatrix (w, x, y, z)
-__device__ __forceinline__ void quat_to_rot(float w, float x, float y, float z, float R[3][3])
-{
-#pragma clang fp contract(off)
-    const float tx = 2.f * x, ty = 2.f * y, tz = 2.f * z;
-    const float twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x, tyy = ty * y, tyz = tz * y, tzz = tz * z;
-    R[0][0] = 1.f - (tyy + tzz); R[0][1] = txy - twz; R[0][2] = txz + twy;
-    R[1][0] = txy + twz; R[1][1] = 1.f - (txx + tzz); R[1][2] = tyz - twx;
-    R[2][0] = txz - twy; R[2][1] = tyz + twx; R[2][2] = 1.f - (txx + tyy);
-}
-
-__device__ __forceinline__ float dot3(const float a[3], const float b0, const float b1, const float b2)
-{
-#pragma clang fp contract(off)
-    return (a[0] * b0 + a[1] * b1) + a[2] * b2;
-}
-
-// robotics::math::RigidTransform(t, q, p) = q.inverse() p + q.inverse() (-t)  (include/quadruped/utils/qr_se3.h:459-466)
-__device__ __forceinline__ void rigid_transform(const float q[4], const float t[3], const float p[3], float out[3])
-{
-#pragma clang fp contract(off)
-    const float n2 = (q[0] * q[0] + q[1] * q[1]) + (q[2] * q[2] + q[3] * q[3]);
-    float Ri[3][3];
-    quat_to_rot(q[0] / n2, -q[1] / n2, -q[2] / n2, -q[3] / n2, Ri);
-#pragma unroll
-    for (int r = 0; r < 3; ++r) out[r] = dot3(Ri[r], p[0], p[1], p[2]) + dot3(Ri[r], -t[0], -t[1], -t[2]);
-}
-
 // the stepper's fixed knot vector, (float)(k / 6) as the constructor writes it (:44-47)
 __device__ __forceinline__ float knot_at(int k)
 {
@@ -307,12 +279,7 @@ __global__ void __launch_bounds__(64) qr_swing_update_kernel(int n, SwingModeDes
         }
     }
     float Rb[3][3];                                                           // stateDataFlow.baseRMat
-    {
-        const float e0 = q[0], e1 = q[1], e2 = q[2], e3 = q[3];
-        Rb[0][0] = 1 - 2 * (e2 * e2 + e3 * e3); Rb[0][1] = 2 * (e1 * e2 - e0 * e3); Rb[0][2] = 2 * (e1 * e3 + e0 * e2);
-        Rb[1][0] = 2 * (e1 * e2 + e0 * e3); Rb[1][1] = 1 - 2 * (e1 * e1 + e3 * e3); Rb[1][2] = 2 * (e2 * e3 - e0 * e1);
-        Rb[2][0] = 2 * (e1 * e3 - e0 * e2); Rb[2][1] = 2 * (e2 * e3 + e0 * e1); Rb[2][2] = 1 - 2 * (e1 * e1 + e2 * e2);
-    }
+    base_rmat(q, Rb);
     int built = (int)ST(SS_BUILT);
     for (int l = 0; l < 4; ++l) {
         const int nst = (int)g_gait_out[(size_t)(8 + l) * N + i], cur = (int)g_gait_out[(size_t)(16 + l) * N + i];

@@ -84,6 +84,126 @@ __device__ __forceinline__ void leg_jacobian_column(int j, float t0, float t1, f
     }
 }
 
+// ---- rotation helpers shared by the swing-mode and stance kernels (robotics::math, include/quadruped/utils/qr_se3.h); fp32 with the
+// reference's float / double mix, contraction off.  3x3 matrices are row-major R[row][col]; a product's entry is (a0 b0 + a1 b1) + a2 b2.
+
+// Eigen::Quaternion<float>::toRotationMatrix (w, x, y, z)
+__device__ __forceinline__ void quat_to_rot(float w, float x, float y, float z, float R[3][3])
+{
+#pragma clang fp contract(off)
+    const float tx = 2.f * x, ty = 2.f * y, tz = 2.f * z;
+    const float twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x, tyy = ty * y, tyz = tz * y, tzz = tz * z;
+    R[0][0] = 1.f - (tyy + tzz); R[0][1] = txy - twz; R[0][2] = txz + twy;
+    R[1][0] = txy + twz; R[1][1] = 1.f - (txx + tzz); R[1][2] = tyz - twx;
+    R[2][0] = txz - twy; R[2][1] = tyz + twx; R[2][2] = 1.f - (txx + tyy);
+}
+
+__device__ __forceinline__ float dot3(const float a[3], const float b0, const float b1, const float b2)
+{
+#pragma clang fp contract(off)
+    return (a[0] * b0 + a[1] * b1) + a[2] * b2;
+}
+
+// robotics::math::RigidTransform(t, q, p) = q.inverse() p + q.inverse() (-t)  (include/quadruped/utils/qr_se3.h:459-466)
+__device__ __forceinline__ void rigid_transform(const float q[4], const float t[3], const float p[3], float out[3])
+{
+#pragma clang fp contract(off)
+    const float n2 = (q[0] * q[0] + q[1] * q[1]) + (q[2] * q[2] + q[3] * q[3]);
+    float Ri[3][3];
+    quat_to_rot(q[0] / n2, -q[1] / n2, -q[2] / n2, -q[3] / n2, Ri);
+#pragma unroll
+    for (int r = 0; r < 3; ++r) out[r] = dot3(Ri[r], p[0], p[1], p[2]) + dot3(Ri[r], -t[0], -t[1], -t[2]);
+}
+
+// stateDataFlow.baseRMat = quaternionToRotationMatrix(q)^T (qr_se3.h:186-203, qr_robot.cpp:70): base -> world
+__device__ __forceinline__ void base_rmat(const float q[4], float R[3][3])
+{
+#pragma clang fp contract(off)
+    const float e0 = q[0], e1 = q[1], e2 = q[2], e3 = q[3];
+    R[0][0] = 1 - 2 * (e2 * e2 + e3 * e3); R[0][1] = 2 * (e1 * e2 - e0 * e3); R[0][2] = 2 * (e1 * e3 + e0 * e2);
+    R[1][0] = 2 * (e1 * e2 + e0 * e3); R[1][1] = 1 - 2 * (e1 * e1 + e3 * e3); R[1][2] = 2 * (e2 * e3 - e0 * e1);
+    R[2][0] = 2 * (e1 * e3 - e0 * e2); R[2][1] = 2 * (e2 * e3 + e0 * e1); R[2][2] = 1 - 2 * (e1 * e1 + e2 * e2);
+}
+
+// robotics::math::invertRigidTransform(t, q, p) = q p + t (qr_se3.h:442-449; Eigen's Quaternion::toRotationMatrix)
+__device__ __forceinline__ void invert_rigid_transform(const float q[4], const float t[3], const float p[3], float out[3])
+{
+#pragma clang fp contract(off)
+    float R[3][3];
+    quat_to_rot(q[0], q[1], q[2], q[3], R);
+#pragma unroll
+    for (int r = 0; r < 3; ++r) out[r] = dot3(R[r], p[0], p[1], p[2]) + t[r];
+}
+
+// TransformVecByQuat(quat, r_b) = (2 q0 q0 - 1) r_b + 2 q0 [q_]x r_b + 2 q_ (q_ . r_b) (qr_se3.h:473-479)
+__device__ __forceinline__ void transform_vec_by_quat(const float q[4], const float rb[3], float out[3])
+{
+#pragma clang fp contract(off)
+    const float q0 = q[0], v0 = q[1], v1 = q[2], v2 = q[3];
+    const float a = 2 * q0 * q0 - 1, s = 2 * q0;
+    const float M[3][3] = {{s * 0.f, s * -v2, s * v1}, {s * v2, s * 0.f, s * -v0}, {s * -v1, s * v0, s * 0.f}};
+    const float d = (v0 * rb[0] + v1 * rb[1]) + v2 * rb[2];
+    const float w[3] = {2 * v0, 2 * v1, 2 * v2};
+#pragma unroll
+    for (int r = 0; r < 3; ++r) out[r] = (a * rb[r] + dot3(M[r], rb[0], rb[1], rb[2])) + w[r] * d;
+}
+
+// quatInverse (qr_se3.h:307-313)
+__device__ __forceinline__ void quat_inverse(const float q[4], float out[4])
+{
+#pragma clang fp contract(off)
+    const float n2 = (q[0] * q[0] + q[1] * q[1]) + (q[2] * q[2] + q[3] * q[3]);
+    out[0] = q[0] / n2; out[1] = -q[1] / n2; out[2] = -q[2] / n2; out[3] = -q[3] / n2;
+}
+
+__device__ __forceinline__ void mat3_mul(const float A[3][3], const float B[3][3], float C[3][3])
+{
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) C[r][c] = (A[r][0] * B[0][c] + A[r][1] * B[1][c]) + A[r][2] * B[2][c];
+}
+
+// rpyToRotMat = Rx(roll) Ry(pitch) Rz(yaw) of coordinateRotation's coordinate-transform matrices (qr_se3.h:71-89, 108-116)
+__device__ __forceinline__ void rpy_to_rotmat(const float rpy[3], float M[3][3])
+{
+#pragma clang fp contract(off)
+    const float sr = sinf(rpy[0]), cr = cosf(rpy[0]), sp = sinf(rpy[1]), cp = cosf(rpy[1]), sy = sinf(rpy[2]), cy = cosf(rpy[2]);
+    const float X[3][3] = {{1.f, 0.f, 0.f}, {0.f, cr, sr}, {0.f, -sr, cr}};
+    const float Y[3][3] = {{cp, 0.f, -sp}, {0.f, 1.f, 0.f}, {sp, 0.f, cp}};
+    const float Z[3][3] = {{cy, sy, 0.f}, {-sy, cy, 0.f}, {0.f, 0.f, 1.f}};
+    float XY[3][3];
+    mat3_mul(X, Y, XY);
+    mat3_mul(XY, Z, M);
+}
+
+// rotationMatrixToRPY(R) = quatToRPY(rotationMatrixToQuaternion(R)) (qr_se3.h:145-178, 209-223, 255-262), given r = R^T: the matrix
+// rotationMatrixToQuaternion works on after its own transpose
+__device__ __forceinline__ void rotmat_t_to_rpy(const float r[3][3], float rpy[3])
+{
+#pragma clang fp contract(off)
+    float q0, q1, q2, q3;
+    const float tr = (r[0][0] + r[1][1]) + r[2][2];
+    if ((double)tr > 0.0) {
+        const float S = (float)(sqrt((double)tr + 1.0) * 2.0);
+        q0 = (float)(0.25 * (double)S); q1 = (r[2][1] - r[1][2]) / S; q2 = (r[0][2] - r[2][0]) / S; q3 = (r[1][0] - r[0][1]) / S;
+    } else if (r[0][0] > r[1][1] && r[0][0] > r[2][2]) {
+        const float S = (float)(sqrt(1.0 + (double)r[0][0] - (double)r[1][1] - (double)r[2][2]) * 2.0);
+        q0 = (r[2][1] - r[1][2]) / S; q1 = (float)(0.25 * (double)S); q2 = (r[0][1] + r[1][0]) / S; q3 = (r[0][2] + r[2][0]) / S;
+    } else if (r[1][1] > r[2][2]) {
+        const float S = (float)(sqrt(1.0 + (double)r[1][1] - (double)r[0][0] - (double)r[2][2]) * 2.0);
+        q0 = (r[0][2] - r[2][0]) / S; q1 = (r[0][1] + r[1][0]) / S; q2 = (float)(0.25 * (double)S); q3 = (r[1][2] + r[2][1]) / S;
+    } else {
+        const float S = (float)(sqrt(1.0 + (double)r[2][2] - (double)r[0][0] - (double)r[1][1]) * 2.0);
+        q0 = (r[1][0] - r[0][1]) / S; q1 = (r[0][2] + r[2][0]) / S; q2 = (r[1][2] + r[2][1]) / S; q3 = (float)(0.25 * (double)S);
+    }
+    const float as = (float)fmin(-2. * (double)(q1 * q3 - q0 * q2), .99999);
+    rpy[2] = atan2f(2 * (q1 * q2 + q0 * q3), ((q0 * q0 + q1 * q1) - q2 * q2) - q3 * q3);
+    rpy[1] = asinf(as);
+    rpy[0] = atan2f(2 * (q2 * q3 + q0 * q1), ((q0 * q0 - q1 * q1) - q2 * q2) + q3 * q3);
+}
+
 // ---- swing-leg helpers shared by the swing kernels (qr_estimator_kernel.hip, qr_swing_modes_kernel.hip); fp32, contraction off -------
 
 // SwingFootTrajectory::GenerateTrajectoryPoint's phase warp (phaseModule = true), qr_foot_trajectory_generator.cpp:328-335

@@ -27,6 +27,11 @@ __global__ void qr_swing_update_kernel(int n, SwingModeDesc M, int reset, int st
                                        float *g_st, float *g_swing_in, float *g_swing_vel_in, float *g_fe_in, int *g_flags);
 __global__ void qr_swing_action_kernel(int n, SwingModeDesc M, EstimatorDesc D, int stop, const float *g_est_in, const float *g_est_out, const float *g_gait_out,
                                        const float *g_gait_state, float *g_st, float *g_out, int *g_flags);
+__global__ void qr_stance_update_kernel(int n, StanceDesc S, float current_time, int stop, int reset, const float *g_est_in, const float *g_est_out,
+                                        const float *g_ground, const float *g_rpy, const float *g_gait_out, const float *g_gait_state, const float *g_cmd,
+                                        float *g_st, float *g_vmc_in, float *g_ratio, float *g_out);
+__global__ void qr_stance_command_kernel(int n, StanceDesc S, int stop, const float *g_vmc_in, const float *g_stance_out, const float *g_tau,
+                                         const float *g_swing_q, const float *g_swing_flag, float *g_cmd);
 __global__ void qr_pack_state_kernel(int n, float c0, float c1, float c2, const float *g_in, const float *g_est, const float *g_rpy, float *g_mpc, float *g_fb);
 __global__ void qr_estimator_kernel(int n, EstimatorDesc D, const float *g_in, const unsigned *g_tick, double *st, float *g_out);
 __global__ void qr_vmc_kernel(VmcLaunch P, const int *type_id, const float *g_in, const float *g_q, float *g_force, float *g_tau, int *g_status);
@@ -769,6 +774,113 @@ int qrgpu_vmc_force_world_batch(qrgpu_ctx *c, int n, const int *d_type_id, const
 {
     if (!d_ratio) return QRGPU_ERR_BAD_ARG;
     return launch_vmc(c, n, d_type_id, d_vmc_in, d_ratio, d_q, d_force, d_tau, d_status);
+}
+
+void qrgpu_stance_desc_default(qrgpu_stance_desc *d, int mode)
+{   // config/a1_sim/stance_leg_controller.yaml (stance_leg_params of the mode), config/user_parameters.yaml:19-21,40, config/a1_sim/a1_sim.yaml:14,62-67
+    // (qr_robot_a1_sim.cpp:104-105), terrain as qrgpu_swing_mode_desc_default
+    if (!d) return;
+    memset(d, 0, sizeof(*d));
+    d->mode = mode;
+    d->terrain = mode == QRGPU_MODE_POSITION ? 1 : mode == QRGPU_MODE_ADVANCED_TROT ? 2 : 3;
+    d->force_in_world = 1;
+    static const float KP[4][6] = {{100.f, 100.f, 100.f, 200.f, 200.f, 0.f}, {100.f, 200.f, 200.f, 100.f, 100.f, 200.f}, {100.f, 200.f, 100.f, 100.f, 100.f, 200.f},
+                                   {100.f, 100.f, 100.f, 200.f, 200.f, 100.f}};
+    static const float KD[4][6] = {{20.f, 20.f, 10.f, 20.f, 20.f, 25.f}, {40.f, 30.f, 10.f, 10.f, 10.f, 30.f}, {40.f, 30.f, 10.f, 10.f, 10.f, 30.f},
+                                   {30.f, 20.f, 10.f, 20.f, 20.f, 25.f}};
+    const int m = mode >= 0 && mode <= 3 ? mode : 0;
+    for (int k = 0; k < 6; ++k) {
+        d->kp[k] = KP[m][k]; d->kd[k] = KD[m][k];
+        d->max_ddq[k] = (m == 3 || k < 3) ? 10.f : 20.f;
+        d->min_ddq[k] = -d->max_ddq[k];
+    }
+    d->desired_height = 0.27f;
+    d->body_height = 0.28f;
+    for (int j = 0; j < 12; ++j) { d->motor_kp[j] = 100.f; d->motor_kd[j] = (j % 3 == 0) ? 1.f : 2.f; }
+}
+
+static bool stance_desc(const qrgpu_stance_desc *d, StanceDesc &S)
+{
+    if (!d || d->mode < 0 || d->mode > 3 || d->terrain < 0 || d->terrain > 4) return false;
+    memset(&S, 0, sizeof(S));
+    S.mode = d->mode; S.terrain = d->terrain; S.force_in_world = d->force_in_world ? 1 : 0;
+    memcpy(S.kp, d->kp, sizeof(S.kp)); memcpy(S.kd, d->kd, sizeof(S.kd));
+    memcpy(S.max_ddq, d->max_ddq, sizeof(S.max_ddq)); memcpy(S.min_ddq, d->min_ddq, sizeof(S.min_ddq));
+    S.desired_height = d->desired_height; memcpy(S.desired_speed, d->desired_speed, sizeof(S.desired_speed));
+    S.desired_twisting_speed = d->desired_twisting_speed; S.body_height = d->body_height; S.pose_reset_time = d->pose_reset_time;
+    memcpy(S.motor_kp, d->motor_kp, sizeof(S.motor_kp)); memcpy(S.motor_kd, d->motor_kd, sizeof(S.motor_kd));
+    return true;
+}
+
+static bool stance_world(const StanceDesc &S) { return S.mode == QRGPU_MODE_WALK || (S.mode == QRGPU_MODE_ADVANCED_TROT && S.force_in_world); }
+
+static int stance_update_check(const qrgpu_ctx *c, int n, const qrgpu_stance_desc *desc, StanceDesc &S, const float *d_est_in, const float *d_est_out,
+                               const float *d_ground_out, const float *d_rpy, const float *d_gait_out, const float *d_gait_state, const float *d_stance_cmd,
+                               const float *d_stance_state)
+{
+    if (!c || n <= 0 || n > c->max_batch || !stance_desc(desc, S)) return QRGPU_ERR_BAD_ARG;
+    if (!d_est_in || !d_est_out || !d_ground_out || !d_rpy || !d_gait_out || !d_stance_cmd || !d_stance_state) return QRGPU_ERR_BAD_ARG;
+    if ((S.mode == QRGPU_MODE_POSITION || S.mode == QRGPU_MODE_ADVANCED_TROT) && !d_gait_state) return QRGPU_ERR_BAD_ARG;   // allowSwitchLegState
+    return QRGPU_OK;
+}
+
+static int stance_command_check(const qrgpu_ctx *c, int n, const StanceDesc &S, const float *d_vmc_in, const float *d_stance_out, const float *d_tau,
+                                const float *d_swing_q, const float *d_swing_flag, const float *d_motor_cmd)
+{
+    if (!c || n <= 0 || n > c->max_batch || !d_tau || !d_motor_cmd) return QRGPU_ERR_BAD_ARG;
+    if (S.mode == QRGPU_MODE_WALK && (!d_vmc_in || !d_stance_out)) return QRGPU_ERR_BAD_ARG;             // contacts, N, moveBasePhase
+    if ((d_swing_q == nullptr) != (d_swing_flag == nullptr)) return QRGPU_ERR_BAD_ARG;                   // both or neither
+    return QRGPU_OK;
+}
+
+int qrgpu_stance_update_batch(qrgpu_ctx *c, int n, const qrgpu_stance_desc *desc, float current_time, int robot_stop, int reset, const float *d_est_in,
+                              const float *d_est_out, const float *d_ground_out, const float *d_rpy, const float *d_gait_out, const float *d_gait_state,
+                              const float *d_stance_cmd, float *d_stance_state, float *d_vmc_in, float *d_ratio, float *d_stance_out)
+{
+    StanceDesc S;
+    const int e = stance_update_check(c, n, desc, S, d_est_in, d_est_out, d_ground_out, d_rpy, d_gait_out, d_gait_state, d_stance_cmd, d_stance_state);
+    if (e != QRGPU_OK) return e;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipLaunchKernelGGL(qr_stance_update_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, n, S, current_time, robot_stop ? 1 : 0, reset ? 1 : 0, d_est_in,
+                       d_est_out, d_ground_out, d_rpy, d_gait_out, d_gait_state, d_stance_cmd, d_stance_state, d_vmc_in, d_ratio, d_stance_out);
+    HIPCHK(c, hipGetLastError());
+    return QRGPU_OK;
+}
+
+int qrgpu_stance_command_batch(qrgpu_ctx *c, int n, const qrgpu_stance_desc *desc, int robot_stop, const float *d_vmc_in, const float *d_stance_out,
+                               const float *d_tau, const float *d_swing_q, const float *d_swing_flag, float *d_motor_cmd)
+{
+    StanceDesc S;
+    if (!stance_desc(desc, S)) return QRGPU_ERR_BAD_ARG;
+    const int e = stance_command_check(c, n, S, d_vmc_in, d_stance_out, d_tau, d_swing_q, d_swing_flag, d_motor_cmd);
+    if (e != QRGPU_OK) return e;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipLaunchKernelGGL(qr_stance_command_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, n, S, robot_stop ? 1 : 0, d_vmc_in, d_stance_out, d_tau, d_swing_q,
+                       d_swing_flag, d_motor_cmd);
+    HIPCHK(c, hipGetLastError());
+    return QRGPU_OK;
+}
+
+int qrgpu_stance_tick_batch(qrgpu_ctx *c, int n, const qrgpu_stance_desc *desc, float current_time, int robot_stop, int reset, const int *d_type_id,
+                            const float *d_est_in, const float *d_est_out, const float *d_ground_out, const float *d_rpy, const float *d_gait_out,
+                            const float *d_gait_state, const float *d_stance_cmd, float *d_stance_state, float *d_vmc_in, float *d_ratio, float *d_stance_out,
+                            float *d_force, float *d_tau, int *d_status, const float *d_swing_q, const float *d_swing_flag, float *d_motor_cmd)
+{
+    StanceDesc S;
+    int e = stance_update_check(c, n, desc, S, d_est_in, d_est_out, d_ground_out, d_rpy, d_gait_out, d_gait_state, d_stance_cmd, d_stance_state);
+    if (e != QRGPU_OK) return e;
+    const bool world = stance_world(S);
+    if (!d_vmc_in || !d_force || (world && !d_ratio)) return QRGPU_ERR_BAD_ARG;
+    e = stance_command_check(c, n, S, d_vmc_in, d_stance_out, d_tau, d_swing_q, d_swing_flag, d_motor_cmd);
+    if (e != QRGPU_OK) return e;
+    if (!(d_type_id ? ready_mask(c->vmc_ready) != 0 : c->vmc_ready[0])) return QRGPU_ERR_NOT_SETUP;
+    e = qrgpu_stance_update_batch(c, n, desc, current_time, robot_stop, reset, d_est_in, d_est_out, d_ground_out, d_rpy, d_gait_out, d_gait_state, d_stance_cmd,
+                                  d_stance_state, d_vmc_in, d_ratio, d_stance_out);
+    if (e != QRGPU_OK) return e;
+    const float *d_q = d_est_in + (size_t)17 * n;                                                       // motor angles: rows 17-28 of est_in
+    e = launch_vmc(c, n, d_type_id, d_vmc_in, world ? d_ratio : nullptr, d_q, d_force, d_tau, d_status);
+    if (e != QRGPU_OK) return e;
+    return qrgpu_stance_command_batch(c, n, desc, robot_stop, d_vmc_in, d_stance_out, d_tau, d_swing_q, d_swing_flag, d_motor_cmd);
 }
 
 int qrgpu_mpc_frontend_batch(qrgpu_ctx *c, int n, int num_horizon_l, float dt_ctrl, float dt_mpc, const float *d_fe_in, float *d_fe_state,

@@ -112,6 +112,31 @@ def swing_mode_desc(mode, terrain=None, is_sim=None, foothold_delta=None, gaps=N
     return d
 
 
+STANCE_CMD_ROWS, STANCE_STATE_FLOATS, STANCE_OUT_ROWS, MOTOR_CMD_ROWS = 28, 1, 33, 60
+
+
+class stance_desc_struct(C.Structure):
+    _fields_ = [("mode", C.c_int), ("terrain", C.c_int), ("force_in_world", C.c_int), ("kp", C.c_float * 6), ("kd", C.c_float * 6),
+                ("max_ddq", C.c_float * 6), ("min_ddq", C.c_float * 6), ("desired_height", C.c_float), ("desired_speed", C.c_float * 3),
+                ("desired_twisting_speed", C.c_float), ("body_height", C.c_float), ("pose_reset_time", C.c_float),
+                ("motor_kp", C.c_float * 12), ("motor_kd", C.c_float * 12)]
+
+
+def stance_desc(mode, terrain=None, force_in_world=None, **fields):
+    """qrgpu_stance_desc: the library's defaults for `mode` (config/a1_sim), with any field overridden (scalars or sequences by name)."""
+    d = stance_desc_struct()
+    load_library().qrgpu_stance_desc_default(C.byref(d), int(mode))
+    if terrain is not None: d.terrain = int(terrain)
+    if force_in_world is not None: d.force_in_world = int(bool(force_in_world))
+    for name, v in fields.items():
+        cur = getattr(d, name)
+        if hasattr(cur, "__len__"):
+            for k, x in enumerate(v): cur[k] = float(x)
+        else:
+            setattr(d, name, float(v))
+    return d
+
+
 EPILOGUE_HIP_COMP, EPILOGUE_CLIP = 1, 2
 COMM_ID_BYTES = 128
 
@@ -141,7 +166,8 @@ EXPORTS = ["qrgpu_model_desc_default", "qrgpu_create", "qrgpu_destroy", "qrgpu_s
            "qrgpu_allgather_tau", "qrgpu_allgather_tau_of_tick", "qrgpu_allgather_fence", "qrgpu_allgather_wait", "qrgpu_comm_sync", "qrgpu_set_warm_start", "qrgpu_set_planned_list",
            "qrgpu_enable_flop_count", "qrgpu_mpc_flop_counts", "qrgpu_mpc_set_hessian_mode", "qrgpu_wbc_inspect_batch", "qrgpu_host_alloc", "qrgpu_host_free",
            "qrgpu_memcpy_async", "qrgpu_memset_async", "qrgpu_mark", "qrgpu_mark_elapsed_ms", "qrgpu_set_tick_pipeline", "qrgpu_set_tick_overlap",
-           "qrgpu_tick_fence", "qrgpu_tick_overlap_stats", "qrgpu_swing_mode_desc_default", "qrgpu_swing_update_batch", "qrgpu_swing_action_batch"]
+           "qrgpu_tick_fence", "qrgpu_tick_overlap_stats", "qrgpu_swing_mode_desc_default", "qrgpu_swing_update_batch", "qrgpu_swing_action_batch",
+           "qrgpu_stance_desc_default", "qrgpu_stance_update_batch", "qrgpu_stance_command_batch", "qrgpu_stance_tick_batch"]
 
 
 def load_library():
@@ -212,6 +238,10 @@ def load_library():
     lib.qrgpu_swing_mode_desc_default.argtypes = [C.POINTER(swing_mode_desc_struct), ip]; lib.qrgpu_swing_mode_desc_default.restype = None
     lib.qrgpu_swing_update_batch.argtypes = [vp, ip, C.POINTER(swing_mode_desc_struct), ip, ip] + [vp] * 9
     lib.qrgpu_swing_action_batch.argtypes = [vp, ip, C.POINTER(swing_mode_desc_struct), C.POINTER(estimator_desc_struct), ip] + [vp] * 7
+    lib.qrgpu_stance_desc_default.argtypes = [C.POINTER(stance_desc_struct), ip]; lib.qrgpu_stance_desc_default.restype = None
+    lib.qrgpu_stance_update_batch.argtypes = [vp, ip, C.POINTER(stance_desc_struct), C.c_float, ip, ip] + [vp] * 11
+    lib.qrgpu_stance_command_batch.argtypes = [vp, ip, C.POINTER(stance_desc_struct), ip] + [vp] * 6
+    lib.qrgpu_stance_tick_batch.argtypes = [vp, ip, C.POINTER(stance_desc_struct), C.c_float, ip, ip] + [vp] * 18
     lib.qrgpu_vmc_force1.argtypes = [vp, ip, fp, fp, fp, fp, C.POINTER(ip)]
     lib.qrgpu_vmc_force_world1.argtypes = [vp, ip, fp, fp, fp, fp, fp, C.POINTER(ip)]
     lib.qrgpu_mpc_frontend_batch.argtypes = [vp, ip, ip, C.c_float, C.c_float] + [vp] * 6
@@ -574,6 +604,29 @@ class Context:
         for i in range(12): d.hip_offset[i] = float(cfg20[7 + i])
         self._chk(self._lib.qrgpu_swing_action_batch(self._h, n, C.byref(desc), C.byref(d), int(bool(stop)), _dp(est_in), _dp(est_out), _dp(gait_out),
                                                      _dp(gait_state), _dp(swing_state), _dp(out), _dp(swing_flags)))
+
+    def stance_update_batch(self, n, desc, est_in, est_out, ground_out, rpy, gait_out, stance_cmd, stance_state, gait_state=None, vmc_in=None,
+                            ratio=None, stance_out=None, current_time=0.0, stop=False, reset=False):
+        """TorqueStanceLegController::UpdateFRatio + UpdateDesCommand of n robots (qr_torque_stance_leg_controller.cpp:89-477): the complete
+        vmc_in [37][n], ratio [8][n] and stance_out [33][n] from arrays the device holds.  desc = stance_desc(mode, ...)."""
+        self._chk(self._lib.qrgpu_stance_update_batch(self._h, n, C.byref(desc), float(current_time), int(bool(stop)), int(bool(reset)), _dp(est_in),
+                                                      _dp(est_out), _dp(ground_out), _dp(rpy), _dp(gait_out), _dp(gait_state), _dp(stance_cmd),
+                                                      _dp(stance_state), _dp(vmc_in), _dp(ratio), _dp(stance_out)))
+
+    def stance_command_batch(self, n, desc, tau, motor_cmd, vmc_in=None, stance_out=None, swing_q=None, swing_flag=None, stop=False):
+        """The motor-command tail of GetAction (:503-541) merged with the swing command (qr_locomotion_controller.cpp:128-147):
+        motor_cmd [60][n] = p, Kp, d, Kd, tua.  vmc_in / stance_out: WALK only; swing_q [24][n], swing_flag [4][n]: both or neither."""
+        self._chk(self._lib.qrgpu_stance_command_batch(self._h, n, C.byref(desc), int(bool(stop)), _dp(vmc_in), _dp(stance_out), _dp(tau), _dp(swing_q),
+                                                       _dp(swing_flag), _dp(motor_cmd)))
+
+    def stance_tick_batch(self, n, desc, est_in, est_out, ground_out, rpy, gait_out, stance_cmd, stance_state, vmc_in, force, tau, motor_cmd,
+                          gait_state=None, ratio=None, stance_out=None, status=None, swing_q=None, swing_flag=None, type_id=None, current_time=0.0,
+                          stop=False, reset=False):
+        """stance_update_batch, the force-balance QP overload the mode selects, stance_command_batch: three launches on the context's stream."""
+        self._chk(self._lib.qrgpu_stance_tick_batch(self._h, n, C.byref(desc), float(current_time), int(bool(stop)), int(bool(reset)), _dp(type_id),
+                                                    _dp(est_in), _dp(est_out), _dp(ground_out), _dp(rpy), _dp(gait_out), _dp(gait_state), _dp(stance_cmd),
+                                                    _dp(stance_state), _dp(vmc_in), _dp(ratio), _dp(stance_out), _dp(force), _dp(tau), _dp(status),
+                                                    _dp(swing_q), _dp(swing_flag), _dp(motor_cmd)))
 
     def pack_state_batch(self, n, com_offset, est_in, est_out, rpy, mpc_state=None, fb_state=None):
         """mpc_state[28] / fb_state[37] from the estimator's inputs and outputs (SolveDenseMPC :385-399, UpdateModel :136-156)."""
