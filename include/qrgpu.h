@@ -27,6 +27,7 @@
  *   qrgpu_swing_targets_batch <- qrRaibertSwingLegController::GetAction (ADVANCED_TROT)   QS/controllers/qr_swing_leg_controller.cpp:362-424
  *   qrgpu_footholds_batch  <- qrRaibertSwingLegController::Update + qrFootholdPlanner::ComputeHeuristicFootHold
  *                             QS/controllers/qr_swing_leg_controller.cpp:211-236, QS/planner/qr_foothold_planner.cpp:110-239
+ *   qrgpu_pose_plan_batch     <- qrPosePlanner::Update (SQP) + ResetBasePose                       QS/planner/qr_pose_planner.cpp
  *   qrgpu_stance_update_batch <- TorqueStanceLegController::UpdateFRatio + UpdateDesCommand   QS/controllers/balance_controller/
  *                             qr_torque_stance_leg_controller.cpp:89-172, 174-477 (with qrComAdjuster::Update, QS/planner/qr_com_adjuster.cpp:61-108,
  *                             and qrPosePlanner::GetIntermediateBasePose, QI/planner/qr_pose_planner.h:327-365)
@@ -551,7 +552,8 @@ int qrgpu_swing_action_batch(qrgpu_ctx *ctx, int n, const qrgpu_swing_mode_desc 
  *   d_gait_state the open-loop generator's state (allowSwitchLegState, rows 20-23): needed by POSITION and ADVANCED_TROT, else may be NULL
  *   d_stance_cmd [QRGPU_STANCE_CMD_ROWS][n], the one input that comes from the host, and changes only when the operator's command or the walk
  *                pose plan does: row 0 stateDes(2); 1-3 stateDes 6..8; 4-6 stateDes 9..11; 7-12 the pose planner's segment source (the pose at
- *                its last Update / ResetBasePose); 13-18 poseDest; 19-24 twist; 25-27 footholdPlanner->GetDesiredComPose().tail(3)
+ *                its last Update / ResetBasePose); 13-18 poseDest; 19-24 twist (rows 7-24 are what qrgpu_pose_plan_batch writes on the device);
+ *                25-27 footholdPlanner->GetDesiredComPose().tail(3)
  *   d_stance_state [QRGPU_STANCE_STATE_FLOATS][n] the controller's memory: row 0 heightInControlFrame, which est_out reports as NaN while no
  *                foot is in stance and the reference then keeps; reset != 0 starts it at desc->body_height (qr_robot_pose_estimator.cpp:50)
  * current_time and desc->pose_reset_time give the WALK pose phase while robot_stop (GetIntermediateBasePose(currentTime)); otherwise that
@@ -602,6 +604,58 @@ int qrgpu_stance_tick_batch(qrgpu_ctx *ctx, int n, const qrgpu_stance_desc *desc
                             const float *d_gait_out, const float *d_gait_state, const float *d_stance_cmd, float *d_stance_state, float *d_vmc_in,
                             float *d_ratio, float *d_stance_out, float *d_force, float *d_tau, int *d_status, const float *d_swing_q,
                             const float *d_swing_flag, float *d_motor_cmd);
+
+/* Walk pose planner: qrPosePlanner::Update with its SQP (QS/planner/qr_pose_planner.cpp:72-456: 20 iterations, each a 6-variable QuadProg++
+ * solve with 3N = 9 or 12 inequality rows) and ResetBasePose (QI/planner/qr_pose_planner.h:311-320), one wavefront per robot.  It writes the
+ * rows of d_stance_cmd that qrgpu_stance_update_batch reads in WALK, so a WALK tick is queued on the context's stream with no host copy:
+ * ground, estimator, walk gait, pose plan, swing update, stance tick, swing action.
+ * Inputs, the arrays and rows of qrgpu_stance_update_batch: d_est_in quat_wxyz 6-9 (GetBaseOrientation); d_est_out
+ * footPositionsInBaseFrame 12-23, basePosition 36-38; d_ground_out controlFrameRPY 6-8 (row 7, the pitch, is the one value the planner uses;
+ * controlFrameOrientation 9-12 only enters values the reference computes and never reads); d_rpy [3][n] GetBaseRollPitchYaw; d_walk_out
+ * desiredLegState 8-11, legState 12-15, curLegState 16-19.  Foot positions in the world frame are invertRigidTransform(basePosition, quat,
+ * footPositionsInBaseFrame) (qr_robot.cpp:222-230).  GetEstimatedPosition() is taken from d_est_out rows 36-38, as the stance kernel takes
+ * the base position: in the reference qrRobotEstimator::estimatedPosition is its own member, filled from the pose estimator's pose
+ * (qr_robot_estimator.cpp:40,58,87), which is also what robot->basePosition receives; this ABI has one array for both.
+ * event, with d_event NULL, applies to every robot: 0 nothing (with reset == 0 the call returns without a launch), 1 Update, 2 ResetBasePose,
+ * 3 Update for exactly the robots with a leg whose legState is SWING (0) and curLegState STANCE (1) -- the switchToSwing rule of
+ * qr_locomotion_controller.cpp:81-89 (USERDEFINED_SWING legs are not built in this library's walk gait).  d_event [n] non-NULL: its values
+ * 0 / 1 / 2 per robot win (anything else is 0).  The swing semaphore and robot->stop stay with the caller.
+ * reset != 0 first puts every robot's d_pose_state into the constructed state (:31-69): Lambda 0.1 x 12, size 12, quat identity, rIB the
+ * estimated position, poseDest (rIB, 0, 0, 0).
+ * d_pose_state [QRGPU_POSE_STATE_ROWS][n], the members the reference keeps between calls or publishes: rows 0-11 Lambda, 12 its current
+ * size (3N of the last Update; conservativeResize(3N) truncates it), 13-15 rIB, 16-19 quat, 20-25 poseDest.  Lambda(i) = u[i] of the last
+ * QP, u indexed by working-set SLOT as solve_quadprog_test returns it, not by constraint.
+ * d_stance_cmd [QRGPU_STANCE_CMD_ROWS][n]: for a robot with an event and no fatal flag rows 7-12 (segment source: estimated position,
+ * d_rpy), 13-18 (poseDest) and, ResetBasePose only, 19-24 (twist = 0) are written; every other row and robot is left as it was.
+ * d_pose_out [QRGPU_POSE_OUT_ROWS][n] (may be NULL; inspection, Update only): rows 7k .. 7k+5 the step p of SQP iteration k and 7k+6 the
+ * size of the working set its QP ended with (iterations >= loops are not written); 140-151 the final Lambda (0 beyond 3N); 152 N;
+ * 153 the vertices kept, bit per counter-clockwise slot (slot c is leg {0, 2, 3, 1}[c]); 154-165 u of iteration 0 (0 beyond 3N);
+ * 166-177 the working set A[] of iteration 0 in slot order (-1 beyond its size).
+ * d_pose_flags [n] (required): QRGPU_PP_* bits of the robot's last event, written for every robot with an event.  FEW_CONTACTS, NOT_PD and
+ * NAN are fatal: the robot's rows of d_stance_cmd and d_pose_state stay untouched.
+ * desc->rBH is 3*leg+axis in leg order; desc->loops is clamped to 1 .. QRGPU_POSE_MAX_LOOPS.
+ * QRGPU_ERR_BAD_ARG (outputs untouched): a NULL required array, n < 1 or n > max_batch, event outside 0..3. */
+#define QRGPU_POSE_MAX_LOOPS  20
+#define QRGPU_POSE_STATE_ROWS 26
+#define QRGPU_POSE_OUT_ROWS   (7 * QRGPU_POSE_MAX_LOOPS + 38)
+#define QRGPU_PP_FEW_CONTACTS 0x1    /* fewer than 3 valid vertices: the reference throws "N < 3" (with no contact it first divides by zero) */
+#define QRGPU_PP_NOT_PD       0x2    /* QuadProg++'s Cholesky would throw: hessF - sum Lambda hessG is not positive definite */
+#define QRGPU_PP_INFEASIBLE   0x4    /* a QP returned +inf with the iterate it had; the reference goes on with that x and u, so does the kernel */
+#define QRGPU_PP_LAMBDA_GROWN 0x8    /* 3N exceeds Lambda's size: the reference reads uninitialised entries, the kernel uses 0.1 */
+#define QRGPU_PP_NONCONVEX    0x10   /* the convexity test of :138-168 erased a vertex */
+#define QRGPU_PP_NAN          0x20   /* a non-finite poseDest (or quaternion, base position, foot position, ground pitch); nothing is written */
+#define QRGPU_PP_MAXITER      0x40   /* a QP was stopped after 200 active-set steps, a bound the reference does not have (set with INFEASIBLE) */
+typedef struct {
+    float rBH[12];                    /* the planner's own hip offsets (qr_pose_planner.cpp:48-50), not the robot's */
+    float l_min, l_max, omega, eps;   /* leg-length window, weight of the support-polygon term, shrink of the polygon */
+    float body_height;                /* bodyHight = A1_BODY_HIGHT */
+    int   loops;                      /* SQP iterations */
+} qrgpu_pose_plan_desc;
+/* (+-0.18, +-0.047, 0), 0.22, 0.35, 0.5, 0.1, 0.27, 20 */
+void qrgpu_pose_plan_desc_default(qrgpu_pose_plan_desc *d);
+int qrgpu_pose_plan_batch(qrgpu_ctx *ctx, int n, const qrgpu_pose_plan_desc *desc, int event, const int *d_event, int reset,
+                          const float *d_est_in, const float *d_est_out, const float *d_ground_out, const float *d_rpy,
+                          const float *d_walk_out, float *d_pose_state, float *d_stance_cmd, float *d_pose_out, int *d_pose_flags);
 
 /* The tick's state arrays from the estimator's inputs and outputs: what SolveDenseMPC (qr_mpc_stance_leg_controller.cpp:385-399:
  * pos, baseVInWorldFrame, quat, baseWInWorldFrame, foot2ComInWorldFrame = baseRMat (footPositionsInBaseFrame - comOffset), rpy) and

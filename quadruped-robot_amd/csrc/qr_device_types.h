@@ -206,6 +206,23 @@ struct StanceDesc {
     float motor_kp[12], motor_kd[12];
 };
 
+// Walk pose planner (qrgpu_pose_plan_desc); rBH is kept per leg (3*leg+axis), the kernel reorders it.  The flag bits are the QRGPU_PP_* of qrgpu.h.
+#define QR_POSE_MAX_LOOPS  20
+#define QR_POSE_STATE_ROWS 26
+#define QR_POSE_OUT_ROWS   (7 * QR_POSE_MAX_LOOPS + 38)
+#define QR_PP_FEW_CONTACTS 0x1
+#define QR_PP_NOT_PD       0x2
+#define QR_PP_INFEASIBLE   0x4
+#define QR_PP_LAMBDA_GROWN 0x8
+#define QR_PP_NONCONVEX    0x10
+#define QR_PP_NAN          0x20
+#define QR_PP_MAXITER      0x40
+struct PosePlanDesc {
+    float rBH[12];
+    float l_min, l_max, omega, eps, body_height;
+    int loops;
+};
+
 // Walk gait generator parameters after the constructor's bookkeeping (qrgpu_walk_gait_desc -> qrgpu_api.hip)
 struct WalkDesc {
     float duty_factor[4], initial_leg_phase[4], full[4];

@@ -204,6 +204,49 @@ __device__ __forceinline__ void rotmat_t_to_rpy(const float r[3][3], float rpy[3
     rpy[0] = atan2f(2 * (q2 * q3 + q0 * q1), ((q0 * q0 - q1 * q1) - q2 * q2) + q3 * q3);
 }
 
+// vectorToSkewMat / crossMatrix (qr_se3.h:95-103, 121-130)
+__device__ __forceinline__ void vector_to_skew_mat(const float v[3], float m[3][3])
+{
+    m[0][0] = 0.f; m[0][1] = -v[2]; m[0][2] = v[1];
+    m[1][0] = v[2]; m[1][1] = 0.f; m[1][2] = -v[0];
+    m[2][0] = -v[1]; m[2][1] = v[0]; m[2][2] = 0.f;
+}
+
+// so3ToQuat (qr_se3.h:402-418): theta in float, the half angle and its sine / cosine in double
+__device__ __forceinline__ void so3_to_quat(const float so3[3], float q[4])
+{
+#pragma clang fp contract(off)
+    const float theta = sqrtf((so3[0] * so3[0] + so3[1] * so3[1]) + so3[2] * so3[2]);
+    if (fabs((double)theta) < 1.e-6) { q[0] = 1.f; q[1] = 0.f; q[2] = 0.f; q[3] = 0.f; return; }
+    const double h = (double)theta / 2., sh = sin(h);
+    q[0] = (float)cos(h);
+    q[1] = (float)((double)(so3[0] / theta) * sh);
+    q[2] = (float)((double)(so3[1] / theta) * sh);
+    q[3] = (float)((double)(so3[2] / theta) * sh);
+}
+
+// ConcatenationTwoQuats(q, p) = (q0 p0 - q_.p_, q0 p_ + p0 q_ + [q_]x p_) (qr_se3.h:484-494)
+__device__ __forceinline__ void concatenation_two_quats(const float q[4], const float p[4], float out[4])
+{
+#pragma clang fp contract(off)
+    float S[3][3];
+    vector_to_skew_mat(q + 1, S);
+    out[0] = q[0] * p[0] - ((q[1] * p[1] + q[2] * p[2]) + q[3] * p[3]);
+#pragma unroll
+    for (int r = 0; r < 3; ++r) out[1 + r] = (q[0] * p[1 + r] + p[0] * q[1 + r]) + dot3(S[r], p[1], p[2], p[3]);
+}
+
+// quatToRPY (qr_se3.h:209-223)
+__device__ __forceinline__ void quat_to_rpy(const float q[4], float rpy[3])
+{
+#pragma clang fp contract(off)
+    const float q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
+    const float as = (float)fmin(-2. * (double)(q1 * q3 - q0 * q2), .99999);
+    rpy[2] = atan2f(2 * (q1 * q2 + q0 * q3), ((q0 * q0 + q1 * q1) - q2 * q2) - q3 * q3);
+    rpy[1] = asinf(as);
+    rpy[0] = atan2f(2 * (q2 * q3 + q0 * q1), ((q0 * q0 - q1 * q1) - q2 * q2) + q3 * q3);
+}
+
 // ---- swing-leg helpers shared by the swing kernels (qr_estimator_kernel.hip, qr_swing_modes_kernel.hip); fp32, contraction off -------
 
 // SwingFootTrajectory::GenerateTrajectoryPoint's phase warp (phaseModule = true), qr_foot_trajectory_generator.cpp:328-335

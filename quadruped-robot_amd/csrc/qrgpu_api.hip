@@ -32,6 +32,8 @@ __global__ void qr_stance_update_kernel(int n, StanceDesc S, float current_time,
                                         float *g_st, float *g_vmc_in, float *g_ratio, float *g_out);
 __global__ void qr_stance_command_kernel(int n, StanceDesc S, int stop, const float *g_vmc_in, const float *g_stance_out, const float *g_tau,
                                          const float *g_swing_q, const float *g_swing_flag, float *g_cmd);
+__global__ void qr_pose_plan_kernel(int n, PosePlanDesc D, int event, const int *g_event, int reset, const float *g_est_in, const float *g_est_out,
+                                    const float *g_ground, const float *g_rpy, const float *g_walk, float *g_state, float *g_cmd, float *g_out, int *g_flags);
 __global__ void qr_pack_state_kernel(int n, float c0, float c1, float c2, const float *g_in, const float *g_est, const float *g_rpy, float *g_mpc, float *g_fb);
 __global__ void qr_estimator_kernel(int n, EstimatorDesc D, const float *g_in, const unsigned *g_tick, double *st, float *g_out);
 __global__ void qr_vmc_kernel(VmcLaunch P, const int *type_id, const float *g_in, const float *g_q, float *g_force, float *g_tau, int *g_status);
@@ -881,6 +883,35 @@ int qrgpu_stance_tick_batch(qrgpu_ctx *c, int n, const qrgpu_stance_desc *desc, 
     e = launch_vmc(c, n, d_type_id, d_vmc_in, world ? d_ratio : nullptr, d_q, d_force, d_tau, d_status);
     if (e != QRGPU_OK) return e;
     return qrgpu_stance_command_batch(c, n, desc, robot_stop, d_vmc_in, d_stance_out, d_tau, d_swing_q, d_swing_flag, d_motor_cmd);
+}
+
+void qrgpu_pose_plan_desc_default(qrgpu_pose_plan_desc *d)
+{
+    if (!d) return;
+    memset(d, 0, sizeof(*d));
+    for (int leg = 0; leg < 4; ++leg) { d->rBH[3 * leg] = leg < 2 ? 0.18f : -0.18f; d->rBH[3 * leg + 1] = (leg & 1) ? 0.047f : -0.047f; }
+    d->l_min = 0.22f; d->l_max = 0.35f; d->omega = 0.5f; d->eps = 0.1f; d->body_height = 0.27f; d->loops = QRGPU_POSE_MAX_LOOPS;
+}
+
+int qrgpu_pose_plan_batch(qrgpu_ctx *c, int n, const qrgpu_pose_plan_desc *desc, int event, const int *d_event, int reset, const float *d_est_in,
+                          const float *d_est_out, const float *d_ground_out, const float *d_rpy, const float *d_walk_out, float *d_pose_state,
+                          float *d_stance_cmd, float *d_pose_out, int *d_pose_flags)
+{
+    if (!c || n <= 0 || n > c->max_batch || !desc || event < 0 || event > 3) return QRGPU_ERR_BAD_ARG;
+    if (!d_est_in || !d_est_out || !d_ground_out || !d_rpy || !d_walk_out || !d_pose_state || !d_stance_cmd || !d_pose_flags) return QRGPU_ERR_BAD_ARG;
+    if (!d_event && event == 0 && !reset) return QRGPU_OK;                                              // nothing to do: no launch
+    static_assert(QRGPU_POSE_STATE_ROWS == QR_POSE_STATE_ROWS && QRGPU_POSE_OUT_ROWS == QR_POSE_OUT_ROWS && QRGPU_POSE_MAX_LOOPS == QR_POSE_MAX_LOOPS, "pose rows");
+    static_assert(QRGPU_PP_FEW_CONTACTS == QR_PP_FEW_CONTACTS && QRGPU_PP_NOT_PD == QR_PP_NOT_PD && QRGPU_PP_INFEASIBLE == QR_PP_INFEASIBLE &&
+                  QRGPU_PP_LAMBDA_GROWN == QR_PP_LAMBDA_GROWN && QRGPU_PP_NONCONVEX == QR_PP_NONCONVEX && QRGPU_PP_NAN == QR_PP_NAN &&
+                  QRGPU_PP_MAXITER == QR_PP_MAXITER, "pose flags");
+    PosePlanDesc D;
+    memcpy(D.rBH, desc->rBH, sizeof(D.rBH));
+    D.l_min = desc->l_min; D.l_max = desc->l_max; D.omega = desc->omega; D.eps = desc->eps; D.body_height = desc->body_height; D.loops = desc->loops;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipLaunchKernelGGL(qr_pose_plan_kernel, dim3(8 * ((n + 7) / 8)), dim3(64), 0, c->stream, n, D, event, d_event, reset ? 1 : 0, d_est_in, d_est_out,
+                       d_ground_out, d_rpy, d_walk_out, d_pose_state, d_stance_cmd, d_pose_out, d_pose_flags);
+    HIPCHK(c, hipGetLastError());
+    return QRGPU_OK;
 }
 
 int qrgpu_mpc_frontend_batch(qrgpu_ctx *c, int n, int num_horizon_l, float dt_ctrl, float dt_mpc, const float *d_fe_in, float *d_fe_state,

@@ -137,6 +137,30 @@ def stance_desc(mode, terrain=None, force_in_world=None, **fields):
     return d
 
 
+POSE_MAX_LOOPS, POSE_STATE_ROWS = 20, 26
+POSE_OUT_ROWS = 7 * POSE_MAX_LOOPS + 38
+PP_FEW_CONTACTS, PP_NOT_PD, PP_INFEASIBLE, PP_LAMBDA_GROWN, PP_NONCONVEX, PP_NAN, PP_MAXITER = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20, 0x40
+POSE_EVENT_NONE, POSE_EVENT_UPDATE, POSE_EVENT_RESET_BASE_POSE, POSE_EVENT_SWITCH_TO_SWING = 0, 1, 2, 3
+
+
+class pose_plan_desc_struct(C.Structure):
+    _fields_ = [("rBH", C.c_float * 12), ("l_min", C.c_float), ("l_max", C.c_float), ("omega", C.c_float), ("eps", C.c_float),
+                ("body_height", C.c_float), ("loops", C.c_int)]
+
+
+def pose_plan_desc(**fields):
+    """qrgpu_pose_plan_desc: the library's defaults (the reference's constants), with any field overridden (scalars or sequences by name)."""
+    d = pose_plan_desc_struct()
+    load_library().qrgpu_pose_plan_desc_default(C.byref(d))
+    for name, v in fields.items():
+        cur = getattr(d, name)
+        if hasattr(cur, "__len__"):
+            for k, x in enumerate(v): cur[k] = float(x)
+        else:
+            setattr(d, name, int(v) if name == "loops" else float(v))
+    return d
+
+
 EPILOGUE_HIP_COMP, EPILOGUE_CLIP = 1, 2
 COMM_ID_BYTES = 128
 
@@ -167,7 +191,8 @@ EXPORTS = ["qrgpu_model_desc_default", "qrgpu_create", "qrgpu_destroy", "qrgpu_s
            "qrgpu_enable_flop_count", "qrgpu_mpc_flop_counts", "qrgpu_mpc_set_hessian_mode", "qrgpu_wbc_inspect_batch", "qrgpu_host_alloc", "qrgpu_host_free",
            "qrgpu_memcpy_async", "qrgpu_memset_async", "qrgpu_mark", "qrgpu_mark_elapsed_ms", "qrgpu_set_tick_pipeline", "qrgpu_set_tick_overlap",
            "qrgpu_tick_fence", "qrgpu_tick_overlap_stats", "qrgpu_swing_mode_desc_default", "qrgpu_swing_update_batch", "qrgpu_swing_action_batch",
-           "qrgpu_stance_desc_default", "qrgpu_stance_update_batch", "qrgpu_stance_command_batch", "qrgpu_stance_tick_batch"]
+           "qrgpu_stance_desc_default", "qrgpu_stance_update_batch", "qrgpu_stance_command_batch", "qrgpu_stance_tick_batch",
+           "qrgpu_pose_plan_desc_default", "qrgpu_pose_plan_batch"]
 
 
 def load_library():
@@ -242,6 +267,8 @@ def load_library():
     lib.qrgpu_stance_update_batch.argtypes = [vp, ip, C.POINTER(stance_desc_struct), C.c_float, ip, ip] + [vp] * 11
     lib.qrgpu_stance_command_batch.argtypes = [vp, ip, C.POINTER(stance_desc_struct), ip] + [vp] * 6
     lib.qrgpu_stance_tick_batch.argtypes = [vp, ip, C.POINTER(stance_desc_struct), C.c_float, ip, ip] + [vp] * 18
+    lib.qrgpu_pose_plan_desc_default.argtypes = [C.POINTER(pose_plan_desc_struct)]; lib.qrgpu_pose_plan_desc_default.restype = None
+    lib.qrgpu_pose_plan_batch.argtypes = [vp, ip, C.POINTER(pose_plan_desc_struct), ip, vp, ip] + [vp] * 9
     lib.qrgpu_vmc_force1.argtypes = [vp, ip, fp, fp, fp, fp, C.POINTER(ip)]
     lib.qrgpu_vmc_force_world1.argtypes = [vp, ip, fp, fp, fp, fp, fp, C.POINTER(ip)]
     lib.qrgpu_mpc_frontend_batch.argtypes = [vp, ip, ip, C.c_float, C.c_float] + [vp] * 6
@@ -612,6 +639,15 @@ class Context:
         self._chk(self._lib.qrgpu_stance_update_batch(self._h, n, C.byref(desc), float(current_time), int(bool(stop)), int(bool(reset)), _dp(est_in),
                                                       _dp(est_out), _dp(ground_out), _dp(rpy), _dp(gait_out), _dp(gait_state), _dp(stance_cmd),
                                                       _dp(stance_state), _dp(vmc_in), _dp(ratio), _dp(stance_out)))
+
+    def pose_plan_batch(self, n, desc, est_in, est_out, ground_out, rpy, walk_out, pose_state, stance_cmd, pose_flags, event=POSE_EVENT_SWITCH_TO_SWING,
+                        event_words=None, pose_out=None, reset=False):
+        """qrPosePlanner::Update (the 20-iteration SQP) / ResetBasePose of n robots (qr_pose_planner.cpp:72-456): rows 7-24 of stance_cmd
+        [28][n] from arrays the device holds.  event: POSE_EVENT_*; event_words [n] int32 (0 / 1 / 2 per robot) wins when given.
+        desc = pose_plan_desc(...); pose_state [26][n]; pose_flags [n] int32 of PP_* bits; pose_out [178][n] or None."""
+        self._chk(self._lib.qrgpu_pose_plan_batch(self._h, n, C.byref(desc), int(event), _dp(event_words), int(bool(reset)), _dp(est_in), _dp(est_out),
+                                                  _dp(ground_out), _dp(rpy), _dp(walk_out), _dp(pose_state), _dp(stance_cmd), _dp(pose_out),
+                                                  _dp(pose_flags)))
 
     def stance_command_batch(self, n, desc, tau, motor_cmd, vmc_in=None, stance_out=None, swing_q=None, swing_flag=None, stop=False):
         """The motor-command tail of GetAction (:503-541) merged with the swing command (qr_locomotion_controller.cpp:128-147):
