@@ -1,24 +1,14 @@
-// Shared host/device plain structs for the qrgpu kernels (gfx950).
+// Shared host/device plain structs for the qrgpu kernels (gfx950).  The parameter blocks a caller fills (qrgpu_*_desc), the status and flag bits
+// and the row counts are those of include/qrgpu.h: kernels take the public structs by value and use the public names.
 #pragma once
 #include <stdint.h>
 #include <hip/hip_runtime.h>
+#include "../../include/qrgpu.h"
 
 namespace qrgpu {
 
 #define QR_QH 96                  // hard cap on the MPC working-set size (rows of S^-1 held in LDS)
-#define QR_MAX_TYPES 4
 #define QR_WARM_STRIDE 80
-
-// status bits (mirror include/qrgpu.h)
-#define QRGPU_ST_MPC_MAXITER_D  0x1
-#define QRGPU_ST_MPC_INFEAS_D   0x2
-#define QRGPU_ST_MPC_OVERFLOW_D 0x4
-#define QRGPU_ST_MPC_NOTSPD_D   0x8
-#define QRGPU_ST_WBC_MAXITER_D  0x10
-#define QRGPU_ST_WBC_INFEAS_D   0x20
-#define QRGPU_ST_VMC_MAXITER_D  0x40
-#define QRGPU_ST_VMC_INFEAS_D   0x80
-#define QRGPU_ST_BAD_TYPE_D     0x01000000   // type id out of range or never set up (bit 24: above the flag byte and the 16-bit iteration count)
 
 // XCD-aware robot index.  Workgroups are dealt round-robin over the 8 XCDs (MI355X_MICROARCH.md: blocks b and b+8
 // share an XCD) and each XCD has its own L2.  The SoA inputs put 32 consecutive robots in one 128-B line, so with
@@ -42,7 +32,7 @@ struct MpcType {
 };
 
 struct MpcLaunch {
-    MpcType type[QR_MAX_TYPES];
+    MpcType type[QRGPU_MAX_TYPES];
     int n;
     int horizon;
     int lds_bytes;
@@ -145,91 +135,50 @@ struct MpcLaunch {
     int *rescue_taken;          // [0..1] the rescue list's second head, [2..3] the planned list's head, by parity
     int linger;                 // planned launch: its first `linger` workgroups stay for the hand-overs, the others leave when the planned list is empty
 };
-#define QRGPU_ST_PIPE_TIMEOUT_D 0x02000000   // pipelined tick: the WBC gave up waiting for this robot's MPC forces (never seen; never silent)
 
-// Force-balance QP parameters (qrgpu_vmc_desc): ComputeContactForce's arguments that do not change per tick.
-struct VmcType {
-    float mass;
-    float inertia[9];          // robot->totalInertia, Eigen column-major
-    float acc_weight[6];
-    float reg_weight, friction, fmin_ratio, fmax_ratio;
-    float hip_l, upper_l, lower_l;
+// Global-memory arguments of one MPC launch (SoA, [field][robot]; see include/qrgpu.h)
+struct MpcIO {
+    const int *type_id;
+    const float *g_state, *g_traj, *g_gait, *g_q;
+    float *g_force, *g_tau;
+    int *g_status;
+    float *dbgH, *dbgG, *g_force_wbc;
+    int force_stride;
+    long long *dbgT;
 };
+
+// Force-balance QP: ComputeContactForce's arguments that do not change per tick, per type.
 struct VmcLaunch {
-    VmcType type[QR_MAX_TYPES];
+    qrgpu_vmc_desc type[QRGPU_MAX_TYPES];
     int n;
     int type_ready;          // bit t: type t was set up (robots naming any other type are flagged QRGPU_ST_BAD_TYPE)
     const float *ratio;      // [8][n] per-leg fMinRatio[4], fMaxRatio[4] of the world-frame overload, or null (the type's scalar ratios)
 };
 
-// Velocity-estimator parameters (qrgpu_estimator_desc)
-struct EstimatorDesc {
-    float hip_l, upper_l, lower_l;
-    float hip_offset[12];
-    float time_step, accelerometer_variance, sensor_variance;
-    int window;
-    float body_height;
-};
-
-// Foothold heuristic parameters (qrgpu_foothold_desc)
-struct FootholdDesc {
-    float hip_offset[12], default_hip_position[12];
-    float hip_l, swing_kp[3], foot_clearance;
-};
-
-// Open-loop gait generator parameters (qrgpu_gait_desc)
-struct GaitDesc {
-    float stance_duration[4], duty_factor[4], initial_leg_phase[4];
-    int initial_leg_state[4];
-    float contact_detection_phase_threshold, wait_time;
-    int advanced_trot;
-};
-
-// Velocity-mode swing action parameters (qrgpu_swing_velocity_desc)
-struct SwingVelDesc { float hip_pos_com[12], stance_duration[4], swing_kp[3], desired_height; };
-
-// Swing-leg controller of the walk and position modes, and the lift-off memory of every mode (qrgpu_swing_mode_desc)
-#define QR_SWING_MAX_GAPS 8
-#define QR_SWING_MAX_PLAN 32
-struct SwingModeDesc {
-    int mode, terrain, is_sim;
-    float foothold_delta;
-    int n_gaps;
-    float gap_distance[QR_SWING_MAX_GAPS], gap_width;
-};
-
-// Force-balance stance controller: front-end and motor commands (qrgpu_stance_desc)
-struct StanceDesc {
-    int mode, terrain, force_in_world;
-    float kp[6], kd[6], max_ddq[6], min_ddq[6];
-    float desired_height, desired_speed[3], desired_twisting_speed, body_height, pose_reset_time;
-    float motor_kp[12], motor_kd[12];
-};
-
-// Walk pose planner (qrgpu_pose_plan_desc); rBH is kept per leg (3*leg+axis), the kernel reorders it.  The flag bits are the QRGPU_PP_* of qrgpu.h.
-#define QR_POSE_MAX_LOOPS  20
-#define QR_POSE_STATE_ROWS 26
-#define QR_POSE_OUT_ROWS   (7 * QR_POSE_MAX_LOOPS + 38)
-#define QR_PP_FEW_CONTACTS 0x1
-#define QR_PP_NOT_PD       0x2
-#define QR_PP_INFEASIBLE   0x4
-#define QR_PP_LAMBDA_GROWN 0x8
-#define QR_PP_NONCONVEX    0x10
-#define QR_PP_NAN          0x20
-#define QR_PP_MAXITER      0x40
-struct PosePlanDesc {
-    float rBH[12];
-    float l_min, l_max, omega, eps, body_height;
-    int loops;
-};
-
-// Walk gait generator parameters after the constructor's bookkeeping (qrgpu_walk_gait_desc -> qrgpu_api.hip)
+// Walk gait generator parameters after the constructor's bookkeeping (qrgpu_walk_gait_desc -> qrgpu_stages.hip)
 struct WalkDesc {
     float duty_factor[4], initial_leg_phase[4], full[4];
     int initial_leg_state[4], state_index0[4];
     float contact_detection_phase_threshold, true_swing_start_in_swing;
     int nq; int que[4]; float ratio[4], accum[5];
 };
+
+// The diagnostic timeline buffer (qrgpu_debug_timeline, -DQR_TIMELINE builds), in long long words: region offsets and sizes.
+#define QR_TL_TICKS       0                                    // [64 epochs][8] first / last moments of a tick's launches
+#define QR_TL_TICKS_N     512
+#define QR_TL_GATES       (QR_TL_TICKS + QR_TL_TICKS_N)        // [64][2] when the gate of a chained tick came up / opened
+#define QR_TL_GATES_N     128
+#define QR_TL_PLANNED     (QR_TL_GATES + QR_TL_GATES_N)        // [64][2] planned launch: first start / last end (the planned extremes)
+#define QR_TL_PLANNED_N   128
+#define QR_TL_SOLVES      (QR_TL_PLANNED + QR_TL_PLANNED_N)    // [2][16 epochs][1024 robots] publish time, cross-tick wait
+#define QR_TL_SOLVES_N    (2 * 16 * 1024)
+#define QR_TL_SOLVE_WAITS (QR_TL_SOLVES + 16 * 1024)           //   ... the second half
+#define QR_TL_PLANS       (QR_TL_SOLVES + QR_TL_SOLVES_N)      // [64][64] list length each planned workgroup read, then [64] what each tick's planning left
+#define QR_TL_PLANS_N     (4096 + 64)
+#define QR_TL_PLAN_LEFT   (QR_TL_PLANS + 4096)                 //   ... the trailing [64]
+#define QR_TL_TRACE       (QR_TL_PLANS + QR_TL_PLANS_N)        // [16 epochs][1024 robots] QR_TRACE bits
+#define QR_TL_TRACE_N     16384
+#define QR_TL_WORDS       (QR_TL_TRACE + QR_TL_TRACE_N)
 
 // Bytes of LDS in front of the block-packed inverse Hessian (must match the carve in qr_mpc_kernel.hip).
 // The four-wave active set needs the exchange buffers xz[4][NV], xr[4][64]; the single-wave one (h > 11 by default, and the

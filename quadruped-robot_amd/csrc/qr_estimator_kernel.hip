@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include "qr_device_types.h"
 #include "qr_wave_helpers.h"
+#include "qr_kernels.h"
 
 namespace qrgpu {
 
@@ -99,7 +100,7 @@ template <typename T> __device__ __forceinline__ void neumaier(T &sum, T &corr, 
 #define EST_AWIN 36
 #define EST_VWIN 96
 
-__global__ void __launch_bounds__(64) qr_estimator_kernel(int n, EstimatorDesc D, const float *__restrict__ g_in, const unsigned *__restrict__ g_tick,
+__global__ void __launch_bounds__(64) qr_estimator_kernel(int n, qrgpu_estimator_desc D, const float *__restrict__ g_in, const unsigned *__restrict__ g_tick,
                                                           double *__restrict__ st, float *__restrict__ g_out)
 {
 #pragma clang fp contract(off)
@@ -351,7 +352,7 @@ __global__ void __launch_bounds__(64) qr_pack_state_kernel(int n, float c0, floa
 //   leg inverse kinematics                      quadruped/src/robots/qr_robot.cpp:106-124, 200-219
 // Writes, for the legs flagged as swinging only: rows 15-50 of wbc_cmd (pFoot_des, vFoot_des, aFoot_des), the foot target in the
 // world frame (an input of the MPC front-end) and the joint angle / velocity targets of the swing-leg position command.
-__global__ void __launch_bounds__(64) qr_swing_kernel(int n, EstimatorDesc D, const float *__restrict__ g_in, float *__restrict__ g_cmd, float *__restrict__ g_tgt_world,
+__global__ void __launch_bounds__(64) qr_swing_kernel(int n, qrgpu_estimator_desc D, const float *__restrict__ g_in, float *__restrict__ g_cmd, float *__restrict__ g_tgt_world,
                                                       float *__restrict__ g_qdes)
 {
 #pragma clang fp contract(off)
@@ -411,7 +412,7 @@ __global__ void __launch_bounds__(64) qr_swing_kernel(int n, EstimatorDesc D, co
 // resetTime, lastTime, cumDt, gaitCycle, then per leg cur, last, desired, legState, allow, firstSwing, firstStance, phaseInFullCycle,
 // normalizedPhase, contactStartPhase, swingTimeRemaining, (spare); `fresh` != 0 applies Reset(0) first.  Plain float arithmetic and
 // fmodf (exact): bit-identical to the CPU restatement.
-__global__ void __launch_bounds__(64) qr_gait_kernel(int n, GaitDesc D, float currentTime, int stop, int fresh, const float *__restrict__ g_contact,
+__global__ void __launch_bounds__(64) qr_gait_kernel(int n, qrgpu_gait_desc D, float currentTime, int stop, int fresh, const float *__restrict__ g_contact,
                                                      float *__restrict__ st, float *__restrict__ g_out, float *__restrict__ g_fe)
 {
 #pragma clang fp contract(off)
@@ -499,7 +500,7 @@ __global__ void __launch_bounds__(64) qr_gait_kernel(int n, GaitDesc D, float cu
 // g_in [46][n] (include/qrgpu.h fh_in); rows 0-15 come from the gait kernel's arrays instead when those are given (legState and
 // allowSwitchLegState are rows 16-23 of gait_state, normalizedPhase / swingTimeRemaining rows 4-7 / 20-23 of gait_out).
 // Writes rows 0-3 of swing_in for every leg, rows 4-7 and 24-35 for the swinging ones.
-__global__ void __launch_bounds__(64) qr_foothold_kernel(int n, FootholdDesc D, const float *__restrict__ g_in, const float *__restrict__ g_gait_state,
+__global__ void __launch_bounds__(64) qr_foothold_kernel(int n, qrgpu_foothold_desc D, const float *__restrict__ g_in, const float *__restrict__ g_gait_state,
                                                          const float *__restrict__ g_gait_out, float *__restrict__ g_swing)
 {
 #pragma clang fp contract(off)
@@ -809,7 +810,7 @@ __global__ void __launch_bounds__(64) qr_walk_gait_kernel(int n, WalkDesc D, flo
 // desiredSpeed[3], desiredTwistingSpeed, dR[9] (baseRInControlFrame, row-major: rows 22-30 of the ground kernel's output), quat_wxyz[4],
 // motor angles[12].  g_out [48][n], for the flagged legs: footTargetPosition[12] (base frame), footPositionInBaseFrame[12], joint angle
 // targets[12], joint velocity targets[12].
-__global__ void __launch_bounds__(64) qr_swing_velocity_kernel(int n, EstimatorDesc D, SwingVelDesc V, const float *__restrict__ g_in, float *__restrict__ g_out)
+__global__ void __launch_bounds__(64) qr_swing_velocity_kernel(int n, qrgpu_estimator_desc D, qrgpu_swing_velocity_desc V, const float *__restrict__ g_in, float *__restrict__ g_out)
 {
 #pragma clang fp contract(off)
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -828,7 +829,7 @@ __global__ void __launch_bounds__(64) qr_swing_velocity_kernel(int n, EstimatorD
 #pragma unroll
     for (int leg = 0; leg < 4; ++leg) {
         if (IN(leg) == 0.f) continue;
-        const float ho[3] = {V.hip_pos_com[3 * leg], V.hip_pos_com[3 * leg + 1], V.hip_pos_com[3 * leg + 2]};
+        const float ho[3] = {V.hip_position_com[3 * leg], V.hip_position_com[3 * leg + 1], V.hip_position_com[3 * leg + 2]};
         const float tw[3] = {-ho[1], ho[0], 0.f};
         float hv[3], hh[3], tgtv[3], u[3], tg[3];
 #pragma unroll

@@ -13,6 +13,7 @@
 // ============================================================================
 #include <hip/hip_runtime.h>
 #include "qr_device_types.h"
+#include "qr_kernels.h"
 
 namespace qrgpu {
 

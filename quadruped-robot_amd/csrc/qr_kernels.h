@@ -1,0 +1,77 @@
+// One prototype per __global__ kernel of libqrgpu.so, included by the host files that launch the kernels and by the kernel files that define
+// them: a kernel's signature is written here and at its definition, nowhere else.
+#pragma once
+#include "qr_device_types.h"
+
+namespace qrgpu {
+
+// qr_mpc_kernel.hip; the same kernels with the executed-arithmetic counters compiled in: qr_mpc_kernel_fl.hip.
+// The launch bounds of the templates are part of the prototype: an instantiation takes them from the FIRST declaration it sees, and one
+// declared here without them was compiled for 1024 threads and no register budget (the definitions use the same two macros).
+// The macros name the template parameters: wherever they expand, those must be spelled MAXB, BIG, LIST, NTHR and MINW.
+#define QR_MAIN_WAVES_PER_SIMD 3     // register budget of the h <= 11 main pass: 3 workgroups per CU (168 VGPRs); the LDS allotment decides how many run
+#define QR_MPC_KERNEL_BOUNDS  __launch_bounds__(NTHR, (MINW ? MINW : ((MAXB <= 4 && !LIST && !BIG) ? (NTHR >= 384 ? 4 : QR_MAIN_WAVES_PER_SIMD) : (NTHR >= 512 ? 2 : 1))))
+#define QR_MPC_PERSIST_BOUNDS __launch_bounds__(NTHR, (MINW ? MINW : ((MAXB <= 4 && !BIG) ? (NTHR >= 384 ? 4 : QR_MAIN_WAVES_PER_SIMD) : (NTHR >= 512 ? 2 : 1))))
+template <int MAXB, bool BIG, bool LIST, int NTHR, int MINW = 0, bool H16 = (MAXB > 4)> __global__ QR_MPC_KERNEL_BOUNDS void qr_mpc_kernel(MpcLaunch P, MpcIO io);
+template <int MAXB, bool BIG, bool LIST, int NTHR, int MINW = 0, bool H16 = (MAXB > 4)> __global__ QR_MPC_KERNEL_BOUNDS void qr_mpc_kernel_fl(MpcLaunch P, MpcIO io);
+template <int MAXB, bool BIG, int NTHR, int MINW = 0> __global__ QR_MPC_PERSIST_BOUNDS void qr_mpc_persist_kernel(MpcLaunch P, MpcIO io);
+#define QR_MPC_INSTANCES(K)                                  \
+    extern template __global__ void K<2, false, false, 512>(MpcLaunch, MpcIO);          \
+    extern template __global__ void K<4, true, true, 256>(MpcLaunch, MpcIO);            \
+    extern template __global__ void K<2, true, false, 512>(MpcLaunch, MpcIO);           \
+    extern template __global__ void K<2, true, false, 512, 4, true>(MpcLaunch, MpcIO);  \
+    extern template __global__ void K<5, true, false, 512>(MpcLaunch, MpcIO);           \
+    extern template __global__ void K<9, true, true, 256>(MpcLaunch, MpcIO);
+QR_MPC_INSTANCES(qr_mpc_kernel)
+QR_MPC_INSTANCES(qr_mpc_kernel_fl)
+#undef QR_MPC_INSTANCES
+extern template __global__ void qr_mpc_kernel<4, true, true, 256, 2, true>(MpcLaunch, MpcIO);
+extern template __global__ void qr_mpc_persist_kernel<2, false, 512>(MpcLaunch, MpcIO);
+extern template __global__ void qr_mpc_persist_kernel<5, true, 512>(MpcLaunch, MpcIO);
+__global__ void qr_lpt_order_kernel(int n, const int *cost, int *order, const int *ftime, int *wbc_order);
+__global__ void qr_gate_kernel(int *counter, int expected_total, long long max_ticks, int *timed_out, int timed_out_value, int *bump);
+__global__ void qr_gate2_kernel(int *c0, int e0, int *c1, int e1, long long max_ticks, long long *stamp);
+__global__ void qr_join_kernel(int *counter, int expected_total, long long max_ticks, int *timed_out, int *g0, int e0, int *g1, int e1, int *tick_done,
+                               int *lane_done, int lane_expect, long long *dbg);
+__global__ void qr_probe_wait_kernel(int *flag, int *out, long long max_ticks, int token);
+__global__ void qr_probe_set_kernel(int *flag, int token);
+__global__ void qr_selftest_kernel(double *out);
+
+// qr_wbc_kernel.hip; with the inspection outputs and cycle stamps compiled in: qr_wbc_kernel_dbg.hip
+__global__ void qr_wbc_kernel(int n, const WbcConst *types, const int *type_id, const float *g_state, const float *g_cmd,
+                              float *g_prev, float *g_tau, float *g_qdes, int *g_status, float *g_dbg, int merge_tau, int status_or, long long *dbgT,
+                              const float *g_fr, int type_ready, int epilogue, float *g_qp, WbcPipe pipe);
+__global__ void qr_wbc_kernel_dbg(int n, const WbcConst *types, const int *type_id, const float *g_state, const float *g_cmd,
+                                  float *g_prev, float *g_tau, float *g_qdes, int *g_status, float *g_dbg, int merge_tau, int status_or, long long *dbgT,
+                                  const float *g_fr, int type_ready, int epilogue, float *g_qp, WbcPipe pipe);
+
+// qr_frontend_kernel.hip, qr_vmc_kernel.hip
+__global__ void qr_frontend_kernel(int n, int horizon, int numHorizonL, float dt, float dtMPC, const float *fin, float *fst, float *g_traj,
+                                   float *g_gait, float *g_cmd, int *g_updated);
+__global__ void qr_vmc_kernel(VmcLaunch P, const int *type_id, const float *g_in, const float *g_q, float *g_force, float *g_tau, int *g_status);
+
+// qr_estimator_kernel.hip
+__global__ void qr_estimator_kernel(int n, qrgpu_estimator_desc D, const float *g_in, const unsigned *g_tick, double *st, float *g_out);
+__global__ void qr_pack_state_kernel(int n, float c0, float c1, float c2, const float *g_in, const float *g_est, const float *g_rpy, float *g_mpc, float *g_fb);
+__global__ void qr_swing_kernel(int n, qrgpu_estimator_desc D, const float *g_in, float *g_cmd, float *g_tgt_world, float *g_qdes);
+__global__ void qr_gait_kernel(int n, qrgpu_gait_desc D, float currentTime, int stop, int fresh, const float *g_contact, float *st, float *g_out, float *g_fe);
+__global__ void qr_foothold_kernel(int n, qrgpu_foothold_desc D, const float *g_in, const float *g_gait_state, const float *g_gait_out, float *g_swing);
+__global__ void qr_ground_kernel(int n, int fresh, const float *g_in, double *g_st, float *g_out, float *g_est_in);
+__global__ void qr_walk_gait_kernel(int n, WalkDesc D, float currentTime, int stop, int fresh, const float *g_contact, float *st, float *g_out, float *g_ratio,
+                                    float *g_vmc_in);
+__global__ void qr_swing_velocity_kernel(int n, qrgpu_estimator_desc D, qrgpu_swing_velocity_desc V, const float *g_in, float *g_out);
+
+// qr_swing_modes_kernel.hip, qr_stance_kernel.hip, qr_pose_plan_kernel.hip
+__global__ void qr_swing_update_kernel(int n, qrgpu_swing_mode_desc M, int reset, int stop, const float *g_est_in, const float *g_est_out, const float *g_gait_out,
+                                       float *g_st, float *g_swing_in, float *g_swing_vel_in, float *g_fe_in, int *g_flags);
+__global__ void qr_swing_action_kernel(int n, qrgpu_swing_mode_desc M, qrgpu_estimator_desc D, int stop, const float *g_est_in, const float *g_est_out,
+                                       const float *g_gait_out, const float *g_gait_state, float *g_st, float *g_out, int *g_flags);
+__global__ void qr_stance_update_kernel(int n, qrgpu_stance_desc S, float current_time, int stop, int reset, const float *g_est_in, const float *g_est_out,
+                                        const float *g_ground, const float *g_rpy, const float *g_gait_out, const float *g_gait_state, const float *g_cmd,
+                                        float *g_st, float *g_vmc_in, float *g_ratio, float *g_out);
+__global__ void qr_stance_command_kernel(int n, qrgpu_stance_desc S, int stop, const float *g_vmc_in, const float *g_stance_out, const float *g_tau,
+                                         const float *g_swing_q, const float *g_swing_flag, float *g_cmd);
+__global__ void qr_pose_plan_kernel(int n, qrgpu_pose_plan_desc D, int event, const int *g_event, int reset, const float *g_est_in, const float *g_est_out,
+                                    const float *g_ground, const float *g_rpy, const float *g_walk, float *g_state, float *g_cmd, float *g_out, int *g_flags);
+
+}  // namespace qrgpu

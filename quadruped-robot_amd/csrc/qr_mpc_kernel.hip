@@ -34,6 +34,7 @@
 #include <type_traits>
 #include "qr_device_types.h"
 #include "qr_wave_helpers.h"
+#include "qr_kernels.h"
 
 namespace qrgpu {
 
@@ -41,7 +42,7 @@ namespace qrgpu {
 // launch, QRGPU_WBC_ORDER=1, needs them too): compiled in only with -DQR_TIMELINE (QRGPU_EXTRA_FLAGS).  With the pointers merely null at run
 // time the main pass was 1.5-2 % slower (1.373 against 1.346 ms at 8192 robots, A/B on one box).
 #ifdef QR_TIMELINE
-#define QR_TRACE(rid_, bits_) do { if (P.tl && P.solved) atomicOr((unsigned long long *)(P.tl + 768 + 32768 + 4096 + 64 + (P.solved_epoch & 15u) * 1024 + ((rid_) & 1023)), (unsigned long long)(bits_) | ((unsigned long long)(P.solved_epoch & 15u) << 32) | (1ull << 40)); } while (0)
+#define QR_TRACE(rid_, bits_) do { if (P.tl && P.solved) atomicOr((unsigned long long *)(P.tl + QR_TL_TRACE + (P.solved_epoch & 15u) * 1024 + ((rid_) & 1023)), (unsigned long long)(bits_) | ((unsigned long long)(P.solved_epoch & 15u) << 32) | (1ull << 40)); } while (0)
 #define QR_P_TL P.tl
 #define QR_P_FTIME P.ftime
 #else
@@ -56,7 +57,6 @@ namespace qrgpu {
 // refresh the stress run is the same with either form: 21 overflow flags at twice the ranges, none inside them, largest count 202 / 204.)
 #define QR_RCP_PIVOT fast_rcp1
 #define QR_REFRESH_EVERY 100         // a solve still going after this many working-set changes gets S^-1 rebuilt from its working set, and again every so many
-#define QR_MAIN_WAVES_PER_SIMD 3     // register budget of the h <= 11 main pass: 3 workgroups per CU (168 VGPRs); the LDS allotment decides how many run
 // The executed-arithmetic counters (qrgpu_enable_flop_count) cost the main pass four live fp64 accumulators and 2.4 % of its time even when the
 // pointer is null (0.2242 -> 0.2189 ms with them compiled out), so the kernels exist twice: this file compiles them without the counters,
 // qr_mpc_kernel_fl.hip includes it with QR_FLOPS_BUILD and gets the same kernels under the name qr_mpc_kernel_fl with the counters in;
@@ -268,17 +268,6 @@ __global__ void __launch_bounds__(256) qr_lpt_order_kernel(int n, const int *__r
 }
 #endif
 
-// Global-memory arguments of one MPC launch (SoA, [field][robot]; see include/qrgpu.h)
-struct MpcIO {
-    const int *type_id;
-    const float *g_state, *g_traj, *g_gait, *g_q;
-    float *g_force, *g_tau;
-    int *g_status;
-    float *dbgH, *dbgG, *g_force_wbc;
-    int force_stride;
-    long long *dbgT;
-};
-
 // One robot's MPC tick by one workgroup of NTHR threads.  MAXB: 3x3 blocks a thread keeps in registers during the sweep (MAXB * NTHR >= number of
 // stance leg-step pairs).  BIG: working-set positions 64 .. 95 live in a second set of per-lane registers.  Every wave returns from here
 // (the workers at their exit command, wave 0 after the outputs), so a workgroup may solve several robots in a row (list mode below).
@@ -302,9 +291,9 @@ __device__ __forceinline__ void mpc_solve_robot(const MpcLaunch &P, const MpcIO 
     // a type id outside the table, or one that was never set up, would read garbage (mass 0 => 1/mass = inf): the robot is solved with the
     // first valid type's constants and carries QRGPU_ST_BAD_TYPE
     int tyid = io.type_id ? io.type_id[rid] : 0;
-    const bool bad_type = tyid < 0 || tyid >= QR_MAX_TYPES || !((P.type_ready >> (tyid & (QR_MAX_TYPES - 1))) & 1);
-    if (bad_type) tyid = __builtin_ctz(P.type_ready | (1 << QR_MAX_TYPES));
-    const MpcType &C = P.type[tyid & (QR_MAX_TYPES - 1)];
+    const bool bad_type = tyid < 0 || tyid >= QRGPU_MAX_TYPES || !((P.type_ready >> (tyid & (QRGPU_MAX_TYPES - 1))) & 1);
+    if (bad_type) tyid = __builtin_ctz(P.type_ready | (1 << QRGPU_MAX_TYPES));
+    const MpcType &C = P.type[tyid & (QRGPU_MAX_TYPES - 1)];
     const int h = P.horizon;
     const int NV = 12 * h, NL = 4 * h;
 
@@ -506,14 +495,14 @@ __device__ __forceinline__ void mpc_solve_robot(const MpcLaunch &P, const MpcIO 
         if (qW > 64) qW = 64;
         if (P.no_wcache == 1) qW = 0;
     }
-    int st = bad_type ? QRGPU_ST_BAD_TYPE_D : 0;
-    if (npairs > MAXB * NTHR) { st |= QRGPU_ST_MPC_OVERFLOW_D; }      // cannot happen: the host picks MAXB from the horizon
+    int st = bad_type ? QRGPU_ST_BAD_TYPE : 0;
+    if (npairs > MAXB * NTHR) { st |= QRGPU_ST_MPC_OVERFLOW; }      // cannot happen: the host picks MAXB from the horizon
     if (!spilled && qcap < (ns < 24 ? ns : 24)) {
         // this launch's LDS allotment cannot hold the inverse Hessian of this robot plus a 24-row S^-1 (the main pass at three workgroups
         // per CU and an all-stance robot): nothing is computed here, the robot goes to the list pass at once -- and, through the `big`
         // bit, onto the planned list of the next call
         if (tid == 0) {
-            if (io.g_status) st_xt(io.g_status + rid, st | QRGPU_ST_MPC_OVERFLOW_D, P.main_done != nullptr);      // (its rescuer may already be running: not behind that one's word)
+            if (io.g_status) st_xt(io.g_status + rid, st | QRGPU_ST_MPC_OVERFLOW, P.main_done != nullptr);      // (its rescuer may already be running: not behind that one's word)
             if (P.main_done) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             QR_TRACE(rid, 4 | (P.rescue_mode << 8));
             if (P.rescue_list && !P.rescue_mode) st_xt(P.rescue_list + atomicAdd(P.rescue_count + P.rescue_parity, 1), rid, P.solved != nullptr);
@@ -606,7 +595,7 @@ __device__ __forceinline__ void mpc_solve_robot(const MpcLaunch &P, const MpcIO 
     if ((long long)NT * NT * 1024 > (long long)P.lds_bytes - (long long)((Mb - smem) * 8)) {
         // (h = 11 all stance in the main pass's half-CU allotment: to the list pass, like a robot whose S^-1 does not fit)
         if (tid == 0) {
-            if (io.g_status) st_xt(io.g_status + rid, st | QRGPU_ST_MPC_OVERFLOW_D, P.main_done != nullptr);      // (its rescuer may already be running: not behind that one's word)
+            if (io.g_status) st_xt(io.g_status + rid, st | QRGPU_ST_MPC_OVERFLOW, P.main_done != nullptr);      // (its rescuer may already be running: not behind that one's word)
             if (P.main_done) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             QR_TRACE(rid, 4 | (P.rescue_mode << 8));
             if (P.rescue_list && !P.rescue_mode) st_xt(P.rescue_list + atomicAdd(P.rescue_count + P.rescue_parity, 1), rid, P.solved != nullptr);
@@ -962,7 +951,7 @@ __device__ __forceinline__ void mpc_solve_robot(const MpcLaunch &P, const MpcIO 
     // phases 0-3 may run on more than four waves (NTHR / 64: one block of a trotting robot's Hessian per thread); the active set is a
     // four-wave protocol, so the others are done here (a wave that has ended no longer counts at the workgroup's barriers)
     if (NTHR > QR_AS_THREADS && tid >= QR_AS_THREADS) { if (PERSIST) QR_IDLE(); return; }
-    if (sMisc[1]) st |= QRGPU_ST_MPC_NOTSPD_D;
+    if (sMisc[1]) st |= QRGPU_ST_MPC_NOTSPD;
     QR_TS(3);
     if (QR_PFLOPS) {
         double steps = 0.0;                              // chain x horizon-step pairs: two chains per off-diagonal tile, one per diagonal tile
@@ -1332,12 +1321,12 @@ __device__ __forceinline__ void mpc_solve_robot(const MpcLaunch &P, const MpcIO 
             const long long c0_ = clock64();
             const long long t0 = wall_clock64();
             while (!qr_epoch_reached(__hip_atomic_load(P.prev_solved + rid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), P.prev_epoch)) {
-                if (wall_clock64() - t0 > P.xtick_wait) { st |= QRGPU_ST_PIPE_TIMEOUT_D; warm_ok = false; break; }
+                if (wall_clock64() - t0 > P.xtick_wait) { st |= QRGPU_ST_PIPE_TIMEOUT; warm_ok = false; break; }
                 __builtin_amdgcn_s_sleep(32);
             }
             t_waited = clock64() - c0_;
             if (lane == 0) QR_TRACE(rid, 32);
-            if (lane == 0 && QR_P_TL) QR_P_TL[768 + 1024 * 16 + (P.solved_epoch & 15u) * 1024 + (rid & 1023)] = ((wall_clock64() - t0) << 8) | (long long)(P.rescue_mode & 7) | (warm_ok ? 0 : 8);
+            if (lane == 0 && QR_P_TL) QR_P_TL[QR_TL_SOLVE_WAITS + (P.solved_epoch & 15u) * 1024 + (rid & 1023)] = ((wall_clock64() - t0) << 8) | (long long)(P.rescue_mode & 7) | (warm_ok ? 0 : 8);
         }
         auto warm_ld = [&](const unsigned char *p_) -> unsigned { return xtick ? (unsigned)__hip_atomic_load(p_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : (unsigned)*p_; };
         if (warm && warm_ok && warm_ld(warm + QR_WARM_STRIDE - 1) == (unsigned)(unsigned char)h) {
@@ -1410,7 +1399,7 @@ __device__ __forceinline__ void mpc_solve_robot(const MpcLaunch &P, const MpcIO 
                 }
                 fastz = qW > 0 && q <= qW;
                 for (;;) {
-                    if (++iter > maxit) { st |= QRGPU_ST_MPC_MAXITER_D; done = true; break; }
+                    if (++iter > maxit) { st |= QRGPU_ST_MPC_MAXITER; done = true; break; }
                     q = __builtin_amdgcn_readfirstlane(q);
                     const bool hi = BIG && q > 64;
                     const double dq = (lane < q) ? slack_at_x0(ck, ct) : 0.0;
@@ -1525,7 +1514,7 @@ __device__ __forceinline__ void mpc_solve_robot(const MpcLaunch &P, const MpcIO 
                     // set as it stands, re-solve on that set, restore dual feasibility and carry on; only a solve that fails the check
                     // after two such repairs keeps the flag
                     if (refac < 2 && q > 0) { ++refac; need_rebuild = true; continue; }
-                    st |= QRGPU_ST_MPC_INFEAS_D;
+                    st |= QRGPU_ST_MPC_INFEAS;
                 }
                 break;
             }
@@ -1542,7 +1531,7 @@ __device__ __forceinline__ void mpc_solve_robot(const MpcLaunch &P, const MpcIO 
             CS_STAMP(0);
             for (;;) {
                 q = __builtin_amdgcn_readfirstlane(q);
-                if (++iter > maxit) { st |= QRGPU_ST_MPC_MAXITER_D; done = true; break; }
+                if (++iter > maxit) { st |= QRGPU_ST_MPC_MAXITER; done = true; break; }
                 double w0, w1, w2_;
                 {
                     Blk B; load_block(Mb, kme, kp, B);
@@ -1605,7 +1594,7 @@ __device__ __forceinline__ void mpc_solve_robot(const MpcLaunch &P, const MpcIO 
                 QR_SYNC();                          // B3
                 CS_STAMP(5);
                 if (degenerate) { if (lane == kp) xmask |= 1u << tp; break; }
-                if (over) { st |= QRGPU_ST_MPC_OVERFLOW_D; done = true; break; }      // (main pass: the robot goes on the rescue list below)
+                if (over) { st |= QRGPU_ST_MPC_OVERFLOW; done = true; break; }      // (main pass: the robot goes on the rescue list below)
                 if (have_z) {
                     const double z0 = w0 - ((xz[NV + 3 * kme] + xz[2 * NV + 3 * kme]) + xz[3 * NV + 3 * kme]);
                     const double z1 = w1 - ((xz[NV + 3 * kme + 1] + xz[2 * NV + 3 * kme + 1]) + xz[3 * NV + 3 * kme + 1]);
@@ -1658,7 +1647,7 @@ __device__ __forceinline__ void mpc_solve_robot(const MpcLaunch &P, const MpcIO 
         if (lane == 0) { sCtl[0] = CMD_EXIT; sMisc[15] = nbar + 1; }      // workers leave at their next X1 (and the parked waves of a persistent workgroup with them)
         QR_SYNC();
         QR_TS(5);
-        const bool to_rescue = (st & QRGPU_ST_MPC_OVERFLOW_D) && P.rescue_list && !P.rescue_mode;
+        const bool to_rescue = (st & QRGPU_ST_MPC_OVERFLOW) && P.rescue_list && !P.rescue_mode;
         if (warm && !to_rescue) {                         // (a robot on its way to the list pass keeps last tick's guess for that pass)
             // this tick's final working set, by original leg-step, for the next tick of this robot slot (only a converged solve is worth it)
             const bool good = (st & 0xff) == 0;
@@ -1726,10 +1715,10 @@ __device__ __forceinline__ void mpc_solve_robot(const MpcLaunch &P, const MpcIO 
                     if (seen == cur) break;
                     cur = seen;
                 }
-                if (late && io.g_status) __hip_atomic_fetch_or(io.g_status + rid, QRGPU_ST_PIPE_TIMEOUT_D, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (late && io.g_status) __hip_atomic_fetch_or(io.g_status + rid, QRGPU_ST_PIPE_TIMEOUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             if (lane == 0 && QR_P_FTIME) QR_P_FTIME[rid] = (int)wall_clock64();
-            if (lane == 0 && QR_P_TL) atomicMax(QR_P_TL + (P.done_epoch & 63u) * 8 + 2, wall_clock64());
+            if (lane == 0 && QR_P_TL) atomicMax(QR_P_TL + QR_TL_TICKS + (P.done_epoch & 63u) * 8 + 2, wall_clock64());
         }
         if (lane == 0 && QR_PFLOPS) { double *fo = QR_PFLOPS + (size_t)rid * 4; fo[0] = fl_v32; fo[1] = fl_m32; fo[2] = fl_sw; fo[3] = fl_as; }
         if (lane == 0 && P.cost) {
@@ -1752,7 +1741,7 @@ __device__ __forceinline__ void mpc_solve_robot(const MpcLaunch &P, const MpcIO 
                 int qcm = 0;
                 if (remm > 0) { qcm = (int)((__builtin_sqrt(8.0 * (double)remm + 1.0) - 1.0) * 0.5); while (tri(qcm) > remm) --qcm; }
                 if (qcm > 64) qcm = 64;
-                big = ((st & QRGPU_ST_MPC_OVERFLOW_D) || q + P.big_margin >= qcm || (P.big_nls > 0 && nls >= P.big_nls)
+                big = ((st & QRGPU_ST_MPC_OVERFLOW) || q + P.big_margin >= qcm || (P.big_nls > 0 && nls >= P.big_nls)
                        || (P.big_cost > 0 && cfine >= (P.rescue_mode == 0 ? P.big_cost : P.big_cost_stay))) ? 1 : 0;
             }
             if (P.planned_done || P.solved) __hip_atomic_store(P.cost + rid, (c > 255 ? 255 : (int)c) | (big << 8) | (cfine << 16), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1764,7 +1753,7 @@ __device__ __forceinline__ void mpc_solve_robot(const MpcLaunch &P, const MpcIO 
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             if (lane == 0) qr_epoch_raise(P.solved + rid, P.solved_epoch);
         }
-        if (lane == 0 && QR_P_TL && P.solved) QR_P_TL[768 + (P.solved_epoch & 15u) * 1024 + (rid & 1023)] = (wall_clock64() << 8) | (long long)(P.rescue_mode & 7) | (to_rescue ? 8 : 0) | ((long long)(P.solved_epoch & 15u) << 4);
+        if (lane == 0 && QR_P_TL && P.solved) QR_P_TL[QR_TL_SOLVES + (P.solved_epoch & 15u) * 1024 + (rid & 1023)] = (wall_clock64() << 8) | (long long)(P.rescue_mode & 7) | (to_rescue ? 8 : 0) | ((long long)(P.solved_epoch & 15u) << 4);
         QR_TS(6);
         if (lane == 0 && QR_DBGT) QR_DBGT[(size_t)rid * 16 + 13] = wall_clock64();
         if (lane == 0 && QR_DBGT) { QR_DBGT[(size_t)rid * 16 + 7] = ns; QR_DBGT[(size_t)rid * 16 + 14] = q; }
@@ -1783,15 +1772,15 @@ __device__ __forceinline__ void mpc_solve_robot(const MpcLaunch &P, const MpcIO 
 //                 their 256 VGPRs under the default of one wave per SIMD, so two of their workgroups never share a CU; MINW = 2 is the build that can.
 //   H16: the h > 11 form of the solve (no early copy of the torque map's Jacobians in LDS, S^-1 may live in the global scratch) -- every MAXB > 4
 //                 variant, and the eight-wave two-blocks-per-thread kernel when it runs a trotting h = 16 robot on half a CU (MINW = 4)
-template <int MAXB, bool BIG, bool LIST, int NTHR, int MINW = 0, bool H16 = (MAXB > 4)>
-__global__ __launch_bounds__(NTHR, (MINW ? MINW : ((MAXB <= 4 && !LIST && !BIG) ? (NTHR >= 384 ? 4 : QR_MAIN_WAVES_PER_SIMD) : (NTHR >= 512 ? 2 : 1))))
+template <int MAXB, bool BIG, bool LIST, int NTHR, int MINW, bool H16>      // (defaults and launch bounds: qr_kernels.h)
+__global__ QR_MPC_KERNEL_BOUNDS
 void qr_mpc_kernel(MpcLaunch P, MpcIO io)
 {
     extern __shared__ double smem[];
     if (P.started && threadIdx.x == 0) atomicAdd(P.started, 1);        // (planned list launches: see qr_gate_kernel)
     if (!LIST && P.main_started && P.rescue_mode == 0 && threadIdx.x == 0) atomicAdd(P.main_started, 1);     // (pipelined tick: the WBC launch's gate)
     if (QR_P_TL && threadIdx.x == 0) {
-        long long *tl = QR_P_TL + (P.done_epoch & 63u) * 8;
+        long long *tl = QR_P_TL + QR_TL_TICKS + (P.done_epoch & 63u) * 8;
         const long long t = wall_clock64();
         if (!LIST && P.rescue_mode == 0) { atomicMin(tl + 0, t); atomicMax(tl + 1, t); }
         if (LIST && P.rescue_mode == 1) atomicMin(tl + 5, t);
@@ -1828,7 +1817,7 @@ void qr_mpc_kernel(MpcLaunch P, MpcIO io)
                     __threadfence();
                     if (atomicAdd(P.pre_count + 2, 1) == 7) {
                         P.pre_hint[P.rescue_parity ^ 1] = atomicAdd(P.pre_count + (P.rescue_parity ^ 1), 0);
-                        if (QR_P_TL) QR_P_TL[768 + 32768 + 4096 + (P.done_epoch & 63u)] = (long long)P.pre_hint[P.rescue_parity ^ 1] | ((long long)(P.rescue_parity ^ 1) << 16) | (1ll << 40);
+                        if (QR_P_TL) QR_P_TL[QR_TL_PLAN_LEFT + (P.done_epoch & 63u)] = (long long)P.pre_hint[P.rescue_parity ^ 1] | ((long long)(P.rescue_parity ^ 1) << 16) | (1ll << 40);
                         __threadfence_system();
                     }
                 }
@@ -1842,7 +1831,7 @@ void qr_mpc_kernel(MpcLaunch P, MpcIO io)
             mpc_solve_robot<MAXB, BIG, NTHR, false, H16>(P, io, ld_xt(list + e, P.solved != nullptr), smem);
             __syncthreads();                           // every wave is out of the solve before the LDS is carved again
         }
-        if (QR_P_TL && threadIdx.x == 0 && P.rescue_mode == 1) atomicMax(QR_P_TL + (P.done_epoch & 63u) * 8 + 6, wall_clock64());
+        if (QR_P_TL && threadIdx.x == 0 && P.rescue_mode == 1) atomicMax(QR_P_TL + QR_TL_TICKS + (P.done_epoch & 63u) * 8 + 6, wall_clock64());
     } else {
         if (P.rescue_mode == 3) {
             // planned list, one robot per workgroup (so that the waves beyond the active set's four may leave after the sweep, which a workgroup
@@ -1851,9 +1840,9 @@ void qr_mpc_kernel(MpcLaunch P, MpcIO io)
             // launch, and workgroups past the end of a shorter list leave at once.
             // (every workgroup of this launch tells the trailing launch when it is done -- planned_done -- whichever way it leaves)
             // (timeline build: first start / last end of the planned launch's workgroups, behind the gate's two slots of the epoch's extra row)
-            if (QR_P_TL && threadIdx.x == 0) atomicMin(QR_P_TL + 640 + (P.done_epoch & 63u) * 2, wall_clock64());
+            if (QR_P_TL && threadIdx.x == 0) atomicMin(QR_P_TL + QR_TL_PLANNED + (P.done_epoch & 63u) * 2, wall_clock64());
             auto tell_done = [&]() {
-                if (QR_P_TL && threadIdx.x == 0) atomicMax(QR_P_TL + 640 + (P.done_epoch & 63u) * 2 + 1, wall_clock64());
+                if (QR_P_TL && threadIdx.x == 0) atomicMax(QR_P_TL + QR_TL_PLANNED + (P.done_epoch & 63u) * 2 + 1, wall_clock64());
                 if (P.planned_done && threadIdx.x < 64) {
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                     if (threadIdx.x == 0) __hip_atomic_fetch_add(P.planned_done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1861,7 +1850,7 @@ void qr_mpc_kernel(MpcLaunch P, MpcIO io)
             };
             if (P.plan_abort && *P.plan_abort == P.plan_epoch) { tell_done(); return; }       // its gate gave up: the main pass solves everybody (below)
             int cnt = ld_xt(P.pre_count + P.rescue_parity, P.solved != nullptr);
-            if (QR_P_TL && threadIdx.x == 0) QR_P_TL[768 + 32768 + (P.done_epoch & 63u) * 64 + (blockIdx.x & 63)] = (long long)cnt | ((long long)P.rescue_parity << 16) | ((long long)gridDim.x << 20) | ((long long)P.planned_stride << 32) | (1ll << 40);
+            if (QR_P_TL && threadIdx.x == 0) QR_P_TL[QR_TL_PLANS + (P.done_epoch & 63u) * 64 + (blockIdx.x & 63)] = (long long)cnt | ((long long)P.rescue_parity << 16) | ((long long)gridDim.x << 20) | ((long long)P.planned_stride << 32) | (1ll << 40);
             cnt = cnt < P.n ? cnt : P.n;
             if constexpr (MAXB == 5) {
                 // (QRGPU_H16_TWO: a tenth of a mixed h = 16 batch is listed -- more robots than the launch may take CUs.  The workgroup keeps its CU
@@ -1980,13 +1969,13 @@ void qr_mpc_kernel(MpcLaunch P, MpcIO io)
 #ifndef QR_FLOPS_BUILD
 // Persistent main pass (MpcLaunch::persist): one workgroup per resident slot; robots come off the queue of the workgroup's own XCD (slot
 // order of its chunk = the longest-first order), then off the others'; every robot taken counts for the WBC launch's gate.
-template <int MAXB, bool BIG, int NTHR, int MINW = 0>
-__global__ __launch_bounds__(NTHR, (MINW ? MINW : ((MAXB <= 4 && !BIG) ? (NTHR >= 384 ? 4 : QR_MAIN_WAVES_PER_SIMD) : (NTHR >= 512 ? 2 : 1))))
+template <int MAXB, bool BIG, int NTHR, int MINW>      // (default and launch bounds: qr_kernels.h)
+__global__ QR_MPC_PERSIST_BOUNDS
 void qr_mpc_persist_kernel(MpcLaunch P, MpcIO io)
 {
     extern __shared__ double smem[];
     volatile int *sNext = (volatile int *)smem;        // (the head of the dynamic LDS, dead between two solves: a static word would push the second workgroup off the CU)
-    if (QR_P_TL && threadIdx.x == 0) atomicMin(QR_P_TL + (P.done_epoch & 63u) * 8, wall_clock64());
+    if (QR_P_TL && threadIdx.x == 0) atomicMin(QR_P_TL + QR_TL_TICKS + (P.done_epoch & 63u) * 8, wall_clock64());
     if (blockIdx.x == 0 && threadIdx.x == 0) {         // the next call's counters
         if (P.rescue_count) st_xt(P.rescue_count + (P.rescue_parity ^ 1), 0, P.solved != nullptr);
         if (P.pre_count) { st_xt(P.pre_count + (P.rescue_parity ^ 1), 0, P.solved != nullptr); st_xt(P.pre_count + 2, 0, P.solved != nullptr); }
@@ -2007,7 +1996,7 @@ void qr_mpc_persist_kernel(MpcLaunch P, MpcIO io)
                     const int r = P.order ? ld_xt(P.order + lo + k, P.main_done != nullptr) : lo + k;
                     if (P.skip && ld_xt(P.skip + r, P.main_done != nullptr) && !(P.plan_abort && *P.plan_abort == P.plan_epoch)) continue;         // solved by the planned list launch, beside this one
                     got = r;
-                    if (QR_P_TL) atomicMax(QR_P_TL + (P.done_epoch & 63u) * 8 + 1, wall_clock64());
+                    if (QR_P_TL) atomicMax(QR_P_TL + QR_TL_TICKS + (P.done_epoch & 63u) * 8 + 1, wall_clock64());
                     break;
                 }
             }
@@ -2045,7 +2034,7 @@ template __global__ void qr_mpc_kernel<2, true, false, 512>(MpcLaunch, MpcIO);  
 __global__ void qr_gate_kernel(int *counter, int expected_total, long long max_ticks, int *timed_out, int timed_out_value, int *bump)
 {
     if (threadIdx.x != 0) return;
-    if (bump) __hip_atomic_fetch_add(bump, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // (the "go" of the planned launch's own gate: see qrgpu_api.hip)
+    if (bump) __hip_atomic_fetch_add(bump, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // (the "go" of the planned launch's own gate: see qrgpu_mpc.hip)
     const long long t0 = wall_clock64();
     for (;;) {
         if ((int)((unsigned)__hip_atomic_load(counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - (unsigned)expected_total) >= 0) return;

@@ -34,6 +34,7 @@
 #include <hip/hip_runtime.h>
 #include "qr_device_types.h"
 #include "qr_wave_helpers.h"
+#include "qr_kernels.h"
 
 namespace qrgpu {
 
@@ -183,8 +184,8 @@ PP_FN bool pp_add_constraint(PoseWork &W, int lane, int &iq, double &R_norm)
 }
 
 // solve_quadprog_test with n = 6, p = 0, m inequality rows.  In: W.Mf (fp32 hessF - hessGSum), W.gradF, W.gradG, W.Gv.  Out: W.x, W.u,
-// W.A, W.iq, W.qpflags (QR_PP_NOT_PD: the Cholesky would throw, nothing else is valid; QR_PP_INFEASIBLE: +inf was returned;
-// QR_PP_MAXITER: a bound the reference does not have).
+// W.A, W.iq, W.qpflags (QRGPU_PP_NOT_PD: the Cholesky would throw, nothing else is valid; QRGPU_PP_INFEASIBLE: +inf was returned;
+// QRGPU_PP_MAXITER: a bound the reference does not have).
 PP_FN void pp_solve_quadprog(PoseWork &W, int lane, int m)
 {
 #pragma clang fp contract(off)
@@ -211,11 +212,11 @@ PP_FN void pp_solve_quadprog(PoseWork &W, int lane, int m)
             }
             for (int k = i + 1; k < 6 && !bad; ++k) W.G[6 * i + k] = W.G[6 * k + i];
         }
-        W.qpflags = bad ? QR_PP_NOT_PD : 0;
+        W.qpflags = bad ? QRGPU_PP_NOT_PD : 0;
         W.iq = 0;
     }
     PP_SYNC();
-    if (W.qpflags & QR_PP_NOT_PD) return;
+    if (W.qpflags & QRGPU_PP_NOT_PD) return;
     // J = L^-T, row i by forward elimination of e_i (:143-151)
     PP_LANES(lane < 6) {
         double y[6];
@@ -296,7 +297,7 @@ PP_FN void pp_solve_quadprog(PoseWork &W, int lane, int m)
             PP_LANES(lane == 6) { W.u[iqc] = 0.0; W.A[iqc] = ipc; }
             PP_SYNC();
             for (;;) {                                                        // l2a
-                if (++guard > 200) { flags |= QR_PP_MAXITER | QR_PP_INFEASIBLE; done = true; break; }
+                if (++guard > 200) { flags |= QRGPU_PP_MAXITER | QRGPU_PP_INFEASIBLE; done = true; break; }
                 const int iqa = iq;
                 PP_LANES(lane < 6) {
                     double sum = 0.0;
@@ -330,21 +331,21 @@ PP_FN void pp_solve_quadprog(PoseWork &W, int lane, int m)
                 if (__builtin_fabs(zz) > DEPS) { t2 = -W.s[ip] / znp; if (t2 < 0) t2 = INF; }
                 else t2 = INF;
                 const double tmin = (t2 < t1) ? t2 : t1;                      // std::min(t1, t2)
-                if (tmin >= INF) { flags |= QR_PP_INFEASIBLE; done = true; break; }
+                if (tmin >= INF) { flags |= QRGPU_PP_INFEASIBLE; done = true; break; }
                 if (t2 >= INF) {                                              // step in dual space
                     PP_LANES(lane <= iqa) { if (lane < iqa) W.u[lane] -= tmin * W.r[lane]; else W.u[lane] += tmin; }
                     PP_SYNC();
-                    if (!pp_delete_constraint(W, lane, iq, l)) { flags |= QR_PP_MAXITER | QR_PP_INFEASIBLE; done = true; break; }
+                    if (!pp_delete_constraint(W, lane, iq, l)) { flags |= QRGPU_PP_MAXITER | QRGPU_PP_INFEASIBLE; done = true; break; }
                     continue;
                 }
                 PP_LANES(lane <= iqa) { if (lane < iqa) W.u[lane] -= tmin * W.r[lane]; else W.u[lane] += tmin; }
                 PP_LANES(lane >= 16 && lane < 22) W.x[lane - 16] += tmin * W.z[lane - 16];
                 PP_SYNC();
                 if (__builtin_fabs(tmin - t2) < DEPS) {                       // full step
-                    if (iq >= 6) { flags |= QR_PP_MAXITER | QR_PP_INFEASIBLE; done = true; break; }      // cannot happen: z = 0 with six rows
+                    if (iq >= 6) { flags |= QRGPU_PP_MAXITER | QRGPU_PP_INFEASIBLE; done = true; break; }      // cannot happen: z = 0 with six rows
                     if (!pp_add_constraint(W, lane, iq, R_norm)) {
                         excl |= 1u << ip;
-                        if (!pp_delete_constraint(W, lane, iq, ip)) { flags |= QR_PP_MAXITER | QR_PP_INFEASIBLE; done = true; break; }
+                        if (!pp_delete_constraint(W, lane, iq, ip)) { flags |= QRGPU_PP_MAXITER | QRGPU_PP_INFEASIBLE; done = true; break; }
                         const int iqn = iq;
                         PP_LANES(lane < iqn) { W.A[lane] = W.Aold[lane]; W.u[lane] = W.uold[lane]; }
                         PP_LANES(lane >= 16 && lane < 22) W.x[lane - 16] = W.xold[lane - 16];
@@ -354,7 +355,7 @@ PP_FN void pp_solve_quadprog(PoseWork &W, int lane, int m)
                     to_l1 = true;
                     break;
                 }
-                if (!pp_delete_constraint(W, lane, iq, l)) { flags |= QR_PP_MAXITER | QR_PP_INFEASIBLE; done = true; break; }
+                if (!pp_delete_constraint(W, lane, iq, l)) { flags |= QRGPU_PP_MAXITER | QRGPU_PP_INFEASIBLE; done = true; break; }
                 const int ipp = ip;                                           // partial step: s[ip] = CI x + ci0
                 PP_LANES(lane == 0) {
                     double sum = 0.0;
@@ -376,7 +377,7 @@ PP_FN void pp_solve_quadprog(PoseWork &W, int lane, int m)
 }  // namespace
 
 // One robot.  ev: 1 Update, 2 ResetBasePose.  Arrays are [row][n]; g_out may be null.
-PP_FN void pose_plan_robot(PoseWork &W, int lane, int rid, int n, const PosePlanDesc &D, int ev, int reset, const float *g_est_in, const float *g_est_out,
+PP_FN void pose_plan_robot(PoseWork &W, int lane, int rid, int n, const qrgpu_pose_plan_desc &D, int ev, int reset, const float *g_est_in, const float *g_est_out,
                            const float *g_ground, const float *g_rpy, const float *g_walk, float *g_state, float *g_cmd, float *g_out, int *g_flags)
 {
 #pragma clang fp contract(off)
@@ -404,7 +405,7 @@ PP_FN void pose_plan_robot(PoseWork &W, int lane, int rid, int n, const PosePlan
             const float my = ((W.rIF[1] + W.rIF[4]) + (W.rIF[7] + W.rIF[10])) / 4.f;
             const float dest[6] = {mx, my, D.body_height, 0.f, 0.f, 0.f};
             int fl = 0;
-            if (!(__builtin_isfinite(mx) && __builtin_isfinite(my))) fl = QR_PP_NAN;
+            if (!(__builtin_isfinite(mx) && __builtin_isfinite(my))) fl = QRGPU_PP_NAN;
             if (!fl) {
 #pragma unroll
                 for (int k = 0; k < 3; ++k) { ROW(g_cmd, 7 + k) = W.src[k]; ROW(g_cmd, 10 + k) = ROW(g_rpy, k); }
@@ -424,7 +425,7 @@ PP_FN void pose_plan_robot(PoseWork &W, int lane, int rid, int n, const PosePlan
         for (int k = 0; k < 4; ++k) fin = fin && __builtin_isfinite(W.q[k]);
 #pragma unroll
         for (int k = 0; k < 12; ++k) fin = fin && __builtin_isfinite(W.rIF[k]) && __builtin_isfinite(W.rBF[k]);
-        if (!fin) fl |= QR_PP_NAN;
+        if (!fin) fl |= QRGPU_PP_NAN;
         for (int c = 0; c < 4; ++c) {
             if (!W.contact[c]) continue;
             const float hb[3] = {W.rBH[3 * c], W.rBH[3 * c + 1], W.rBH[3 * c + 2]};
@@ -441,7 +442,7 @@ PP_FN void pose_plan_robot(PoseWork &W, int lane, int rid, int n, const PosePlan
             ++cnt;
         }
         int N = cnt;
-        if (cnt < 3) fl |= QR_PP_FEW_CONTACTS;
+        if (cnt < 3) fl |= QRGPU_PP_FEW_CONTACTS;
         else {
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
@@ -465,14 +466,14 @@ PP_FN void pose_plan_robot(PoseWork &W, int lane, int rid, int n, const PosePlan
                         for (int k = 0; k < 3; ++k) { W.vert[3 * v + k] = W.vert[3 * v + 3 + k]; W.g[3 * v + k] = W.g[3 * v + 3 + k]; }
                     }
                     N = 3;
-                    fl |= QR_PP_NONCONVEX;
+                    fl |= QRGPU_PP_NONCONVEX;
                 }
             }
             // Lambda.conservativeResize(3N): entries it does not have yet are uninitialised in the reference, 0.1 here
             int ls = reset ? 12 : (int)ROW(g_state, 12);
             ls = ls < 0 ? 0 : (ls > 12 ? 12 : ls);
             if (3 * N > ls) {
-                fl |= QR_PP_LAMBDA_GROWN;
+                fl |= QRGPU_PP_LAMBDA_GROWN;
                 for (int i = ls; i < 3 * N; ++i) W.lam[i] = 0.1f;
             }
         }
@@ -481,11 +482,11 @@ PP_FN void pose_plan_robot(PoseWork &W, int lane, int rid, int n, const PosePlan
     }
     PP_SYNC();
     const int N = W.N, m = 3 * N;
-    if (W.flags & (QR_PP_FEW_CONTACTS | QR_PP_NAN)) {
+    if (W.flags & (QRGPU_PP_FEW_CONTACTS | QRGPU_PP_NAN)) {
         PP_LANES(lane == 0) g_flags[rid] = W.flags;
         return;
     }
-    const int loops = D.loops < 1 ? 1 : (D.loops > QR_POSE_MAX_LOOPS ? QR_POSE_MAX_LOOPS : D.loops);
+    const int loops = D.loops < 1 ? 1 : (D.loops > QRGPU_POSE_MAX_LOOPS ? QRGPU_POSE_MAX_LOOPS : D.loops);
     for (int loop = 0; loop < loops; ++loop) {
         // ---- per-vertex blocks: ComputeGradientF / HessianF / G / GradientG / HessianG (:282-443)
         PP_LANES(lane < N) {
@@ -604,8 +605,8 @@ PP_FN void pose_plan_robot(PoseWork &W, int lane, int rid, int n, const PosePlan
         }
         PP_SYNC();
         pp_solve_quadprog(W, lane, m);
-        if (W.qpflags & QR_PP_NOT_PD) {
-            PP_LANES(lane == 0) g_flags[rid] = W.flags | QR_PP_NOT_PD;
+        if (W.qpflags & QRGPU_PP_NOT_PD) {
+            PP_LANES(lane == 0) g_flags[rid] = W.flags | QRGPU_PP_NOT_PD;
             return;
         }
         // ---- the step (:194-211)
@@ -661,7 +662,7 @@ PP_FN void pose_plan_robot(PoseWork &W, int lane, int rid, int n, const PosePlan
 #pragma unroll
         for (int k = 0; k < 6; ++k) fin = fin && __builtin_isfinite(dest[k]);
         int fl = W.flags;
-        if (!fin) fl |= QR_PP_NAN;
+        if (!fin) fl |= QRGPU_PP_NAN;
         else {
 #pragma unroll
             for (int k = 0; k < 3; ++k) { ROW(g_cmd, 7 + k) = W.src[k]; ROW(g_cmd, 10 + k) = ROW(g_rpy, k); ROW(g_state, 13 + k) = W.rIB[k]; }
@@ -687,7 +688,7 @@ PP_FN void pose_plan_robot(PoseWork &W, int lane, int rid, int n, const PosePlan
 #ifndef QR_POSE_PLAN_HOST
 // event: 0 none, 1 Update, 2 ResetBasePose, 3 Update where a leg has legState SWING and curLegState STANCE (qr_locomotion_controller.cpp:81-89);
 // g_event (may be null) overrides it per robot with 0 / 1 / 2.  reset: every robot's state is first put into the constructed state (:31-69).
-__global__ void __launch_bounds__(64) qr_pose_plan_kernel(int n, PosePlanDesc D, int event, const int *__restrict__ g_event, int reset,
+__global__ void __launch_bounds__(64) qr_pose_plan_kernel(int n, qrgpu_pose_plan_desc D, int event, const int *__restrict__ g_event, int reset,
                                                           const float *__restrict__ g_est_in, const float *__restrict__ g_est_out,
                                                           const float *__restrict__ g_ground, const float *__restrict__ g_rpy,
                                                           const float *__restrict__ g_walk, float *__restrict__ g_state, float *__restrict__ g_cmd,
@@ -705,7 +706,7 @@ __global__ void __launch_bounds__(64) qr_pose_plan_kernel(int n, PosePlanDesc D,
             if ((int)g_walk[(size_t)(12 + l) * Ns + rid] == 0 && (int)g_walk[(size_t)(16 + l) * Ns + rid] == 1) ev = 1;
     }
     if (ev != 1 && ev != 2) ev = 0;
-    if (reset && lane < QR_POSE_STATE_ROWS) {                                 // the constructor (:31-69)
+    if (reset && lane < QRGPU_POSE_STATE_ROWS) {                                 // the constructor (:31-69)
         float v = 0.f;
         if (lane < 12) v = 0.1f;
         else if (lane == 12) v = 12.f;

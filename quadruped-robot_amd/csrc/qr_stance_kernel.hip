@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include "qr_device_types.h"
 #include "qr_wave_helpers.h"
+#include "qr_kernels.h"
 
 namespace qrgpu {
 
@@ -45,7 +46,7 @@ __device__ __forceinline__ void com_vertex(const float p[3], const float pCw[3],
 // is in stance).  g_cmd [28][n]: stateDes(2), stateDes 6..8, stateDes 9..11, the pose planner's source[6], dest[6], twist[6],
 // GetDesiredComPose().tail(3).  Outputs (each may be null): g_vmc_in [37][n] complete, g_ratio [8][n], g_out [33][n] = stateCur[12],
 // stateDes[12], ddqDes[6], N, moveBasePhase, computeForceInWorldFrame.
-__global__ void __launch_bounds__(64) qr_stance_update_kernel(int n, StanceDesc S, float current_time, int stop, int reset, const float *__restrict__ g_est_in,
+__global__ void __launch_bounds__(64) qr_stance_update_kernel(int n, qrgpu_stance_desc S, float current_time, int stop, int reset, const float *__restrict__ g_est_in,
                                                               const float *__restrict__ g_est_out, const float *__restrict__ g_ground,
                                                               const float *__restrict__ g_rpy, const float *__restrict__ g_gait_out,
                                                               const float *__restrict__ g_gait_state, const float *__restrict__ g_cmd, float *__restrict__ g_st,
@@ -331,7 +332,7 @@ __global__ void __launch_bounds__(64) qr_stance_update_kernel(int n, StanceDesc 
 // (qr_locomotion_controller.cpp:128-147).  g_cmd [60][n]: p[12], Kp[12], d[12], Kd[12], tua[12].  WALK reads contacts (rows 18-21 of
 // g_vmc_in), N and moveBasePhase (rows 30, 31 of g_stance_out).  g_swing_q [24][n] joint angle and velocity targets and g_swing_flag [4][n]
 // (both may be null): a flagged leg's motors become {q, kp, qd, kd, 0} (qr_swing_leg_controller.cpp:456-458).
-__global__ void __launch_bounds__(64) qr_stance_command_kernel(int n, StanceDesc S, int stop, const float *__restrict__ g_vmc_in,
+__global__ void __launch_bounds__(64) qr_stance_command_kernel(int n, qrgpu_stance_desc S, int stop, const float *__restrict__ g_vmc_in,
                                                                const float *__restrict__ g_stance_out, const float *__restrict__ g_tau,
                                                                const float *__restrict__ g_swing_q, const float *__restrict__ g_swing_flag,
                                                                float *__restrict__ g_cmd)

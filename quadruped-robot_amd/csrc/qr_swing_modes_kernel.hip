@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include "qr_device_types.h"
 #include "qr_wave_helpers.h"
+#include "qr_kernels.h"
 
 namespace qrgpu {
 
@@ -162,7 +163,7 @@ __device__ __forceinline__ double quadprog_1d(const double ci[6], const double c
 }
 
 // qrFootStepper::CheckSolution (:85-116)
-__device__ __forceinline__ double check_solution(const SwingModeDesc &M, const float cx[4], double front, double back, float fd, float fw, float bd, float bw)
+__device__ __forceinline__ double check_solution(const qrgpu_swing_mode_desc &M, const float cx[4], double front, double back, float fd, float fw, float bd, float bw)
 {
 #pragma clang fp contract(off)
     const float delta = M.foothold_delta;
@@ -186,7 +187,7 @@ __device__ __forceinline__ double check_solution(const SwingModeDesc &M, const f
 }
 
 // qrFootStepper::StepGenerator (:118-179); gaitFlag is bit 2 of *pflags
-__device__ __forceinline__ int step_generator(const SwingModeDesc &M, const float cx[4], float des[4], int *pflags)
+__device__ __forceinline__ int step_generator(const qrgpu_swing_mode_desc &M, const float cx[4], float des[4], int *pflags)
 {
 #pragma clang fp contract(off)
     const float delta = M.foothold_delta;
@@ -238,7 +239,7 @@ __device__ __forceinline__ int step_generator(const SwingModeDesc &M, const floa
 
 // Reset (reset != 0) and Update of the swing-leg controller and its foothold planner: the lift-off memory of every mode, the footholds
 // and walk trajectories of the position and walk modes.  Optionally writes the lift-off rows the ADVANCED_TROT / VELOCITY kernels read.
-__global__ void __launch_bounds__(64) qr_swing_update_kernel(int n, SwingModeDesc M, int reset, int stop, const float *__restrict__ g_est_in,
+__global__ void __launch_bounds__(64) qr_swing_update_kernel(int n, qrgpu_swing_mode_desc M, int reset, int stop, const float *__restrict__ g_est_in,
                                                              const float *__restrict__ g_est_out, const float *__restrict__ g_gait_out, float *__restrict__ g_st,
                                                              float *__restrict__ g_swing_in, float *__restrict__ g_swing_vel_in, float *__restrict__ g_fe_in,
                                                              int *__restrict__ g_flags)
@@ -317,7 +318,7 @@ __global__ void __launch_bounds__(64) qr_swing_update_kernel(int n, SwingModeDes
             } else if (M.n_gaps > 0) {                                        // GetOptimalFootholdsOffset (:483-525)
                 int pf = (int)fminf(fmaxf(ST(SS_PFLAGS), 0.f), 3.f);
                 // head / tail address the queue: clamped, so that a state array that never saw reset = 2 cannot index outside it
-                int tail = (int)fminf(fmaxf(ST(SS_TAIL), 0.f), (float)QR_SWING_MAX_PLAN);
+                int tail = (int)fminf(fmaxf(ST(SS_TAIL), 0.f), (float)QRGPU_SWING_MAX_PLAN);
                 int head = (int)fminf(fmaxf(ST(SS_HEAD), 0.f), (float)tail);
                 if (!(pf & 1)) {
                     head = 0; tail = 0;
@@ -339,7 +340,7 @@ __global__ void __launch_bounds__(64) qr_swing_update_kernel(int n, SwingModeDes
                             cx[0] = (float)((double)cx[0] + (double)M.foothold_delta / 2.0);
                             cx[3] = (float)((double)cx[3] + (double)M.foothold_delta / 2.0);
                         } else {
-                            if (tail >= QR_SWING_MAX_PLAN) { flags |= SW_PLAN_FULL; break; }
+                            if (tail >= QRGPU_SWING_MAX_PLAN) { flags |= SW_PLAN_FULL; break; }
 #pragma unroll
                             for (int k = 0; k < 4; ++k) { ST(SS_PLAN + 4 * tail + k) = des[k]; cx[k] = cx[k] + des[k]; }
                             ++tail;
@@ -392,7 +393,7 @@ __global__ void __launch_bounds__(64) qr_swing_update_kernel(int n, SwingModeDes
 // GetAction of the position and walk modes: swing-leg selection, trajectory point, frame change, leg IK, J^-1 v, and the command loop over
 // the swingJointAnglesVelocities map (entries of legs that swung earlier and are flagged now re-emit their last targets).
 // g_out rows: foot position in the base frame[12], foot velocity in the base frame[12], joint angles[12], joint velocities[12], command[4].
-__global__ void __launch_bounds__(64) qr_swing_action_kernel(int n, SwingModeDesc M, EstimatorDesc D, int stop, const float *__restrict__ g_est_in,
+__global__ void __launch_bounds__(64) qr_swing_action_kernel(int n, qrgpu_swing_mode_desc M, qrgpu_estimator_desc D, int stop, const float *__restrict__ g_est_in,
                                                              const float *__restrict__ g_est_out, const float *__restrict__ g_gait_out,
                                                              const float *__restrict__ g_gait_state, float *__restrict__ g_st, float *__restrict__ g_out,
                                                              int *__restrict__ g_flags)

@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include "qr_device_types.h"
 #include "qr_wave_helpers.h"
+#include "qr_kernels.h"
 
 namespace qrgpu {
 
@@ -36,7 +37,7 @@ __device__ __forceinline__ float chain3(float a0, float b0, float a1, float b1, 
 }
 
 // fp32 QP data -> LDS.  sIn: the 37 inputs.  Outputs: Gf[144], af[12], cn[24][3], bf[24].
-__device__ __forceinline__ void vmc_assemble(int lane, const VmcType &C, const float *sIn, float *sA /*9*3 scratch*/, float *xc, float *Mm, float *Gf,
+__device__ __forceinline__ void vmc_assemble(int lane, const qrgpu_vmc_desc &C, const float *sIn, float *sA /*9*3 scratch*/, float *xc, float *Mm, float *Gf,
                                              float *af, float *cn, float *bf, const float *ratio /* fMinRatio[4], fMaxRatio[4] or null */)
 {
 #pragma clang fp contract(off)
@@ -134,9 +135,9 @@ __global__ void __launch_bounds__(64) qr_vmc_kernel(VmcLaunch P, const int *__re
     const int rid = xcd_robot_index(blockIdx.x, n);
     if (rid < 0) return;
     int tyid = type_id ? type_id[rid] : 0;
-    const bool bad_type = tyid < 0 || tyid >= QR_MAX_TYPES || !((P.type_ready >> (tyid & (QR_MAX_TYPES - 1))) & 1);
-    if (bad_type) tyid = __builtin_ctz(P.type_ready | (1 << QR_MAX_TYPES));       // computed with the first valid type, flagged QRGPU_ST_BAD_TYPE
-    const VmcType &C = P.type[tyid & (QR_MAX_TYPES - 1)];
+    const bool bad_type = tyid < 0 || tyid >= QRGPU_MAX_TYPES || !((P.type_ready >> (tyid & (QRGPU_MAX_TYPES - 1))) & 1);
+    if (bad_type) tyid = __builtin_ctz(P.type_ready | (1 << QRGPU_MAX_TYPES));       // computed with the first valid type, flagged QRGPU_ST_BAD_TYPE
+    const qrgpu_vmc_desc &C = P.type[tyid & (QRGPU_MAX_TYPES - 1)];
 
     __shared__ float sIn[48], sA[27], xc[12], Mm[72], Gf[144], af[12], cn[72], bf[24];
     __shared__ double Md[144], colv[12], xd[12], wd[12], zd[12], Sq[13 * 13], dd[12], rr[12], uu[13], mna[12 * 12];
@@ -154,12 +155,12 @@ __global__ void __launch_bounds__(64) qr_vmc_kernel(VmcLaunch P, const int *__re
 #pragma unroll
     for (int i = 0; i < 12; ++i) c1 += Md[13 * i];
     // ---- symmetric sweep: Md <- -G^-1 ; the pivots are the LDL^T pivots, L_jj = sqrt(pivot)
-    int st = bad_type ? QRGPU_ST_BAD_TYPE_D : 0;
+    int st = bad_type ? QRGPU_ST_BAD_TYPE : 0;
     for (int k = 0; k < 12; ++k) {
         if (lane < 12) colv[lane] = Md[12 * lane + k];
         vsync();
         const double piv = colv[k];
-        if (!(piv > 0.0)) st |= QRGPU_ST_VMC_INFEAS_D;
+        if (!(piv > 0.0)) st |= QRGPU_ST_VMC_INFEAS;
         c2 += 1.0 / __builtin_sqrt(piv);
         const double ip = 1.0 / piv;
         for (int e = lane; e < 144; e += 64) {
@@ -191,9 +192,9 @@ __global__ void __launch_bounds__(64) qr_vmc_kernel(VmcLaunch P, const int *__re
     unsigned active = 0, excluded = 0;            // bit c (uniform)
     int q = 0, iter = 0;
     const int maxit = 50 * 36 + 100;
-    bool stop = (st & QRGPU_ST_VMC_INFEAS_D) != 0;
+    bool stop = (st & QRGPU_ST_VMC_INFEAS) != 0;
     while (!stop) {
-        if (++iter > maxit) { st |= QRGPU_ST_VMC_MAXITER_D; break; }
+        if (++iter > maxit) { st |= QRGPU_ST_VMC_MAXITER; break; }
         double s = isrow ? ci0 + n0 * xd[3 * lc] + n1 * xd[3 * lc + 1] + n2 * xd[3 * lc + 2] : 0.0;
         const double psi = wave_sum_d(s < 0.0 ? s : 0.0);
         const bool cand = isrow && !(((active | excluded) >> lane) & 1u) && s < 0.0;
@@ -205,7 +206,7 @@ __global__ void __launch_bounds__(64) qr_vmc_kernel(VmcLaunch P, const int *__re
         double sip = smin;
         double unew = 0.0;
         for (;;) {
-            if (++iter > maxit) { st |= QRGPU_ST_VMC_MAXITER_D; stop = true; break; }
+            if (++iter > maxit) { st |= QRGPU_ST_VMC_MAXITER; stop = true; break; }
             // w = M n_p ; d = N_A' w ; r = S^-1 d ; z = w - M N_A r
             if (lane < 12) wd[lane] = Md[12 * lane + 3 * lp] * p0 + Md[12 * lane + 3 * lp + 1] * p1 + Md[12 * lane + 3 * lp + 2] * p2;
             vsync();
@@ -248,7 +249,7 @@ __global__ void __launch_bounds__(64) qr_vmc_kernel(VmcLaunch P, const int *__re
             const double delta = wd[3 * lp] * p0 + wd[3 * lp + 1] * p1 + wd[3 * lp + 2] * p2;
             const double t2 = (znp > 1e-8 * delta) ? -sip / znp : INF;
             const double t = t1 < t2 ? t1 : t2;
-            if (!(t < INF)) { st |= QRGPU_ST_VMC_INFEAS_D; stop = true; break; }       // QuadProg++ returns inf here; x stays as it is
+            if (!(t < INF)) { st |= QRGPU_ST_VMC_INFEAS; stop = true; break; }       // QuadProg++ returns inf here; x stays as it is
             const bool dual_only = !(t2 < INF);
             if (!dual_only && lane < 12) xd[lane] += t * zd[lane];
             if (lane < q) uu[lane] -= t * rr[lane];

@@ -27,6 +27,7 @@
 #include <type_traits>
 #include "qr_device_types.h"
 #include "qr_wave_helpers.h"
+#include "qr_kernels.h"
 
 namespace qrgpu {
 
@@ -463,7 +464,7 @@ __device__ __forceinline__ void wbc_qp_and_store(const int lane, const int rid, 
         qc0[c] = v;
     }
     wsync();
-    int stw = bad_type ? QRGPU_ST_BAD_TYPE_D : 0;
+    int stw = bad_type ? QRGPU_ST_BAD_TYPE : 0;
     {
         // Goldfarb-Idnani, Schur-complement form, M = W^-1 diagonal, dense normals.
         int q = 0;
@@ -479,7 +480,7 @@ __device__ __forceinline__ void wbc_qp_and_store(const int lane, const int rid, 
         // the six floating-base equalities: S^-1 = S_e^-1 is in place (wbc_qp_setup); u_e = -S_e^-1 c_e, z = M N_e' u_e, working set = {0..5}
         int next_eq = 0;
         {
-            if (eq_dependent) { stw |= QRGPU_ST_WBC_INFEAS_D; fail = true; }
+            if (eq_dependent) { stw |= QRGPU_ST_WBC_INFEAS; fail = true; }
             if (lane < 6) {
                 real acc = 0.0;
 #pragma unroll
@@ -519,7 +520,7 @@ __device__ __forceinline__ void wbc_qp_and_store(const int lane, const int rid, 
             }
             real up = 0.0;
             for (;;) {
-                if (++iter > maxit) { stw |= QRGPU_ST_WBC_MAXITER_D; fail = true; break; }
+                if (++iter > maxit) { stw |= QRGPU_ST_WBC_MAXITER; fail = true; break; }
                 *iter_out = iter;
                 // an inequality row touches the three force unknowns of one contact: its products are three terms, not a reduction
                 const int pj = 6 + 3 * ((p - 6) / 6);
@@ -557,7 +558,7 @@ __device__ __forceinline__ void wbc_qp_and_store(const int lane, const int rid, 
                 const real izc = fast_rcp(zc);
                 const real t2 = have_z ? -sp * izc : INF_;
                 const real t = t1 < t2 ? t1 : t2;
-                if (!(t < INF_)) { stw |= QRGPU_ST_WBC_INFEAS_D; fail = true; break; }
+                if (!(t < INF_)) { stw |= QRGPU_ST_WBC_INFEAS; fail = true; break; }
                 if (have_z) {
                     // z = w - M N r ; x += t z
                     real acc = 0.0;
@@ -648,7 +649,7 @@ __device__ __forceinline__ void wbc_qp_and_store(const int lane, const int rid, 
     }
     if (g_prev && lane < 3) st_w(&g_prev[(size_t)lane * n + rid], (float)cm[12 + lane], piped);          // desiredVel of the orientation task (quirk 4's memory)
     if (lane == 0 && g_status) {
-        if (status_or & 2) stw |= QRGPU_ST_PIPE_TIMEOUT_D;
+        if (status_or & 2) stw |= QRGPU_ST_PIPE_TIMEOUT;
         if (status_or & 1) st_w(&g_status[rid], stw | (piped ? __hip_atomic_load(g_status + rid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : g_status[rid]), piped);
         else st_w(&g_status[rid], stw, piped);
     }
@@ -696,13 +697,13 @@ void qr_wbc_kernel(int n, const WbcConst *__restrict__ types, const int *__restr
     }
     if (rid < 0) return;
     if (!pipe.second && gate_gave_up) { wbc_signal_done(pipe.finished, lane); return; }
-    if (QW_P_TL && threadIdx.x == 0 && !pipe.second) atomicMin(QW_P_TL + (pipe.epoch & 63u) * 8 + 3, wall_clock64());
+    if (QW_P_TL && threadIdx.x == 0 && !pipe.second) atomicMin(QW_P_TL + QR_TL_TICKS + (pipe.epoch & 63u) * 8 + 3, wall_clock64());
     if (pipe.order && !pipe.second) rid = pipe.order[rid];        // (a permutation inside the XCD chunk: qr_mpc_kernel.hip, finish_order_chunk)
     if (QW_P_TLR && threadIdx.x == 0 && !pipe.second) QW_P_TLR[rid] = (int)wall_clock64();
     int tyid = type_id ? type_id[rid] : 0;
-    const bool bad_type = tyid < 0 || tyid >= QR_MAX_TYPES || !((type_ready >> (tyid & (QR_MAX_TYPES - 1))) & 1);
-    if (bad_type) tyid = __builtin_ctz(type_ready | (1 << QR_MAX_TYPES));     // computed with the first valid type, flagged QRGPU_ST_BAD_TYPE
-    const WbcConst &K = types[tyid & (QR_MAX_TYPES - 1)];
+    const bool bad_type = tyid < 0 || tyid >= QRGPU_MAX_TYPES || !((type_ready >> (tyid & (QRGPU_MAX_TYPES - 1))) & 1);
+    if (bad_type) tyid = __builtin_ctz(type_ready | (1 << QRGPU_MAX_TYPES));     // computed with the first valid type, flagged QRGPU_ST_BAD_TYPE
+    const WbcConst &K = types[tyid & (QRGPU_MAX_TYPES - 1)];
 
     __shared__ real sm[QR_WBC_LDS_DOUBLES];
     real *A = sm;                  // 324  mass matrix
@@ -1350,7 +1351,7 @@ void qr_wbc_kernel(int n, const WbcConst *__restrict__ types, const int *__restr
                 // Never silent, also when the solve is still running and will store its status word OVER the one this workgroup writes: leave
                 // "gave up in this epoch" in the flag word itself (bit 31; epochs stay below 2^30) -- the solve raises the flag with an exchange
                 // and, finding that value, adds QRGPU_ST_PIPE_TIMEOUT to the status word it has just stored (qr_mpc_kernel.hip).
-                pipe_st = QRGPU_ST_PIPE_TIMEOUT_D;
+                pipe_st = QRGPU_ST_PIPE_TIMEOUT;
                 if (lane == 0) __hip_atomic_store(const_cast<unsigned *>(pipe.flag) + rid, 0x80000000u | (pipe.epoch << 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 break;
             }
@@ -1362,7 +1363,7 @@ void qr_wbc_kernel(int n, const WbcConst *__restrict__ types, const int *__restr
         if (lane < 12) cm[51 + lane] = (real)__hip_atomic_load(g_fr + (size_t)lane * n + rid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         wsync();
     }
-    if (pipe.wait_epoch && ((volatile int *)&sPipe)[0]) pipe_st = QRGPU_ST_PIPE_TIMEOUT_D;
+    if (pipe.wait_epoch && ((volatile int *)&sPipe)[0]) pipe_st = QRGPU_ST_PIPE_TIMEOUT;
     wbc_qp_and_store(lane, rid, n, K, nc, cpack, bad_type, eq_dependent, A, JC, cm, W, sI, g_tau, g_status, merge_tau, status_or | (pipe_st ? 2 : 0), epilogue, dbgT, g_qp,
                      pipe.flag != nullptr || pipe.wbc_done != nullptr, g_prev);
     if (pipe.wbc_done) {
@@ -1371,7 +1372,7 @@ void qr_wbc_kernel(int n, const WbcConst *__restrict__ types, const int *__restr
         if (lane == 0) qr_epoch_raise(pipe.wbc_done + rid, pipe.epoch);
     }
     wbc_signal_done(pipe.finished, lane);
-    if (QW_P_TL && lane == 0) atomicMax(QW_P_TL + (pipe.epoch & 63u) * 8 + (pipe.second ? 7 : 4), wall_clock64());
+    if (QW_P_TL && lane == 0) atomicMax(QW_P_TL + QR_TL_TICKS + (pipe.epoch & 63u) * 8 + (pipe.second ? 7 : 4), wall_clock64());
     if (QW_P_TLR && lane == 0 && !pipe.second) QW_P_TLR[2 * n + rid] = (int)wall_clock64();
 }
 

@@ -1,5 +1,5 @@
 // Internal: the context behind the opaque qrgpu_ctx of include/qrgpu.h, the environment switches and the declarations the host files share
-// (qrgpu_api.hip, qrgpu_mpc.hip, qrgpu_tick.hip, qrgpu_comm.hip).
+// (qrgpu_api.hip, qrgpu_stages.hip, qrgpu_debug.hip, qrgpu_mpc.hip, qrgpu_tick.hip, qrgpu_comm.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdlib>
@@ -10,6 +10,7 @@
 
 #include "../../include/qrgpu.h"
 #include "qr_device_types.h"
+#include "qr_kernels.h"
 
 using namespace qrgpu;
 
@@ -85,11 +86,11 @@ struct qrgpu_ctx {
     hipStream_t stream = nullptr;
     hipStream_t own_stream = nullptr;
     MpcLaunch mpc{};
-    bool mpc_ready[QR_MAX_TYPES] = {false, false, false, false};
-    bool wbc_ready[QR_MAX_TYPES] = {false, false, false, false};
+    bool mpc_ready[QRGPU_MAX_TYPES] = {false, false, false, false};
+    bool wbc_ready[QRGPU_MAX_TYPES] = {false, false, false, false};
     VmcLaunch vmc{};
-    bool vmc_ready[QR_MAX_TYPES] = {false, false, false, false};
-    WbcConst wbc_host[QR_MAX_TYPES];
+    bool vmc_ready[QRGPU_MAX_TYPES] = {false, false, false, false};
+    WbcConst wbc_host[QRGPU_MAX_TYPES];
     WbcConst *d_wbc = nullptr;
     bool wbc_dirty = true;
     // scratch for the single-robot calls and the fused tick
@@ -250,21 +251,19 @@ inline const QrEnv &qr_env() { static const QrEnv env{}; return env; }
 // ---------------------------------------------------------------------------------------------
 // Shared by the host files
 // ---------------------------------------------------------------------------------------------
-namespace qrgpu {
-struct MpcIO {
-    const int *type_id;
-    const float *g_state, *g_traj, *g_gait, *g_q;
-    float *g_force, *g_tau;
-    int *g_status;
-    float *dbgH, *dbgG, *g_force_wbc;
-    int force_stride;
-    long long *dbgT;
-};
-// (qr_mpc_kernel.hip)
-__global__ void qr_gate_kernel(int *counter, int expected_total, long long max_ticks, int *timed_out, int timed_out_value, int *bump);
-}
+inline int ready_mask(const bool *r) { int m = 0; for (int t = 0; t < QRGPU_MAX_TYPES; ++t) if (r[t]) m |= 1 << t; return m; }
 
-inline int ready_mask(const bool *r) { int m = 0; for (int t = 0; t < QR_MAX_TYPES; ++t) if (r[t]) m |= 1 << t; return m; }
+// The check every batched entry point starts with.
+inline bool batch_ok(const qrgpu_ctx *c, int n) { return c && n > 0 && n <= c->max_batch; }
+
+// A device allocation that lives as long as the scope that made it: freed on every exit path, an early HIPCHK return included.
+struct DeviceScratch {
+    void *p = nullptr;
+    DeviceScratch() = default;
+    DeviceScratch(const DeviceScratch &) = delete;
+    DeviceScratch &operator=(const DeviceScratch &) = delete;
+    ~DeviceScratch() { (void)hipFree(p); }
+};
 
 // Brackets a launch with a pair of events while timing is on (qrgpu_enable_timing): kernel 0 = the MPC main pass, 1 = the WBC launch.
 struct TimerScope {
@@ -320,6 +319,8 @@ inline MpcIO mpc_io(const int *type_id, const float *state, const float *traj, c
 int launch_mpc(qrgpu_ctx *c, int n, const MpcIO &arrays, const MpcOpts &opt = MpcOpts{});                                  // qrgpu_mpc.hip
 int launch_wbc(qrgpu_ctx *c, int n, const int *d_type, const float *d_state, const float *d_cmd, float *d_prev, float *d_tau, float *d_qdes, int *d_status,
                const WbcOpts &opt = WbcOpts{});                                                                            // qrgpu_api.hip
+int launch_vmc(qrgpu_ctx *c, int n, const int *d_type_id, const float *d_vmc_in, const float *d_ratio, const float *d_q, float *d_force, float *d_tau,
+               int *d_status);                                                                                             // qrgpu_api.hip
 hipError_t create_side_stream(hipStream_t *s);                                                                            // qrgpu_api.hip
 int lane_create(qrgpu_ctx *c, Lane &L, bool own_stream, bool masked = false);                                             // qrgpu_api.hip
 

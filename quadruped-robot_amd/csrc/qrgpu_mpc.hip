@@ -8,29 +8,6 @@
 
 #include "qrgpu_ctx.h"
 
-namespace qrgpu {
-template <int MAXB, bool BIG, bool LIST, int NTHR, int MINW = 0, bool H16 = (MAXB > 4)> __global__ void qr_mpc_kernel(MpcLaunch P, MpcIO io);
-extern template __global__ void qr_mpc_kernel<2, false, false, 512>(MpcLaunch, MpcIO);
-extern template __global__ void qr_mpc_kernel<4, true, true, 256>(MpcLaunch, MpcIO);
-extern template __global__ void qr_mpc_kernel<2, true, false, 512>(MpcLaunch, MpcIO);
-extern template __global__ void qr_mpc_kernel<2, true, false, 512, 4, true>(MpcLaunch, MpcIO);
-extern template __global__ void qr_mpc_kernel<5, true, false, 512>(MpcLaunch, MpcIO);
-extern template __global__ void qr_mpc_kernel<9, true, true, 256>(MpcLaunch, MpcIO);
-extern template __global__ void qr_mpc_kernel<4, true, true, 256, 2, true>(MpcLaunch, MpcIO);
-template <int MAXB, bool BIG, int NTHR, int MINW = 0> __global__ void qr_mpc_persist_kernel(MpcLaunch P, MpcIO io);
-extern template __global__ void qr_mpc_persist_kernel<2, false, 512>(MpcLaunch, MpcIO);
-extern template __global__ void qr_mpc_persist_kernel<5, true, 512>(MpcLaunch, MpcIO);
-// the same kernels with the executed-arithmetic counters compiled in (qr_mpc_kernel_fl.hip)
-template <int MAXB, bool BIG, bool LIST, int NTHR, int MINW = 0, bool H16 = (MAXB > 4)> __global__ void qr_mpc_kernel_fl(MpcLaunch P, MpcIO io);
-extern template __global__ void qr_mpc_kernel_fl<2, false, false, 512>(MpcLaunch, MpcIO);
-extern template __global__ void qr_mpc_kernel_fl<4, true, true, 256>(MpcLaunch, MpcIO);
-extern template __global__ void qr_mpc_kernel_fl<2, true, false, 512>(MpcLaunch, MpcIO);
-extern template __global__ void qr_mpc_kernel_fl<2, true, false, 512, 4, true>(MpcLaunch, MpcIO);
-extern template __global__ void qr_mpc_kernel_fl<5, true, false, 512>(MpcLaunch, MpcIO);
-extern template __global__ void qr_mpc_kernel_fl<9, true, true, 256>(MpcLaunch, MpcIO);
-__global__ void qr_lpt_order_kernel(int n, const int *cost, int *order, const int *ftime, int *wbc_order);
-}
-
 // One row per MpcVar (qrgpu_ctx.h), in the enum's order: the kernel, its counting build (qr_mpc_kernel_fl.hip; null: there is none and an
 // instrumented launch runs the plain kernel), the threads of a workgroup, and the persistent form of a main pass.
 struct MpcVariant { const void *fn, *fn_fl; int threads; MpcVar persistent; };

@@ -8,14 +8,6 @@
 
 #include "qrgpu_ctx.h"
 
-namespace qrgpu {
-__global__ void qr_join_kernel(int *counter, int expected_total, long long max_ticks, int *timed_out, int *g0, int e0, int *g1, int e1, int *tick_done,
-                               int *lane_done, int lane_expect, long long *dbg);
-__global__ void qr_gate2_kernel(int *c0, int e0, int *c1, int e1, long long max_ticks, long long *stamp);
-__global__ void qr_probe_wait_kernel(int *flag, int *out, long long max_ticks, int token);
-__global__ void qr_probe_set_kernel(int *flag, int token);
-}
-
 // The arrays of one qrgpu_tick_batch call.
 struct TickArgs {
     int n;
@@ -87,7 +79,7 @@ static int ov_begin(qrgpu_ctx *c, Lane &LN, const TickArgs &a, bool was_chain, b
         Lane &PL = c->lane[c->ov_lane_last];
         // (h > 11: the planned launches live on reserved CUs, the main pass cannot keep them from starting)
         hipLaunchKernelGGL(qr_gate2_kernel, dim3(1), dim3(64), 0, LN.stream, c->d_main_started, (int)c->ov_main_total, small_h ? PL.d_started : (int *)nullptr, (int)PL.started_total, (long long)5000000,
-                           c->d_timeline ? c->d_timeline + 512 + (epoch & 63u) * 2 : (long long *)nullptr);      // (diagnostic: qrgpu_debug_gate2)
+                           c->d_timeline ? c->d_timeline + QR_TL_GATES + (epoch & 63u) * 2 : (long long *)nullptr);      // (diagnostic: qrgpu_debug_gate2)
         HIPCHK(c, hipGetLastError());
     } else {
         ov.chained = false;
@@ -255,8 +247,9 @@ int qrgpu_tick_batch(qrgpu_ctx *c, int n, const int *d_type_id, const float *d_m
 // against each other and against the rest (a launch on one that waits for a launch queued afterwards on the other).
 static int probe_streams(qrgpu_ctx *c, hipStream_t *st, int nst, int npair)
 {
-    int *d_probe = nullptr;
-    HIPCHK(c, hipMalloc(&d_probe, 16 * sizeof(int)));
+    DeviceScratch scratch;
+    HIPCHK(c, hipMalloc(&scratch.p, 16 * sizeof(int)));
+    int *const d_probe = (int *)scratch.p;
     HIPCHK(c, hipMemset(d_probe, 0, 16 * sizeof(int)));
     HIPCHK(c, hipDeviceSynchronize());
     int k = 0, token = 0;
@@ -276,7 +269,6 @@ static int probe_streams(qrgpu_ctx *c, hipStream_t *st, int nst, int npair)
                 k = (k + 1) & 7;
             }
             if (res != 1) {
-                hipFree(d_probe);
                 static char msg[320];
                 snprintf(msg, sizeof(msg), "qrgpu_set_tick_overlap: two of the context's streams share a hardware queue in this process (set GPU_MAX_HW_QUEUES=8 before the first HIP call); "
                          "overlapped ticks stay off [a launch on stream %d of the set waited for one queued behind it on stream %d]", a, b);
@@ -285,7 +277,6 @@ static int probe_streams(qrgpu_ctx *c, hipStream_t *st, int nst, int npair)
                 return QRGPU_ERR_NOT_SETUP;
             }
         }
-    hipFree(d_probe);
     return QRGPU_OK;
 }
 

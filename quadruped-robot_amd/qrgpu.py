@@ -46,6 +46,25 @@ class MissingExtension(QrgpuError):
     """libqrgpu.so has not been built (run `python -c 'import __graft_entry__ as g; g.build()'`)."""
 
 
+def _set_fields(d, fields):
+    """Set fields of a ctypes struct from a dict: scalars or sequences by name, None = leave as it is.  Whether a value becomes an int or a
+    float is decided by the field's ctype."""
+    ctype_of = dict(d._fields_)
+    for name, v in fields.items():
+        if v is None:
+            continue
+        if name not in ctype_of:
+            raise AttributeError("%s has no field %r" % (type(d).__name__, name))
+        t = ctype_of[name]
+        if issubclass(t, C.Array):
+            conv = int if issubclass(t._type_, C.c_int) else float
+            arr = getattr(d, name)
+            for k, x in enumerate(v): arr[k] = conv(x)
+        else:
+            setattr(d, name, (int if issubclass(t, C.c_int) else float)(v))
+    return d
+
+
 class model_desc_struct(C.Structure):
     _fields_ = [("hip_l", C.c_float), ("upper_l", C.c_float), ("lower_l", C.c_float), ("body_size", C.c_float * 3),
                 ("kp_body_pos", C.c_float), ("kd_body_pos", C.c_float), ("kp_body_ori", C.c_float), ("kd_body_ori", C.c_float),
@@ -62,6 +81,18 @@ class estimator_desc_struct(C.Structure):
     _fields_ = [("hip_l", C.c_float), ("upper_l", C.c_float), ("lower_l", C.c_float), ("hip_offset", C.c_float * 12),
                 ("time_step", C.c_float), ("accelerometer_variance", C.c_float), ("sensor_variance", C.c_float), ("window", C.c_int),
                 ("body_height", C.c_float)]
+
+
+def _estimator_desc(cfg20, geometry_only=False):
+    """qrgpu_estimator_desc from workload.estimator_cfg() (an estimator_desc_struct is passed on as it is).  geometry_only: the leg geometry
+    alone -- hip_l, upper_l, lower_l, hip_offset -- and the rest zero: all the swing stages read."""
+    if isinstance(cfg20, estimator_desc_struct):
+        return cfg20
+    v = np.asarray(cfg20, np.float32)
+    d = _set_fields(estimator_desc_struct(), dict(hip_l=v[0], upper_l=v[1], lower_l=v[2], hip_offset=v[7:19]))
+    if not geometry_only:
+        _set_fields(d, dict(time_step=v[3], accelerometer_variance=v[4], sensor_variance=v[5], window=v[6], body_height=v[19]))
+    return d
 
 
 class foothold_desc_struct(C.Structure):
@@ -102,13 +133,9 @@ def swing_mode_desc(mode, terrain=None, is_sim=None, foothold_delta=None, gaps=N
     """qrgpu_swing_mode_desc: the library's defaults for `mode` (config/a1_sim), with any field overridden."""
     d = swing_mode_desc_struct()
     load_library().qrgpu_swing_mode_desc_default(C.byref(d), int(mode))
-    if terrain is not None: d.terrain = int(terrain)
-    if is_sim is not None: d.is_sim = int(bool(is_sim))
-    if foothold_delta is not None: d.foothold_delta = float(foothold_delta)
-    if gap_width is not None: d.gap_width = float(gap_width)
+    _set_fields(d, dict(terrain=terrain, is_sim=None if is_sim is None else bool(is_sim), foothold_delta=foothold_delta, gap_width=gap_width))
     if gaps is not None:
-        d.n_gaps = len(gaps)
-        for k, g in enumerate(list(gaps)[:MAX_GAPS]): d.gap_distance[k] = float(g)
+        _set_fields(d, dict(n_gaps=len(gaps), gap_distance=list(gaps)[:MAX_GAPS]))
     return d
 
 
@@ -126,15 +153,8 @@ def stance_desc(mode, terrain=None, force_in_world=None, **fields):
     """qrgpu_stance_desc: the library's defaults for `mode` (config/a1_sim), with any field overridden (scalars or sequences by name)."""
     d = stance_desc_struct()
     load_library().qrgpu_stance_desc_default(C.byref(d), int(mode))
-    if terrain is not None: d.terrain = int(terrain)
-    if force_in_world is not None: d.force_in_world = int(bool(force_in_world))
-    for name, v in fields.items():
-        cur = getattr(d, name)
-        if hasattr(cur, "__len__"):
-            for k, x in enumerate(v): cur[k] = float(x)
-        else:
-            setattr(d, name, float(v))
-    return d
+    _set_fields(d, dict(terrain=terrain, force_in_world=None if force_in_world is None else bool(force_in_world)))
+    return _set_fields(d, fields)
 
 
 POSE_MAX_LOOPS, POSE_STATE_ROWS = 20, 26
@@ -152,13 +172,7 @@ def pose_plan_desc(**fields):
     """qrgpu_pose_plan_desc: the library's defaults (the reference's constants), with any field overridden (scalars or sequences by name)."""
     d = pose_plan_desc_struct()
     load_library().qrgpu_pose_plan_desc_default(C.byref(d))
-    for name, v in fields.items():
-        cur = getattr(d, name)
-        if hasattr(cur, "__len__"):
-            for k, x in enumerate(v): cur[k] = float(x)
-        else:
-            setattr(d, name, int(v) if name == "loops" else float(v))
-    return d
+    return _set_fields(d, fields)
 
 
 EPILOGUE_HIP_COMP, EPILOGUE_CLIP = 1, 2
@@ -430,13 +444,7 @@ class Context:
     def wbc_setup(self, type_id, hip_l=None, upper_l=None, lower_l=None, body_size=None, **gains):
         d = model_desc_struct()
         self._lib.qrgpu_model_desc_default(C.byref(d))
-        if hip_l is not None: d.hip_l = hip_l
-        if upper_l is not None: d.upper_l = upper_l
-        if lower_l is not None: d.lower_l = lower_l
-        if body_size is not None:
-            for i in range(3): d.body_size[i] = body_size[i]
-        for k, v in gains.items():
-            setattr(d, k, v)
+        _set_fields(d, dict(hip_l=hip_l, upper_l=upper_l, lower_l=lower_l, body_size=None if body_size is None else [body_size[i] for i in range(3)], **gains))
         self._chk(self._lib.qrgpu_wbc_setup(self._h, type_id, C.byref(d)))
 
     def wbc_setup_packed(self, type_id, model6):
@@ -545,11 +553,7 @@ class Context:
 
     def estimator_update_batch(self, n, cfg20, est_in, tick, est_state, est_out):
         """UpdateDataFlow kinematics + qrRobotVelocityEstimator::Update of n robots.  cfg20 = workload.estimator_cfg()."""
-        d = estimator_desc_struct()
-        cfg20 = np.asarray(cfg20, np.float32)
-        d.hip_l, d.upper_l, d.lower_l, d.time_step, d.accelerometer_variance, d.sensor_variance = (float(v) for v in cfg20[:6])
-        d.window = int(cfg20[6]); d.body_height = float(cfg20[19])
-        for i in range(12): d.hip_offset[i] = float(cfg20[7 + i])
+        d = _estimator_desc(cfg20)
         self._chk(self._lib.qrgpu_estimator_update_batch(self._h, n, C.byref(d), _dp(est_in), _dp(tick), _dp(est_state), _dp(est_out)))
 
     def gait_update_batch(self, n, cfg19, current_time, contact, gait_state, gait_out=None, fe_in=None, stop=False, reset=False):
@@ -596,10 +600,7 @@ class Context:
     def swing_velocity_batch(self, n, cfg20, vdesc20, swing_vel_in, out):
         """Swing-leg action of the velocity mode (qr_swing_leg_controller.cpp:285-309, 408-424).  cfg20 = workload.estimator_cfg() (geometry
         part), vdesc20 = workload.swing_velocity_cfg(): hip position + com offset[12], stanceDuration[4], swingKp[3], desiredHeight - clearance."""
-        d = estimator_desc_struct()
-        cfg20 = np.asarray(cfg20, np.float32)
-        d.hip_l, d.upper_l, d.lower_l = (float(v) for v in cfg20[:3])
-        for i in range(12): d.hip_offset[i] = float(cfg20[7 + i])
+        d = _estimator_desc(cfg20, geometry_only=True)
         v = swing_velocity_desc_struct(); vd = np.asarray(vdesc20, np.float32)
         for i in range(12): v.hip_position_com[i] = float(vd[i])
         for i in range(4): v.stance_duration[i] = float(vd[12 + i])
@@ -609,10 +610,7 @@ class Context:
 
     def swing_targets_batch(self, n, cfg20, swing_in, wbc_cmd=None, foot_target_world=None, qdes=None):
         """Swing-leg targets (qr_swing_leg_controller.cpp:362-424, ADVANCED_TROT).  cfg20 = workload.estimator_cfg() (geometry part)."""
-        d = estimator_desc_struct()
-        cfg20 = np.asarray(cfg20, np.float32)
-        d.hip_l, d.upper_l, d.lower_l = (float(v) for v in cfg20[:3])
-        for i in range(12): d.hip_offset[i] = float(cfg20[7 + i])
+        d = _estimator_desc(cfg20, geometry_only=True)
         self._chk(self._lib.qrgpu_swing_targets_batch(self._h, n, C.byref(d), _dp(swing_in), _dp(wbc_cmd), _dp(foot_target_world), _dp(qdes)))
 
     def swing_update_batch(self, n, desc, est_in, est_out, gait_out, swing_state, swing_flags, gait_state=None, swing_in=None, swing_vel_in=None,
@@ -625,10 +623,7 @@ class Context:
     def swing_action_batch(self, n, desc, cfg20, est_in, est_out, gait_out, swing_state, out, swing_flags, gait_state=None, stop=False):
         """GetAction of the position and walk modes (qr_swing_leg_controller.cpp:204-229, 311-359, 407-459).  cfg20 = workload.estimator_cfg()
         (geometry part); out [52][n]."""
-        d = estimator_desc_struct()
-        cfg20 = np.asarray(cfg20, np.float32)
-        d.hip_l, d.upper_l, d.lower_l = (float(v) for v in cfg20[:3])
-        for i in range(12): d.hip_offset[i] = float(cfg20[7 + i])
+        d = _estimator_desc(cfg20, geometry_only=True)
         self._chk(self._lib.qrgpu_swing_action_batch(self._h, n, C.byref(desc), C.byref(d), int(bool(stop)), _dp(est_in), _dp(est_out), _dp(gait_out),
                                                      _dp(gait_state), _dp(swing_state), _dp(out), _dp(swing_flags)))
 

@@ -84,6 +84,54 @@ def test_desc_defaults(pkg):
                        pkg.workload.walk_cfg())
 
 
+def _header_structs():
+    """The `typedef struct { ... } qrgpu_*_desc;` blocks of include/qrgpu.h as {name: [(member, "float" | "int", array length or 0)]};
+    array lengths given by a macro are resolved from the header's own #define.  A member the parser does not understand raises."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    txt = open(os.path.join(root, "include", "qrgpu.h")).read()
+    defines = {m.group(1): int(m.group(2), 0) for m in re.finditer(r"^#define\s+(QRGPU_\w+)\s+(\d+|0x[0-9a-fA-F]+)\b", txt, re.M)}
+    code = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    out = {}
+    for body, name in re.findall(r"typedef\s+struct\s*\{(.*?)\}\s*(qrgpu_\w+_desc)\s*;", code, re.S):
+        members = []
+        for stmt in (x.strip() for x in body.split(";")):
+            if not stmt:
+                continue
+            m = re.fullmatch(r"(float|int)\s+(.+)", stmt, re.S)
+            assert m, "%s: unparsed member %r" % (name, stmt)
+            for decl in (x.strip() for x in m.group(2).split(",")):
+                d = re.fullmatch(r"(\w+)(?:\[(\w+)\])?", decl)
+                assert d, "%s: unparsed declarator %r" % (name, decl)
+                dim = d.group(2)
+                members.append((d.group(1), m.group(1), 0 if dim is None else int(dim) if dim.isdigit() else defines[dim]))
+        out[name] = members
+    return out
+
+
+def test_ctypes_structs_mirror_the_header(pkg):
+    """Every parameter block of include/qrgpu.h against its ctypes class in qrgpu.py: member names, their order, float / int, array lengths."""
+    structs = _header_structs()
+    assert len(structs) >= 10, sorted(structs)
+    q = pkg.qrgpu
+    mirror = {"qrgpu_model_desc": q.model_desc_struct, "qrgpu_vmc_desc": q.vmc_desc_struct, "qrgpu_estimator_desc": q.estimator_desc_struct,
+              "qrgpu_gait_desc": q.gait_desc_struct, "qrgpu_walk_gait_desc": q.walk_gait_desc_struct,
+              "qrgpu_swing_velocity_desc": q.swing_velocity_desc_struct, "qrgpu_foothold_desc": q.foothold_desc_struct,
+              "qrgpu_swing_mode_desc": q.swing_mode_desc_struct, "qrgpu_stance_desc": q.stance_desc_struct, "qrgpu_pose_plan_desc": q.pose_plan_desc_struct}
+    assert set(structs) == set(mirror), set(structs) ^ set(mirror)
+    base = {C.c_float: "float", C.c_int: "int"}
+    for name, cls in mirror.items():
+        got = []
+        for field, t in cls._fields_:
+            if issubclass(t, C.Array):
+                got.append((field, base[t._type_], t._length_))
+            else:
+                got.append((field, base[t], 0))
+        assert got == structs[name], name
+        assert C.sizeof(cls) == 4 * sum(max(1, dim) for _, _, dim in structs[name]), name
+    gaps = dict((f, dim) for f, _, dim in structs["qrgpu_swing_mode_desc"])["gap_distance"]
+    assert gaps == 8 == q.MAX_GAPS
+
+
 @pytest.mark.gpu
 def test_error_returns(gpu_ctx, pkg):
     """The reference has no error channel on this path; the C ABI returns a code from every call (error behaviour)."""
@@ -136,7 +184,7 @@ def test_supported_environment_switches_are_listed_in_the_header():
     import glob
     csrc = os.path.join(root, "quadruped-robot_amd", "csrc")
     host = sorted(glob.glob(os.path.join(csrc, "qrgpu_*.hip")) + glob.glob(os.path.join(csrc, "qrgpu_*.h")))
-    assert len(host) >= 5, host                  # (api, mpc, tick, comm and the context header)
+    assert len(host) >= 5, host                  # (api, stages, debug, mpc, tick, comm and the context header)
     read, read_lab = set(), set()
     for f in host:
         src = open(f).read()

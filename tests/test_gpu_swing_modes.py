@@ -389,3 +389,86 @@ def test_swing_modes_bad_arguments(gpu_ctx, pkg):
         gpu_ctx.swing_action_batch(n, pkg.swing_mode_desc(1), ecfg, a[0], a[1], a[2], a[3], a[0], d_fl)   # position without gait state
     for v in a + [d_fl]:
         v.free()
+
+
+def test_swing_stages_read_only_the_geometry(gpu_ctx, pkg):
+    """qrgpu_swing_targets_batch, qrgpu_swing_velocity_batch and qrgpu_swing_action_batch (WALK) hand the caller's qrgpu_estimator_desc to their
+    kernels as it is: the members that are not leg geometry may hold anything.  n = 65: two workgroups, the second with one robot.  Each stage
+    runs on the same inputs with a clean geometry-only block and with window = -7, time_step = NaN, variances 1e30, body_height = -1: bit-equal."""
+    W = pkg.workload
+    S = pkg.to_soa
+    n = 65
+    sentinel = np.float32(-777.0)
+    clean = pkg.qrgpu._estimator_desc(W.estimator_cfg("a1"), geometry_only=True)
+    junk = pkg.qrgpu._estimator_desc(W.estimator_cfg("a1", time_step=np.nan, accelerometer_variance=1e30, sensor_variance=1e30, window=-7, body_height=-1.0))
+    assert (clean.window, clean.time_step, clean.body_height) == (0, 0.0, 0.0)
+    assert junk.window == -7 and np.isnan(junk.time_step) and junk.sensor_variance == np.float32(1e30) and junk.body_height == -1.0
+    assert list(junk.hip_offset) == list(clean.hip_offset) and (junk.hip_l, junk.upper_l, junk.lower_l) == (clean.hip_l, clean.upper_l, clean.lower_l)
+
+    def fresh(rows):
+        return gpu_ctx.alloc((rows, n)).upload(np.full((rows, n), sentinel, np.float32))
+
+    def same(a, b):
+        return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
+
+    # swing targets
+    d_in = gpu_ctx.alloc((58, n)).upload(S(W.make_swing_batch(n, seed=31)))
+    res = []
+    for desc in (clean, junk):
+        outs = [fresh(67), fresh(12), fresh(24)]
+        gpu_ctx.swing_targets_batch(n, desc, d_in, *outs)
+        gpu_ctx.sync()
+        res.append([v.download() for v in outs])
+        for v in outs:
+            v.free()
+    d_in.free()
+    assert all(same(a, b) for a, b in zip(*res))
+    assert (res[0][0][15:51] != sentinel).any() and (res[0][2] != sentinel).any()                 # ... and something was written
+
+    # velocity-mode swing action
+    d_in = gpu_ctx.alloc((53, n)).upload(S(W.make_swing_velocity_batch(n, seed=32)))
+    res = []
+    for desc in (clean, junk):
+        d_out = fresh(48)
+        gpu_ctx.swing_velocity_batch(n, desc, W.swing_velocity_cfg("a1"), d_in, d_out)
+        gpu_ctx.sync()
+        res.append(d_out.download()); d_out.free()
+    d_in.free()
+    assert same(*res) and (res[0] != sentinel).any()
+
+    # walk-mode swing action: one 1 s walk cycle of gait, swing update and action (as run_modes drives them, contacts following the schedule as in
+    # gait_pass: a foot is down unless the previous tick had it in TRUE_SWING); every 25th tick -- a leg's true swing lasts 37 -- the action runs
+    # twice from the same state, with either block
+    gcfg = W.walk_cfg(**WALK_SHORT)
+    sdesc = pkg.swing_mode_desc(pkg.qrgpu.MODE_WALK)
+    d_gs = gpu_ctx.alloc((33, n)); d_go = gpu_ctx.alloc((41, n)); d_ct = gpu_ctx.alloc((4, n))
+    d_ei = gpu_ctx.alloc((54, n)); d_eo = gpu_ctx.alloc((42, n))
+    d_st = gpu_ctx.alloc((R.STATE_FLOATS, n)).upload(np.full((R.STATE_FLOATS, n), np.nan, np.float32)); d_fl = gpu_ctx.alloc((n,))
+    d_out = fresh(R.OUT_ROWS)
+    compared = commanded = 0
+    contact = np.ones((4, n), np.float32)
+    for k in range(500):
+        d_ct.upload(contact)
+        gpu_ctx.walk_gait_update_batch(n, gcfg, k * DT, d_ct, d_gs, d_go, reset=2 if k == 0 else 0)
+        ei, eo = est_arrays(n, k, 33, drift=0.0)
+        d_ei.upload(ei); d_eo.upload(eo)
+        gpu_ctx.swing_update_batch(n, sdesc, d_ei, d_eo, d_go, d_st, d_fl, gait_state=d_gs, reset=2 if k == 0 else 0)
+        gpu_ctx.sync()
+        contact = (d_go.download().reshape(41, n)[8:12] != 8).astype(np.float32)
+        if k % 25 != 24:
+            gpu_ctx.swing_action_batch(n, sdesc, clean, d_ei, d_eo, d_go, d_st, d_out, d_fl)
+            continue
+        before = [v.download() for v in (d_out, d_st, d_fl)]
+        res = []
+        for desc in (clean, junk):
+            for v, h in zip((d_out, d_st, d_fl), before):
+                v.upload(h)
+            gpu_ctx.swing_action_batch(n, sdesc, desc, d_ei, d_eo, d_go, d_st, d_out, d_fl)
+            gpu_ctx.sync()
+            res.append([v.download() for v in (d_out, d_st, d_fl)])
+        assert all(same(a, b) for a, b in zip(*res)), k
+        compared += 1
+        commanded += int((res[0][0][48:52] == 1).sum())
+    for v in (d_gs, d_go, d_ct, d_ei, d_eo, d_st, d_fl, d_out):
+        v.free()
+    assert compared == 20 and commanded > 0                                                       # ... on ticks with legs in true swing
