@@ -1,0 +1,182 @@
+"""-m gpu: the WBC kernel's rigid-body quantities (qrgpu_fb_debug_batch) and its torques far off the stand pose.
+
+First link of the chain  kernel -> oracle -> mechanics  (the second, the float64 oracle against the first-principles model of
+tests/rigid_body_ref.py at 1e-10, is tests/test_rigid_body_ref.py):
+  * H and C against the model directly (they live in body coordinates and do not see the float32 quaternion's norm defect);
+  * all seven quantities against the float64 oracle on the same raw float32 state (the oracle shares the kernel's unnormalised R), at the
+    project's bars: H 2e-6, G 2e-5, C 2e-6, Jc 1e-6, Jcdqd 2e-5, pGC 1e-6, vGC 1e-6, each times max(1, max|ref|).
+One mixed batch, A1 = type 0 and Lite3 = type 1 interleaved through type_id, each robot with the stand (make_batch), wide (attitude uniform
+on S^3, joints and rates far off the stand pose) and edge families; n = 239 is odd and above 64, so the per-XCD robot ranges have a remainder.
+"""
+import numpy as np
+import pytest
+
+import gpu_helpers as G
+import rigid_body_ref as M
+
+pytestmark = pytest.mark.gpu
+
+ROBOTS = ("a1", "lite3")
+BARS = (("H", 2e-6), ("G", 2e-5), ("C", 2e-6), ("Jc", 1e-6), ("Jcdqd", 2e-5), ("pGC", 1e-6), ("vGC", 1e-6))
+
+
+def _setup_both(ctx, pkg):
+    for t, robot in enumerate(ROBOTS):
+        ctx.mpc_setup_packed(t, pkg.mpc_cfg(robot), 10); ctx.wbc_setup_packed(t, pkg.model_desc(robot))
+
+
+def _interleave(rows_a1, rows_lite3):
+    """A1 rows at even places, Lite3 rows at odd ones (A1 may have one more)."""
+    na, nl = len(rows_a1), len(rows_lite3)
+    assert na in (nl, nl + 1)
+    out = np.empty((na + nl,) + rows_a1.shape[1:], rows_a1.dtype)
+    out[0::2] = rows_a1; out[1::2] = rows_lite3
+    return out
+
+
+@pytest.fixture(scope="module")
+def rb(gpu_ctx, pkg, oracle):
+    """The mixed batch, what the kernel gives on it, the float64 oracle on the same raw float32 rows and the model on the normalised ones
+    (computed once, shared, read-only).  family[i] / row[i]: which family robot i's state is from and its row there."""
+    _setup_both(gpu_ctx, pkg)
+    states, family, row = {}, {}, {}
+    for robot in ROBOTS:
+        f = M.families(pkg, robot)
+        if robot == "a1":          # one more stand state: n odd
+            f["stand"] = np.concatenate([f["stand"], pkg.make_batch(1, 10, "a1", seed=M.SEEDS["a1"]["stand"] + 1)["fb_state"]])
+        states[robot] = np.concatenate([f["stand"], f["wide"], f["edge"]])
+        family[robot] = np.array(sum(([k] * len(f[k]) for k in ("stand", "wide", "edge")), []))
+        row[robot] = np.concatenate([np.arange(len(f[k])) for k in ("stand", "wide", "edge")])
+    st = _interleave(states["a1"], states["lite3"])
+    n = len(st)
+    assert n == 239 and n % 2 == 1 and n > 64
+    tid = pkg.shard.interleave_types(n, 2)
+    got = G.run_fb_debug(gpu_ctx, pkg, dict(n=n, fb_state=st), type_id=tid)
+    ora = {k: np.zeros(got[k].shape) for k, _ in BARS}
+    for i in range(n):
+        o = oracle.fb_compute(pkg.model_desc(ROBOTS[tid[i]]), st[i].astype(np.float64), np.float64)
+        for k, _ in BARS:
+            ora[k][i] = o[k]
+    model = {k: np.zeros(got[k].shape) for k in ("H", "C")}
+    for t, robot in enumerate(ROBOTS):
+        r = M.compute(pkg.model_desc(robot), M.normalised(st[t::2]))
+        for k in model:
+            model[k][t::2] = r[k]
+    yield dict(n=n, state=st, tid=tid, got=got, oracle=ora, model=model, family=_interleave(family["a1"], family["lite3"]),
+               row=_interleave(row["a1"], row["lite3"]))
+    G.setup_a1(gpu_ctx, pkg, 10)
+
+
+def _rel(got, ref):
+    """Per robot: max|got - ref| / max(1, max|ref|)."""
+    n = len(ref)
+    return np.abs(got - ref).reshape(n, -1).max(1) / np.maximum(1.0, np.abs(ref).reshape(n, -1).max(1))
+
+
+def _report(what, rb, k, rel, tol):
+    for t, robot in enumerate(ROBOTS):
+        print("%s %-5s %-5s " % (what, robot, k) + "  ".join("%s %.2e" % (fam, rel[(rb["tid"] == t) & (rb["family"] == fam)].max())
+                                                            for fam in ("stand", "wide", "edge")) + "  (bar %.0e)" % tol)
+
+
+def test_mass_matrix_and_coriolis_against_the_model(rb):
+    """fb_debug_batch against first-principles mechanics directly, every state, both robots: 2e-6 * max(1, max|x|), the bars of
+    test_rigid_body_quantities.  Un-mirroring one hip inertia in build_wbc_const moves H by 2.5e-6 to 6.6e-6 of that scale on every state
+    here and C by up to 6e-4; one wrong `loc` sign moves H by 2e-2: both are above the bar.
+    Measured: H at its float32 rounding (4.5e-9); C 1.7e-7 on the wide family, which is the rotors' own terms (1e-8 kg, 1e-8 kg m^2 each) that
+    the kernel's Coriolis chain leaves out -- the model without them reproduces the kernel's figure to three digits (LAB_NOTES A.12)."""
+    for k, tol in (("H", 2e-6), ("C", 2e-6)):
+        rel = _rel(rb["got"][k], rb["model"][k])
+        _report("kernel vs model ", rb, k, rel, tol)
+        assert np.all(rel <= tol), (k, int(rel.argmax()), rb["family"][rel.argmax()], rel.max())
+
+
+def test_all_seven_against_the_float64_oracle(rb):
+    """fb_debug_batch against oracle.fb_compute(float64) on the same raw float32 state, all seven quantities, the project's bars."""
+    bad = []
+    for k, tol in BARS:
+        rel = _rel(rb["got"][k], rb["oracle"][k])
+        _report("kernel vs oracle", rb, k, rel, tol)
+        if not np.all(rel <= tol):
+            bad.append((k, int(rel.argmax()), str(rb["family"][rel.argmax()]), float(rel.max())))
+    assert not bad, bad
+
+
+def _edge(rb, t, r):
+    i = np.nonzero((rb["tid"] == t) & (rb["family"] == "edge") & (rb["row"] == r))[0]
+    assert len(i) == 1
+    return int(i[0])
+
+
+def test_negated_quaternion_gives_the_same_bits(rb):
+    """R is even in the quaternion (every entry is a sum of products of two components), so q and -q give bit-equal outputs."""
+    for t in range(2):
+        a, b = _edge(rb, t, M.NEG_PAIR[0]), _edge(rb, t, M.NEG_PAIR[1])
+        assert np.array_equal(rb["state"][a, 0:4], -rb["state"][b, 0:4]) and np.array_equal(rb["state"][a, 4:], rb["state"][b, 4:])
+        for k, _ in BARS:
+            assert np.array_equal(rb["got"][k][a], rb["got"][k][b]), (ROBOTS[t], k, np.abs(rb["got"][k][a] - rb["got"][k][b]).max())
+    assert (rb["state"][rb["family"] == "wide", 0] < 0).any()
+
+
+def test_unit_velocity_states(rb):
+    """nu = e_k: the kernel's foot velocity is column k of its own foot Jacobian, within 1e-6."""
+    worst = 0.0
+    for t in range(2):
+        for r in M.UNIT_EDGES:
+            i = _edge(rb, t, r)
+            worst = max(worst, np.abs(rb["got"]["vGC"][i] - rb["got"]["Jc"][i][:, :, r - 5]).max())
+    print("nu = e_k: max |vGC - Jc[:, :, k]| = %.2e" % worst)
+    assert worst <= 1e-6
+
+
+def test_rest_states(rb):
+    """At rest C, Jcdqd and vGC vanish: within the bars, absolute (max(1, 0) = 1)."""
+    tol = dict(BARS)
+    for t in range(2):
+        for r in M.REST_EDGES:
+            i = _edge(rb, t, r)
+            assert not rb["state"][i, 7:13].any() and not rb["state"][i, 25:37].any()
+            for k in ("C", "Jcdqd", "vGC"):
+                assert np.abs(rb["got"][k][i]).max() <= tol[k], (ROBOTS[t], r, k, np.abs(rb["got"][k][i]).max())
+
+
+def test_wbc_torques_off_the_stand_pose(gpu_ctx, pkg, oracle):
+    """The whole WBC tick on the stand and wide families of both robots (mixed batch), wbc_cmd and prev_ori_vel from make_batch, the contact
+    patterns (0,0,0,0) and (0,1,0,0) forced on rows 0-3 of each family, against oracle.wbc_run(float64) on the same float32 inputs:
+    status 0, tau within 1e-6 * max(1,|tau|), qdes within 1e-5 and qddes within 1e-4 of max(1,|.|).
+    Condition on the inputs, checked here on the CPU for every state used (rigid_body_ref.wbc_cases redraws by seed at generation, nothing is
+    dropped here): the float64 oracle returns rc 0 and amplifies a 1e-12 relative perturbation of state and command by less than 1e6 relative
+    to max(1,|tau|) (worst seen 6.9e3), so 1e-6 is the float32 rounding of the output, not conditioning.
+    The float32 oracle's 1e-4 bar is not asserted: on the wide family it is 1.8e-3 from its own float64 evaluation (test_rigid_body_ref)."""
+    _setup_both(gpu_ctx, pkg)
+    cs = [M.wbc_cases(pkg, oracle, robot) for robot in ROBOTS]
+    for c in cs:
+        assert np.all(c["amp"] < M.AMPLIFICATION_MAX)
+    b = dict(n=2 * len(cs[0]["state"]), fb_state=_interleave(cs[0]["state"], cs[1]["state"]), wbc_cmd=_interleave(cs[0]["cmd"], cs[1]["cmd"]),
+             prev_ori_vel=_interleave(cs[0]["prev"], cs[1]["prev"]))
+    n = b["n"]
+    tid = pkg.shard.interleave_types(n, 2)
+    out = G.run_wbc(gpu_ctx, pkg, b, type_id=tid)
+    G.setup_a1(gpu_ctx, pkg, 10)
+    tau = np.zeros((n, 12)); qdes = np.zeros((n, 12)); qddes = np.zeros((n, 12))
+    for i in range(n):
+        w = oracle.wbc_run(pkg.model_desc(ROBOTS[tid[i]]), b["fb_state"][i].astype(np.float64), b["wbc_cmd"][i].astype(np.float64),
+                           b["prev_ori_vel"][i].astype(np.float64), dtype=np.float64)
+        assert w["rc"] == 0
+        tau[i], qdes[i], qddes[i] = w["tau"], w["qdes"], w["qddes"]
+    e_tau = np.abs(out["tau"] - tau) / np.maximum(1.0, np.abs(tau))
+    e_q = np.abs(out["qdes"] - qdes) / np.maximum(1.0, np.abs(qdes))
+    e_qdd = np.abs(out["qddes"] - qddes) / np.maximum(1.0, np.abs(qddes))
+    wide = (np.arange(n) // 2) >= M.N_STAND
+    for name, sel in (("stand", ~wide), ("wide", wide)):
+        print("wbc off the stand pose, %-5s: tau %.2e (bar 1e-6)  qdes %.2e (1e-5)  qddes %.2e (1e-4)  max|tau| %.0f"
+              % (name, e_tau[sel].max(), e_q[sel].max(), e_qdd[sel].max(), np.abs(tau[sel]).max()))
+    amp = _interleave(cs[0]["amp"], cs[1]["amp"])
+    i = int(e_tau.max(1).argmax())
+    print("worst tau: robot %d (%s), %.2e of max(1,|tau|), max|tau| %.0f, its amplification %.1e; the five largest amplifications %s have tau errors %s"
+          % (i, ROBOTS[tid[i]], e_tau[i].max(), np.abs(tau[i]).max(), amp[i], np.sort(amp)[-5:], e_tau.max(1)[np.argsort(amp)[-5:]]))
+    assert np.all(out["status"] == 0), np.unique(out["status"])
+    assert np.all(e_tau <= 1e-6), (int(e_tau.max(1).argmax()), e_tau.max())
+    assert np.all(e_q <= 1e-5), e_q.max()
+    assert np.all(e_qdd <= 1e-4), e_qdd.max()
+    assert np.abs(tau[wide]).max() > 100.0          # the wide family is far off the stand pose
