@@ -664,6 +664,55 @@ int qrgpu_pose_plan_batch(qrgpu_ctx *ctx, int n, const qrgpu_pose_plan_desc *des
 int qrgpu_pack_state_batch(qrgpu_ctx *ctx, int n, const float com_offset[3], const float *d_est_in, const float *d_est_out, const float *d_rpy,
                            float *d_mpc_state, float *d_fb_state);
 
+/* ---- the plant: forward dynamics, ground contact, one control tick of the simulated robot -------------------------------------------------
+ * What turns the torque of tick t into the state of tick t + 1, so that a batch runs in closed loop on the device.  The model is the one
+ * qrgpu_wbc_setup uploads per type (base, 12 links, 12 rotors: BuildDynamicModel); both calls need a type set up there and follow the WBC's
+ * rule for d_type_id (QRGPU_ERR_NOT_SETUP when no type was set up; a robot with a bad id is computed with the first valid type and flagged).
+ *
+ * qrgpu_forward_dynamics_batch: FloatingBaseModel::runABA with _externalForces (floating_base_model.cpp:876-947), rotor terms included.
+ *   d_fb_state [37][n], d_tau [12][n], d_foot_force [12][n] (world-frame force on each foot point, 3*leg+axis; NULL = none)
+ *   d_nu_dot [18][n]: the time derivative of the components of (omega_body, v_body, qd): dBodyVelocity and qdd.  It satisfies
+ *   H nu_dot + C + G = [0; tau] + sum_leg Jc^T f.  The quaternion is normalised in fp64 on entry; arithmetic is fp64.
+ *
+ * qrgpu_plant_step_batch: d_fb_state advances in place by one control tick of params->substeps sub-steps of h = dt / substeps, each:
+ *   motor law (the Gazebo joint controller's): tau = clip(Kp (p - q) + Kd (d - qd) + tua, +-tau_max) from d_motor_cmd [QRGPU_MOTOR_CMD_ROWS][n]
+ *   contact law (OURS: the reference leaves the ground to its simulator): flat ground at ground_z; for a foot depth delta = ground_z - p_z > 0
+ *     f_n = max(0, contact_k delta (1 - contact_a v_z)),  f_t = -mu f_n v_t / sqrt(|v_t|^2 + v_eps^2);  zero otherwise (continuous in the state)
+ *   forward dynamics as above; semi-implicit Euler: nu += h nu_dot; q += h qd (new); pos += h R v_body (new v_body, R before the attitude
+ *     update); quat <- normalise(quat (x) exp(h omega_body)) (new omega_body)
+ *   The state is held in fp64 across the sub-steps: read once, written once as float32.
+ * Outputs, each may be NULL:
+ *   d_plant_out [QRGPU_PLANT_OUT_ROWS][n]: of the last sub-step foot force (world) [12], contact flag [4] (f_n > contact_threshold), applied
+ *     torque [12] and nu_dot [18], at rows 0, 24, 28, 40; of the state written, foot position (world) [12] at row 12
+ *   d_mpc_state [28][n]: the ground truth in qrgpu_pack_state_batch's conventions (foot vectors R (foot_b - com_offset); roll, pitch, yaw of
+ *     the float32 quaternion written)
+ *   d_est_in: rows 0-40 of est_in [54][n] without ReceiveObservation's filters: accelerometer (specific force at the base origin over the last
+ *     sub-step, base frame), baseLinearAcceleration (the same), quaternion, gyro, foot contact, q, qd.  Rows 41-53 are left alone.
+ *   d_status [n]: QRGPU_PL_* bits, 0 = fine.
+ * QRGPU_ERR_BAD_ARG (nothing launched): n < 1 or n > max_batch, a NULL required array, substeps outside 1..64, dt <= 0.
+ * Each call is one launch on the context's stream. */
+#define QRGPU_PLANT_OUT_ROWS 58
+#define QRGPU_PL_NONFINITE  0x1          /* a component of the result is not finite */
+#define QRGPU_PL_QUAT_ZERO  0x2          /* the quaternion read was zero or not finite: the identity was used */
+#define QRGPU_PL_BAD_TYPE   0x01000000   /* as QRGPU_ST_BAD_TYPE */
+typedef struct {
+    float dt;                   /* control tick, s */
+    int substeps;               /* 1..64 */
+    float contact_k;            /* N/m */
+    float contact_a;            /* s/m */
+    float mu;
+    float v_eps;                /* m/s */
+    float ground_z;
+    float tau_max;              /* N m */
+    float contact_threshold;    /* N */
+    float com_offset[3];
+} qrgpu_plant_params;
+void qrgpu_plant_params_default(qrgpu_plant_params *p);     /* 0.002, 2, 2e4, 1.0, 0.6, 0.01, 0, 33.5, 5.0, A1's com offset */
+int qrgpu_forward_dynamics_batch(qrgpu_ctx *ctx, int n, const int *d_type_id, const float *d_fb_state, const float *d_tau,
+                                 const float *d_foot_force, float *d_nu_dot, int *d_status);
+int qrgpu_plant_step_batch(qrgpu_ctx *ctx, int n, const qrgpu_plant_params *params, const int *d_type_id, float *d_fb_state,
+                           const float *d_motor_cmd, float *d_plant_out, float *d_mpc_state, float *d_est_in, int *d_status);
+
 /* ---- multi-GPU: all-gather of the per-robot torques over RCCL / xGMI ----------------------------------------
  * One process per GPU, one context per process; rank r of N owns a contiguous shard of the robot population and there is no exchange
  * inside a tick.  The only collective of the path collects every rank's tau[12][n_local] on every rank:

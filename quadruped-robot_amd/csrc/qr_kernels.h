@@ -74,4 +74,10 @@ __global__ void qr_stance_command_kernel(int n, qrgpu_stance_desc S, int stop, c
 __global__ void qr_pose_plan_kernel(int n, qrgpu_pose_plan_desc D, int event, const int *g_event, int reset, const float *g_est_in, const float *g_est_out,
                                     const float *g_ground, const float *g_rpy, const float *g_walk, float *g_state, float *g_cmd, float *g_out, int *g_flags);
 
+// qr_plant_kernel.hip: four lanes per robot, sixteen robots per workgroup of one wavefront
+__global__ void qr_fwd_dyn_kernel(int n, const WbcConst *types, const int *type_id, int type_ready, const float *g_state, const float *g_tau, const float *g_ff,
+                                  float *g_nudot, int *g_status);
+__global__ void qr_plant_step_kernel(int n, qrgpu_plant_params P, const WbcConst *types, const int *type_id, int type_ready, float *g_state, const float *g_cmd,
+                                     float *g_out, float *g_mpc, float *g_est, int *g_status);
+
 }  // namespace qrgpu

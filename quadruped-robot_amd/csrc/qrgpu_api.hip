@@ -154,7 +154,7 @@ static void lane_destroy(Lane &L)
     L = Lane{};
 }
 
-static int upload_wbc(qrgpu_ctx *c)
+int upload_wbc(qrgpu_ctx *c)
 {
     if (!c->wbc_dirty) return QRGPU_OK;
     HIPCHK(c, hipMemcpyAsync(c->d_wbc, c->wbc_host, sizeof(WbcConst) * QRGPU_MAX_TYPES, hipMemcpyHostToDevice, c->stream));

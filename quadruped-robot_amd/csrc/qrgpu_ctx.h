@@ -321,6 +321,7 @@ int launch_wbc(qrgpu_ctx *c, int n, const int *d_type, const float *d_state, con
                const WbcOpts &opt = WbcOpts{});                                                                            // qrgpu_api.hip
 int launch_vmc(qrgpu_ctx *c, int n, const int *d_type_id, const float *d_vmc_in, const float *d_ratio, const float *d_q, float *d_force, float *d_tau,
                int *d_status);                                                                                             // qrgpu_api.hip
+int upload_wbc(qrgpu_ctx *c);                              // qrgpu_api.hip: the per-type model constants on the device are those of the last qrgpu_wbc_setup
 hipError_t create_side_stream(hipStream_t *s);                                                                            // qrgpu_api.hip
 int lane_create(qrgpu_ctx *c, Lane &L, bool own_stream, bool masked = false);                                             // qrgpu_api.hip
 

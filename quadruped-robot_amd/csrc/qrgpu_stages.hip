@@ -1,6 +1,6 @@
 // ============================================================================
 // libqrgpu.so host side: the per-robot stages around the solves -- estimator, gaits, ground, footholds, swing, stance, pose planner, state
-// packing, MPC front-end -- and the defaults of their parameter blocks.  Every entry point is "check the arguments, normalise the block where
+// packing, MPC front-end, the plant -- and the defaults of their parameter blocks.  Every entry point is "check the arguments, normalise the block where
 // the reference does, one launch on the context's stream"; the kernels take the caller's blocks (include/qrgpu.h) by value.
 // ============================================================================
 #include <hip/hip_runtime.h>
@@ -323,6 +323,47 @@ int qrgpu_mpc_frontend_batch(qrgpu_ctx *c, int n, int num_horizon_l, float dt_ct
     if (!c->mpc_ready[0]) return QRGPU_ERR_NOT_SETUP;
     return launch_stage(c, qr_frontend_kernel, per_robot(n), dim3(64, c->mpc.horizon), n, c->mpc.horizon, num_horizon_l, dt_ctrl, dt_mpc, d_fe_in, d_fe_state, d_traj,
                         d_gait, d_wbc_cmd, d_mpc_updated);
+}
+
+void qrgpu_plant_params_default(qrgpu_plant_params *p)
+{
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->dt = 0.002f; p->substeps = 2;
+    p->contact_k = 2e4f; p->contact_a = 1.0f; p->mu = 0.6f; p->v_eps = 0.01f; p->ground_z = 0.f;
+    p->tau_max = 33.5f;                                                                                 // a1_description's joint effort limit
+    p->contact_threshold = 5.0f;                                                                        // qr_robot_a1_sim.cpp:662
+    p->com_offset[0] = -0.008f; p->com_offset[1] = 0.005f; p->com_offset[2] = 0.f;                      // config/a1_sim/a1_sim.yaml (A1's comOffset)
+}
+
+// The plant kernels read the model constants the WBC launch reads: the same readiness rule, the same upload.
+static int plant_model(qrgpu_ctx *c, const int *d_type_id)
+{
+    if (!(d_type_id ? ready_mask(c->wbc_ready) != 0 : c->wbc_ready[0])) return QRGPU_ERR_NOT_SETUP;
+    HIPCHK(c, hipSetDevice(c->device));
+    return upload_wbc(c);
+}
+static dim3 per_quad(int n) { return dim3((n + 15) / 16); }      // four lanes per robot, one wavefront per workgroup
+
+int qrgpu_forward_dynamics_batch(qrgpu_ctx *c, int n, const int *d_type_id, const float *d_fb_state, const float *d_tau, const float *d_foot_force,
+                                 float *d_nu_dot, int *d_status)
+{
+    if (!batch_ok(c, n) || !d_fb_state || !d_tau || !d_nu_dot) return QRGPU_ERR_BAD_ARG;
+    const int e = plant_model(c, d_type_id);
+    if (e != QRGPU_OK) return e;
+    return launch_stage(c, qr_fwd_dyn_kernel, per_quad(n), dim3(64), n, (const WbcConst *)c->d_wbc, d_type_id, ready_mask(c->wbc_ready), d_fb_state, d_tau, d_foot_force,
+                        d_nu_dot, d_status);
+}
+
+int qrgpu_plant_step_batch(qrgpu_ctx *c, int n, const qrgpu_plant_params *params, const int *d_type_id, float *d_fb_state, const float *d_motor_cmd,
+                           float *d_plant_out, float *d_mpc_state, float *d_est_in, int *d_status)
+{
+    if (!batch_ok(c, n) || !params || !d_fb_state || !d_motor_cmd) return QRGPU_ERR_BAD_ARG;
+    if (params->substeps < 1 || params->substeps > 64 || !(params->dt > 0.f)) return QRGPU_ERR_BAD_ARG;
+    const int e = plant_model(c, d_type_id);
+    if (e != QRGPU_OK) return e;
+    return launch_stage(c, qr_plant_step_kernel, per_quad(n), dim3(64), n, *params, (const WbcConst *)c->d_wbc, d_type_id, ready_mask(c->wbc_ready), d_fb_state,
+                        d_motor_cmd, d_plant_out, d_mpc_state, d_est_in, d_status);
 }
 
 }  // extern "C"

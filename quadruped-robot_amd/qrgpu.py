@@ -175,6 +175,22 @@ def pose_plan_desc(**fields):
     return _set_fields(d, fields)
 
 
+PLANT_OUT_ROWS = 58
+PL_NONFINITE, PL_QUAT_ZERO, PL_BAD_TYPE = 0x1, 0x2, 0x01000000
+
+
+class plant_params_struct(C.Structure):
+    _fields_ = [("dt", C.c_float), ("substeps", C.c_int), ("contact_k", C.c_float), ("contact_a", C.c_float), ("mu", C.c_float), ("v_eps", C.c_float),
+                ("ground_z", C.c_float), ("tau_max", C.c_float), ("contact_threshold", C.c_float), ("com_offset", C.c_float * 3)]
+
+
+def plant_params(**fields):
+    """qrgpu_plant_params: the library's defaults (A1, 2 ms ticks of 2 sub-steps), with any field overridden (scalars or sequences by name)."""
+    d = plant_params_struct()
+    load_library().qrgpu_plant_params_default(C.byref(d))
+    return _set_fields(d, fields)
+
+
 EPILOGUE_HIP_COMP, EPILOGUE_CLIP = 1, 2
 COMM_ID_BYTES = 128
 
@@ -206,7 +222,7 @@ EXPORTS = ["qrgpu_model_desc_default", "qrgpu_create", "qrgpu_destroy", "qrgpu_s
            "qrgpu_memcpy_async", "qrgpu_memset_async", "qrgpu_mark", "qrgpu_mark_elapsed_ms", "qrgpu_set_tick_pipeline", "qrgpu_set_tick_overlap",
            "qrgpu_tick_fence", "qrgpu_tick_overlap_stats", "qrgpu_swing_mode_desc_default", "qrgpu_swing_update_batch", "qrgpu_swing_action_batch",
            "qrgpu_stance_desc_default", "qrgpu_stance_update_batch", "qrgpu_stance_command_batch", "qrgpu_stance_tick_batch",
-           "qrgpu_pose_plan_desc_default", "qrgpu_pose_plan_batch"]
+           "qrgpu_pose_plan_desc_default", "qrgpu_pose_plan_batch", "qrgpu_plant_params_default", "qrgpu_forward_dynamics_batch", "qrgpu_plant_step_batch"]
 
 
 def load_library():
@@ -283,6 +299,9 @@ def load_library():
     lib.qrgpu_stance_tick_batch.argtypes = [vp, ip, C.POINTER(stance_desc_struct), C.c_float, ip, ip] + [vp] * 18
     lib.qrgpu_pose_plan_desc_default.argtypes = [C.POINTER(pose_plan_desc_struct)]; lib.qrgpu_pose_plan_desc_default.restype = None
     lib.qrgpu_pose_plan_batch.argtypes = [vp, ip, C.POINTER(pose_plan_desc_struct), ip, vp, ip] + [vp] * 9
+    lib.qrgpu_plant_params_default.argtypes = [C.POINTER(plant_params_struct)]; lib.qrgpu_plant_params_default.restype = None
+    lib.qrgpu_forward_dynamics_batch.argtypes = [vp, ip] + [vp] * 6
+    lib.qrgpu_plant_step_batch.argtypes = [vp, ip, C.POINTER(plant_params_struct)] + [vp] * 7
     lib.qrgpu_vmc_force1.argtypes = [vp, ip, fp, fp, fp, fp, C.POINTER(ip)]
     lib.qrgpu_vmc_force_world1.argtypes = [vp, ip, fp, fp, fp, fp, fp, C.POINTER(ip)]
     lib.qrgpu_mpc_frontend_batch.argtypes = [vp, ip, ip, C.c_float, C.c_float] + [vp] * 6
@@ -663,6 +682,18 @@ class Context:
         """mpc_state[28] / fb_state[37] from the estimator's inputs and outputs (SolveDenseMPC :385-399, UpdateModel :136-156)."""
         co = np.ascontiguousarray(com_offset, np.float32)
         self._chk(self._lib.qrgpu_pack_state_batch(self._h, n, _fp(co), _dp(est_in), _dp(est_out), _dp(rpy), _dp(mpc_state), _dp(fb_state)))
+
+    def forward_dynamics_batch(self, n, fb_state, tau, nu_dot, foot_force=None, status=None, type_id=None):
+        """nu_dot [18][n] = d/dt of (omega_body, v_body, qd) under tau [12][n] and the world-frame foot forces [12][n] (None: none):
+        FloatingBaseModel::runABA with _externalForces, rotor terms included."""
+        self._chk(self._lib.qrgpu_forward_dynamics_batch(self._h, n, _dp(type_id), _dp(fb_state), _dp(tau), _dp(foot_force), _dp(nu_dot), _dp(status)))
+
+    def plant_step_batch(self, n, params, fb_state, motor_cmd, plant_out=None, mpc_state=None, est_in=None, status=None, type_id=None):
+        """fb_state [37][n] advances in place by one control tick of the simulated robots (params: plant_params()): motor law on motor_cmd
+        [60][n], ground contact, forward dynamics, semi-implicit Euler.  plant_out [PLANT_OUT_ROWS][n], the ground-truth mpc_state [28][n]
+        and rows 0-40 of est_in [54][n] are written when given."""
+        self._chk(self._lib.qrgpu_plant_step_batch(self._h, n, C.byref(params), _dp(type_id), _dp(fb_state), _dp(motor_cmd), _dp(plant_out),
+                                                   _dp(mpc_state), _dp(est_in), _dp(status)))
 
     def mpc_frontend_batch(self, n, fe_in, fe_state, traj, gait, wbc_cmd=None, mpc_updated=None, num_horizon_l=2, dt_ctrl=0.002, dt_mpc=0.06):
         """SetupCommand + Run + UpdateMPC (without the solve) of n robots: qr_mpc_stance_leg_controller.cpp:158-382."""

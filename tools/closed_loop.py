@@ -1,0 +1,100 @@
+#!/usr/bin/env python3
+"""n simulated A1 robots in closed loop on one GPU: plant -> truth mpc_state -> qrgpu_tick_batch -> plant, tick after tick, with no host copy
+inside the loop.
+
+  python tools/closed_loop.py [--robots 1024] [--ticks 500] [--substeps 2]            prints ONE JSON line
+  rocprofv3 --kernel-trace --stats -d DIR -- python tools/closed_loop.py --profile    the same loop as the workload of a kernel trace
+
+The robots are dropped from z = 0.30 onto joint PD at the stand pose (400 ticks of 1 ms), shoved by up to 0.3 m/s in x and y, and handed to
+MPC + WBC: qrgpu_plant_step_batch (include/qrgpu.h) writes the ground-truth mpc_state and fb_state the tick reads, and the tick -- the plain
+one: pipelined, consecutive ticks not overlapped -- writes its torque straight into rows 48-59 of the motor command the plant reads.  All-stance
+gait, a trajectory and a WBC command that hold the origin at height 0.27, warm start on.
+
+  ticks_per_s   closed-loop control ticks per second: every robot advances one tick per (plant step + controller tick)
+  in_band       share of the robots that end inside the stand band: |z - 0.27| <= 0.01, |x|, |y| <= 0.03, |roll|, |pitch| <= 0.03
+"""
+import argparse
+import importlib.util
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+STAND_POSE = np.tile(np.array([0.0, 0.8, -1.6], np.float32), 4)
+HEIGHT, HORIZON = 0.27, 10
+
+
+def _load_pkg():
+    d = os.path.join(ROOT, "quadruped-robot_amd")
+    spec = importlib.util.spec_from_file_location("quadruped_robot_amd", os.path.join(d, "__init__.py"), submodule_search_locations=[d])
+    mod = importlib.util.module_from_spec(spec)
+    sys.modules["quadruped_robot_amd"] = mod
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def _rpy(q):
+    q0, q1, q2, q3 = (q[:, k].astype(np.float64) for k in range(4))
+    return np.stack([np.arctan2(2 * (q2 * q3 + q0 * q1), q0 * q0 - q1 * q1 - q2 * q2 + q3 * q3), np.arcsin(np.clip(-2 * (q1 * q3 - q0 * q2), -1, 1))], 1)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--robots", type=int, default=1024)
+    ap.add_argument("--ticks", type=int, default=500, help="closed-loop ticks of 2 ms, timed")
+    ap.add_argument("--substeps", type=int, default=2)
+    ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--profile", action="store_true", help="the run a profiler traces: fewer ticks, nothing else changed")
+    a = ap.parse_args()
+    pkg = _load_pkg()
+    pkg._build.build()
+    n, h = a.robots, HORIZON
+    ticks = min(a.ticks, 100) if a.profile else a.ticks
+    ctx = pkg.Context(device_id=0, max_batch=n, horizon_max=16)
+    ctx.mpc_setup_packed(0, pkg.mpc_cfg("a1"), h)
+    ctx.wbc_setup_packed(0, pkg.model_desc("a1"))
+    fb0 = np.zeros((37, n), np.float32); fb0[0] = 1.0; fb0[6] = 0.30; fb0[13:25] = STAND_POSE[:, None]
+    cmd0 = np.zeros((60, n), np.float32); cmd0[0:12] = STAND_POSE[:, None]; cmd0[12:24] = 100.0; cmd0[36:48] = 2.0
+    traj = np.zeros((h, 12, n), np.float32); traj[:, 5] = HEIGHT
+    wcmd = np.zeros((67, n), np.float32); wcmd[2] = HEIGHT; wcmd[63:67] = 1.0
+    d = dict(fb=ctx.alloc((37, n)).upload(fb0), cmd=ctx.alloc((60, n)).upload(cmd0), mpc=ctx.alloc((28, n)), out=ctx.alloc((pkg.qrgpu.PLANT_OUT_ROWS, n)),
+             traj=ctx.alloc((12 * h, n)).upload(traj.reshape(12 * h, n)), gait=ctx.alloc((4 * h, n)).upload(np.ones((4 * h, n), np.float32)),
+             wcmd=ctx.alloc((67, n)).upload(wcmd), prev=ctx.alloc((3, n)).zero(), force=ctx.alloc((12, n)),
+             tick_status=ctx.alloc((n,), np.int32), plant_status=ctx.alloc((n,), np.int32), flags=ctx.alloc((2, n), np.int32))
+    settle = pkg.plant_params(dt=0.001, substeps=1)
+    for _ in range(400):
+        ctx.plant_step_batch(n, settle, d["fb"], d["cmd"], mpc_state=d["mpc"])
+    ctx.sync()
+    fb = d["fb"].download()
+    rng = np.random.default_rng(a.seed)
+    fb[10:12] += rng.uniform(-0.3, 0.3, (2, n)).astype(np.float32)
+    d["fb"].upload(fb); d["cmd"].zero()
+    ctx.set_warm_start(True)
+    params = pkg.plant_params(dt=0.002, substeps=a.substeps)
+    tau = d["cmd"].row(48)
+
+    def loop(k):
+        for _ in range(k):
+            ctx.plant_step_batch(n, params, d["fb"], d["cmd"], plant_out=d["out"], mpc_state=d["mpc"], status=d["plant_status"])
+            ctx.tick_batch(n, d["mpc"], d["traj"], d["gait"], d["fb"], d["wcmd"], d["prev"], d["force"], tau, d["tick_status"])
+
+    loop(20)                                                          # warm-up: the first launches, the scheduler's history
+    ctx.sync()
+    t0 = time.perf_counter()
+    loop(ticks)
+    ctx.sync()
+    sec = time.perf_counter() - t0
+    fb = d["fb"].download()
+    rp = _rpy(fb[0:4].T)
+    ok = (np.abs(fb[6] - HEIGHT) <= 0.01) & (np.abs(fb[4:6]).max(0) <= 0.03) & (np.abs(rp).max(1) <= 0.03)
+    tick_flags = pkg.status_flags(d["tick_status"].download()); plant_flags = d["plant_status"].download()
+    print(json.dumps(dict(metric="closed_loop_ticks_per_s", value=ticks / sec, robot_ticks_per_s=n * ticks / sec, ms_per_tick=1e3 * sec / ticks, robots=n, ticks=ticks,
+                          substeps=a.substeps, in_band=float(ok.mean()), last_tick_flagged=int(((tick_flags != 0) | (plant_flags != 0)).sum()), profile=bool(a.profile))))
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
