@@ -88,12 +88,6 @@ __device__ __forceinline__ float det2(float a, float b, float c, float d)
     return __builtin_fmaf(a, b, -(c * d));
 }
 
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 __device__ __forceinline__ int tri(int i) { return (i * (i + 1)) >> 1; }
 __device__ __forceinline__ int pidx(int i, int j) { return i >= j ? tri(i) + j : tri(j) + i; }
 
@@ -127,6 +121,7 @@ __device__ __forceinline__ void load_block(const double *Mb, int k, int kc, Blk 
 // Column j of the analytic leg Jacobian of leg `leg` (AnalyticalLegJacobian, QS/robots/qr_robot.cpp:148-172) from the joint angles in HBM:
 // thread (leg, j) of phase 0 stores it in LDS, so that the torque map at the very end is three multiply-adds instead of a global-memory
 // round trip and twenty sinf / cosf on the critical path of every robot.
+// (The expressions are leg_jacobian_column's, qr_wave_helpers.h; written out here because calling it moves the schedule of the 128-VGPR main pass.)
 __device__ __forceinline__ void mpc_jacobian_column(int leg, int j, int rid, int n, const MpcType &C, const float *__restrict__ g_q, float *sJ3)
 {
     const float t0 = g_q[(size_t)(3 * leg) * n + rid], t1 = g_q[(size_t)(3 * leg + 1) * n + rid], t2 = g_q[(size_t)(3 * leg + 2) * n + rid];
@@ -151,23 +146,7 @@ __device__ __forceinline__ void mpc_jacobian_column(int leg, int j, int rid, int
     sJ3[0] = J0; sJ3[1] = J1; sJ3[2] = J2;
 }
 
-// epilogue (MPC-only batches; in the fused tick the WBC kernel applies it after the stance/swing merge): bit 0 = the +-0.9 N m abad
-// compensation of qrFSMStateLocomotion::Run (QS/fsm/qr_fsm_state_locomotion.cpp:141-151), bit 1 = the +-23 N m clip of
-// qrSafetyChecker::CheckForceFeedForward (QS/fsm/qr_safety_checker.cpp:48-66); legCmd.tua is a double there.
-__device__ __forceinline__ float torque_epilogue(float tau, int motor, bool comp, int epilogue)
-{
-    double t = (double)tau;
-    if (comp && (epilogue & 1) && motor % 3 == 0) t += (double)(((motor / 3) & 1) ? 0.9f : -0.9f);     // tua_ * pow(-1, (leg + 1) % 2)
-    if (epilogue & 2) t = t > 23.0 ? 23.0 : (t < -23.0 ? -23.0 : t);
-    return (float)t;
-}
-
-// (st_out: a plain store, or -- pipelined tick, where another launch reads the value while this one still runs -- an agent-scope one:
-//  global_store ... sc1, written through to memory)
-__device__ __forceinline__ void st_out(float *p, float v, bool through)
-{
-    if (through) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); else *p = v;
-}
+// (epilogue: MPC-only batches; in the fused tick the WBC kernel applies torque_epilogue after the stance/swing merge)
 __device__ __forceinline__ void mpc_outputs(int lane, int rid, int n, const double *yl, const float (&R)[3][3], const float *sJ, const MpcType &C,
                                             const float *__restrict__ g_q, float *__restrict__ g_force, float *__restrict__ g_force_wbc,
                                             int force_stride, float *__restrict__ g_tau, int epilogue, bool through = false)
@@ -175,7 +154,7 @@ __device__ __forceinline__ void mpc_outputs(int lane, int rid, int n, const doub
     if (lane < 12) {
         const int leg = lane / 3;
         const float fx = (float)yl[3 * leg], fy = (float)yl[3 * leg + 1], fz = (float)yl[3 * leg + 2];
-        st_out(&g_force[(size_t)lane * n + rid], (float)yl[lane], through);
+        st_through(&g_force[(size_t)lane * n + rid], (float)yl[lane], through);
         if (g_force_wbc) g_force_wbc[(size_t)(force_stride + lane) * n + rid] = (float)yl[lane];
         if (g_tau) {
             // f_ff = -R^T f  (R^T = quaternionToRotationMatrix(quat)), tau = J^T f_ff
@@ -186,7 +165,7 @@ __device__ __forceinline__ void mpc_outputs(int lane, int rid, int n, const doub
             if (!sJ) mpc_jacobian_column(leg, lane - 3 * leg, rid, n, C, g_q, Jl);      // (h = 16 variants: no LDS to spare for the early copy)
             const float J0 = sJ ? sJ[3 * lane] : Jl[0], J1 = sJ ? sJ[3 * lane + 1] : Jl[1], J2 = sJ ? sJ[3 * lane + 2] : Jl[2];
             const float tq = J0 * fff[0] + J1 * fff[1] + J2 * fff[2];
-            st_out(&g_tau[(size_t)lane * n + rid], epilogue ? torque_epilogue(tq, lane, true, epilogue) : tq, through);
+            st_through(&g_tau[(size_t)lane * n + rid], epilogue ? torque_epilogue(tq, lane, true, epilogue) : tq, through);
         }
     }
 }
@@ -203,10 +182,6 @@ __device__ __forceinline__ void mpc_outputs(int lane, int rid, int n, const doub
 template <typename T> __device__ __forceinline__ T ld_xt(const T *p, bool xt)
 {
     return xt ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *p;
-}
-template <typename T> __device__ __forceinline__ void st_xt(T *p, T v, bool xt)
-{
-    if (xt) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); else *p = v;
 }
 __device__ __forceinline__ void lpt_order_chunk(int x, int n, const int *__restrict__ cost, int *__restrict__ order, int *hist /* >= 2048 ints of LDS */)
 {
@@ -329,18 +304,8 @@ __device__ __forceinline__ void mpc_solve_robot(const MpcLaunch &P, const MpcIO 
     // ---------------- phase 1: SRBD terms ----------------
     // R = quat.toRotationMatrix() from the quaternion: phases 1-2 keep it in registers; the output phase, a whole active set later, forms it
     // again from the copy of the quaternion in sMisc[4..7] (nine VGPRs less to carry -- and spill -- through the 128-register main pass)
-    auto quat_to_R = [](float w, float x, float y, float z, float (&R)[3][3]) {
-#pragma clang fp contract(off)
-        const float tx = 2.f * x, ty = 2.f * y, tz = 2.f * z;
-        const float twx = tx * w, twy = ty * w, twz = tz * w;
-        const float txx = tx * x, txy = ty * x, txz = tz * x;
-        const float tyy = ty * y, tyz = tz * y, tzz = tz * z;
-        R[0][0] = 1.f - (tyy + tzz); R[0][1] = txy - twz;         R[0][2] = txz + twy;
-        R[1][0] = txy + twz;         R[1][1] = 1.f - (txx + tzz); R[1][2] = tyz - twx;
-        R[2][0] = txz - twy;         R[2][1] = tyz + twx;         R[2][2] = 1.f - (txx + tyy);
-    };
     float R[3][3];
-    quat_to_R(sSt[6], sSt[7], sSt[8], sSt[9], R);
+    quat_to_rot(sSt[6], sSt[7], sSt[8], sSt[9], R);
     if (tid < 4) ((float *)sMisc)[4 + tid] = sSt[6 + tid];
     const float dt = C.dt, dt2 = C.dt * C.dt, minv = 1.0f / C.mass;
     if (tid < 4) {
@@ -502,12 +467,12 @@ __device__ __forceinline__ void mpc_solve_robot(const MpcLaunch &P, const MpcIO 
         // per CU and an all-stance robot): nothing is computed here, the robot goes to the list pass at once -- and, through the `big`
         // bit, onto the planned list of the next call
         if (tid == 0) {
-            if (io.g_status) st_xt(io.g_status + rid, st | QRGPU_ST_MPC_OVERFLOW, P.main_done != nullptr);      // (its rescuer may already be running: not behind that one's word)
+            if (io.g_status) st_through(io.g_status + rid, st | QRGPU_ST_MPC_OVERFLOW, P.main_done != nullptr);      // (its rescuer may already be running: not behind that one's word)
             if (P.main_done) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             QR_TRACE(rid, 4 | (P.rescue_mode << 8));
-            if (P.rescue_list && !P.rescue_mode) st_xt(P.rescue_list + atomicAdd(P.rescue_count + P.rescue_parity, 1), rid, P.solved != nullptr);
+            if (P.rescue_list && !P.rescue_mode) st_through(P.rescue_list + atomicAdd(P.rescue_count + P.rescue_parity, 1), rid, P.solved != nullptr);
             else if (P.solved) qr_epoch_raise(P.solved + rid, P.solved_epoch);      // (nobody solves it again this tick)
-            if (P.cost) st_xt(P.cost + rid, 255 | (P.pre_list ? 256 : 0) | (0xff0 << 16), P.solved != nullptr);
+            if (P.cost) st_through(P.cost + rid, 255 | (P.pre_list ? 256 : 0) | (0xff0 << 16), P.solved != nullptr);
             if (P.done_flag) __hip_atomic_store(P.done_flag + rid, (P.done_epoch << 1) | 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (QR_P_FTIME) QR_P_FTIME[rid] = (int)wall_clock64();
         }
@@ -595,12 +560,12 @@ __device__ __forceinline__ void mpc_solve_robot(const MpcLaunch &P, const MpcIO 
     if ((long long)NT * NT * 1024 > (long long)P.lds_bytes - (long long)((Mb - smem) * 8)) {
         // (h = 11 all stance in the main pass's half-CU allotment: to the list pass, like a robot whose S^-1 does not fit)
         if (tid == 0) {
-            if (io.g_status) st_xt(io.g_status + rid, st | QRGPU_ST_MPC_OVERFLOW, P.main_done != nullptr);      // (its rescuer may already be running: not behind that one's word)
+            if (io.g_status) st_through(io.g_status + rid, st | QRGPU_ST_MPC_OVERFLOW, P.main_done != nullptr);      // (its rescuer may already be running: not behind that one's word)
             if (P.main_done) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             QR_TRACE(rid, 4 | (P.rescue_mode << 8));
-            if (P.rescue_list && !P.rescue_mode) st_xt(P.rescue_list + atomicAdd(P.rescue_count + P.rescue_parity, 1), rid, P.solved != nullptr);
+            if (P.rescue_list && !P.rescue_mode) st_through(P.rescue_list + atomicAdd(P.rescue_count + P.rescue_parity, 1), rid, P.solved != nullptr);
             else if (P.solved) qr_epoch_raise(P.solved + rid, P.solved_epoch);      // (nobody solves it again this tick)
-            if (P.cost) st_xt(P.cost + rid, 255 | (P.pre_list ? 256 : 0) | (0xff0 << 16), P.solved != nullptr);
+            if (P.cost) st_through(P.cost + rid, 255 | (P.pre_list ? 256 : 0) | (0xff0 << 16), P.solved != nullptr);
             if (P.done_flag) __hip_atomic_store(P.done_flag + rid, (P.done_epoch << 1) | 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (QR_P_FTIME) QR_P_FTIME[rid] = (int)wall_clock64();
         }
@@ -1684,7 +1649,7 @@ __device__ __forceinline__ void mpc_solve_robot(const MpcLaunch &P, const MpcIO 
         {
             float Ro[3][3];
             const float *qs = (const float *)sMisc + 4;
-            quat_to_R(qs[0], qs[1], qs[2], qs[3], Ro);
+            quat_to_rot(qs[0], qs[1], qs[2], qs[3], Ro);
             mpc_outputs(lane, rid, n, xz, Ro, sJ, C, io.g_q, io.g_force, io.g_force_wbc, io.force_stride, io.g_tau, P.epilogue, P.done_flag != nullptr);
         }
         if (lane == 0 && io.g_status) {
@@ -1693,7 +1658,7 @@ __device__ __forceinline__ void mpc_solve_robot(const MpcLaunch &P, const MpcIO 
         }
         if (to_rescue && P.main_done) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (its rescuer may start at once: everything this solve stored is out first)
         if (lane == 0 && to_rescue) QR_TRACE(rid, 64);
-        if (lane == 0 && to_rescue) st_xt(P.rescue_list + atomicAdd(P.rescue_count + P.rescue_parity, 1), rid, P.solved != nullptr);
+        if (lane == 0 && to_rescue) st_through(P.rescue_list + atomicAdd(P.rescue_count + P.rescue_parity, 1), rid, P.solved != nullptr);
         if (P.done_flag) {
             // pipelined tick: the forces, torques and status word of this robot are on their way to memory (write-through stores of this very
             // wave): wait for them, then raise the robot's flag for the WBC workgroup that is waiting for it (or, for a robot on its way to the
@@ -1807,8 +1772,8 @@ void qr_mpc_kernel(MpcLaunch P, MpcIO io)
                 const int chunk = (P.n + 7) >> 3, lo = blockIdx.x * chunk, hi = (lo + chunk < P.n) ? lo + chunk : P.n;
                 for (int i = lo + threadIdx.x; i < hi; i += NTHR) {
                     const int big = (ld_xt(P.lpt_cost_in + i, P.solved != nullptr) >> 8) & 1;
-                    st_xt(P.skip + i, (unsigned char)big, P.solved != nullptr);
-                    if (big) st_xt(P.pre_list + P.pre_list_next + atomicAdd(P.pre_count + (P.rescue_parity ^ 1), 1), i, P.solved != nullptr);
+                    st_through(P.skip + i, (unsigned char)big, P.solved != nullptr);
+                    if (big) st_through(P.pre_list + P.pre_list_next + atomicAdd(P.pre_count + (P.rescue_parity ^ 1), 1), i, P.solved != nullptr);
                 }
                 __syncthreads();
                 // the last of the eight planning workgroups tells the host how long the list is (a write to pinned host memory: no copy
@@ -1944,9 +1909,9 @@ void qr_mpc_kernel(MpcLaunch P, MpcIO io)
             return;
         }
         if (blockIdx.x == 0 && threadIdx.x == 0) {     // the next call's counters
-            if (P.rescue_count) st_xt(P.rescue_count + (P.rescue_parity ^ 1), 0, P.solved != nullptr);
-            if (P.rescue_taken) { st_xt(P.rescue_taken + (P.rescue_parity ^ 1), 0, true); st_xt(P.rescue_taken + 2 + (P.rescue_parity ^ 1), 0, true); }
-            if (P.pre_count) { st_xt(P.pre_count + (P.rescue_parity ^ 1), 0, P.solved != nullptr); st_xt(P.pre_count + 2, 0, P.solved != nullptr); }
+            if (P.rescue_count) st_through(P.rescue_count + (P.rescue_parity ^ 1), 0, P.solved != nullptr);
+            if (P.rescue_taken) { st_through(P.rescue_taken + (P.rescue_parity ^ 1), 0, true); st_through(P.rescue_taken + 2 + (P.rescue_parity ^ 1), 0, true); }
+            if (P.pre_count) { st_through(P.pre_count + (P.rescue_parity ^ 1), 0, P.solved != nullptr); st_through(P.pre_count + 2, 0, P.solved != nullptr); }
         }
         const int slot = xcd_robot_index(blockIdx.x, P.n);
         if (slot >= 0) {
@@ -1977,8 +1942,8 @@ void qr_mpc_persist_kernel(MpcLaunch P, MpcIO io)
     volatile int *sNext = (volatile int *)smem;        // (the head of the dynamic LDS, dead between two solves: a static word would push the second workgroup off the CU)
     if (QR_P_TL && threadIdx.x == 0) atomicMin(QR_P_TL + QR_TL_TICKS + (P.done_epoch & 63u) * 8, wall_clock64());
     if (blockIdx.x == 0 && threadIdx.x == 0) {         // the next call's counters
-        if (P.rescue_count) st_xt(P.rescue_count + (P.rescue_parity ^ 1), 0, P.solved != nullptr);
-        if (P.pre_count) { st_xt(P.pre_count + (P.rescue_parity ^ 1), 0, P.solved != nullptr); st_xt(P.pre_count + 2, 0, P.solved != nullptr); }
+        if (P.rescue_count) st_through(P.rescue_count + (P.rescue_parity ^ 1), 0, P.solved != nullptr);
+        if (P.pre_count) { st_through(P.pre_count + (P.rescue_parity ^ 1), 0, P.solved != nullptr); st_through(P.pre_count + 2, 0, P.solved != nullptr); }
     }
     if (blockIdx.x == 0 && threadIdx.x < 8) P.qhead_next[threadIdx.x] = 0;
     const int xcc = (int)(__builtin_amdgcn_s_getreg(20 | (3 << 11)) & 7u);      // HW_REG_XCC_ID[3:0]

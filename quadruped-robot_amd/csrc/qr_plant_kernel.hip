@@ -52,8 +52,7 @@ __device__ __forceinline__ Who who_am_i(int n, const WbcConst *types, const int 
     w.robot = w.live ? robot : n - 1;
     w.leg = threadIdx.x & 3;
     int tyid = type_id ? type_id[w.robot] : 0;
-    const bool bad_type = tyid < 0 || tyid >= QRGPU_MAX_TYPES || !((type_ready >> (tyid & (QRGPU_MAX_TYPES - 1))) & 1);
-    if (bad_type) tyid = __builtin_ctz(type_ready | (1 << QRGPU_MAX_TYPES));
+    const bool bad_type = resolve_type(tyid, type_ready);
     w.flags = bad_type ? QRGPU_PL_BAD_TYPE : 0;
     w.K = types + (tyid & (QRGPU_MAX_TYPES - 1));
     return w;
@@ -69,7 +68,7 @@ __device__ __forceinline__ void unit_quat(real &w, real &x, real &y, real &z, in
 }
 
 // Forward dynamics of one robot across its quad, after leg_start: this lane's leg in, the base's and this leg's accelerations out.
-__device__ __forceinline__ void forward_dynamics(const WbcConst &K, int leg, const Stash &st, const m3 &R, sv6 v0, real qd0, real qd1, real qd2, real tau0,
+__device__ __forceinline__ void forward_dynamics(const WbcConst &K, int leg, const Stash &st, const frame3 &R, sv6 v0, real qd0, real qd1, real qd2, real tau0,
                                                  real tau1, real tau2, v3 f_b, sv6 &afb, real &qdd0, real &qdd1, real &qdd2)
 {
     abi IA;
@@ -101,7 +100,7 @@ __global__ void __launch_bounds__(64) qr_fwd_dyn_kernel(int n, const WbcConst *_
     const int i = w.robot, leg = w.leg, j = 3 * leg;
     real qw = ROW(g_state, 0), qx = ROW(g_state, 1), qy = ROW(g_state, 2), qz = ROW(g_state, 3);
     unit_quat(qw, qx, qy, qz, w.flags);
-    const m3 R = quat_to_rot(qw, qx, qy, qz);
+    const frame3 R = quat_to_rot(qw, qx, qy, qz);
     sv6 v0;
     v0.a = mk(ROW(g_state, 7), ROW(g_state, 8), ROW(g_state, 9));
     v0.l = mk(ROW(g_state, 10), ROW(g_state, 11), ROW(g_state, 12));
@@ -159,7 +158,7 @@ __global__ void __launch_bounds__(64) qr_plant_step_kernel(int n, qrgpu_plant_pa
     real fn = 0, tau0 = 0, tau1 = 0, tau2 = 0, qdd0 = 0, qdd1 = 0, qdd2 = 0;
 #pragma unroll 1
     for (int s = 0; s < P.substeps; ++s) {
-        const m3 R = quat_to_rot(qw, qx, qy, qz);
+        const frame3 R = quat_to_rot(qw, qx, qy, qz);
         tau0 = clip(kp0 * (cp0 - q0) + kd0 * (cd0 - qd0) + ff0, tau_max);
         tau1 = clip(kp1 * (cp1 - q1) + kd1 * (cd1 - qd1) + ff1, tau_max);
         tau2 = clip(kp2 * (cp2 - q2) + kd2 * (cd2 - qd2) + ff2, tau_max);
@@ -203,7 +202,7 @@ __global__ void __launch_bounds__(64) qr_plant_step_kernel(int n, qrgpu_plant_pa
     }
     if (leg == 2 && g_status) g_status[i] = w.flags;
     // the foot of the state just written
-    const m3 R = quat_to_rot(qw, qx, qy, qz);
+    const frame3 R = quat_to_rot(qw, qx, qy, qz);
     v3 foot_b, foot_vel;
     leg_start(K, leg, st, q0, q1, q2, qd0, qd1, qd2, v0, foot_b, foot_vel);
     const v3 foot_w = pos + mul(R, foot_b);

@@ -1,6 +1,6 @@
-// 3-vector, rigid-body-inertia and spatial-vector algebra of the plant kernels (qr_plant_kernel.hip), and the articulated-body forward dynamics
-// of one leg on top of it.  fp64 throughout.  Every function is __host__ __device__: the same text compiles for a CPU check against the float64
-// mechanics of tests/rigid_body_ref.py.
+// What is the plant kernels' own (qr_plant_kernel.hip) on top of the shared algebra of qr_rigid_body.h: the column-vector rotation, articulated-body
+// inertias, the articulated-body forward dynamics of one leg and the contact law.  fp64 throughout.  Every function is __host__ __device__: the
+// same text compiles for a CPU check against the float64 mechanics of tests/rigid_body_ref.py.
 //
 // Coordinates: Featherstone's link coordinates.  A link's frame sits at its joint, so a link's inertia is a constant and its joint axis a unit
 // vector; what passes between a link and its parent goes through the joint's transform (a rotation about a coordinate axis and a constant
@@ -11,13 +11,10 @@
 //   force vector  (a; l): moment about the frame's origin; force
 #pragma once
 #include "qr_device_types.h"
-
-#define QR_HD __host__ __device__ __forceinline__
+#include "qr_rigid_body.h"
 
 namespace qrgpu {
 namespace plant {
-
-typedef double real;
 
 // Rotor data BuildDynamicModel gives every robot (QS/robots/qr_robot_a1_sim.cpp:184-189, :243) beyond what WbcConst carries: float literals, widened.
 #define QR_PL_ROTOR_MASS   ((double)1e-8f)
@@ -26,55 +23,27 @@ typedef double real;
 #define QR_PL_HIP_ROTOR_Y  ((double)0.04f)
 #define QR_PL_GRAVITY      9.81
 
-struct v3 { real x, y, z; };
-QR_HD v3 mk(real x, real y, real z) { v3 r = {x, y, z}; return r; }
-QR_HD v3 operator+(v3 a, v3 b) { return mk(a.x + b.x, a.y + b.y, a.z + b.z); }
-QR_HD v3 operator-(v3 a, v3 b) { return mk(a.x - b.x, a.y - b.y, a.z - b.z); }
-QR_HD v3 operator*(real s, v3 a) { return mk(s * a.x, s * a.y, s * a.z); }
-QR_HD v3 cross(v3 a, v3 b) { return mk(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
-QR_HD real dot(v3 a, v3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-
-// Rotation matrix, columns c0 c1 c2 (a frame's axes in its parent's coordinates).
-struct m3 { v3 c0, c1, c2; };
-QR_HD v3 mul(const m3 &R, v3 b) { return b.x * R.c0 + (b.y * R.c1 + b.z * R.c2); }
-QR_HD v3 mulT(const m3 &R, v3 b) { return mk(dot(R.c0, b), dot(R.c1, b), dot(R.c2, b)); }
-QR_HD m3 mul(const m3 &A, const m3 &B) { m3 C; C.c0 = mul(A, B.c0); C.c1 = mul(A, B.c1); C.c2 = mul(A, B.c2); return C; }
-QR_HD m3 rot_x(real s, real c) { m3 R; R.c0 = mk(1, 0, 0); R.c1 = mk(0, c, s); R.c2 = mk(0, -s, c); return R; }
-QR_HD m3 rot_y(real s, real c) { m3 R; R.c0 = mk(c, 0, -s); R.c1 = mk(0, 1, 0); R.c2 = mk(s, 0, c); return R; }
+// Rotation matrix as three column vectors c0 c1 c2 (a frame's axes in its parent's coordinates); a product with a vector is summed
+// b.x c0 + (b.y c1 + b.z c2).  (The WBC chains' xform3 is row-major and sums (a0 b0 + a1 b1) + a2 b2: the two are kept apart.)
+struct frame3 { v3 c0, c1, c2; };
+QR_HD v3 mul(const frame3 &R, v3 b) { return b.x * R.c0 + (b.y * R.c1 + b.z * R.c2); }
+QR_HD v3 mulT(const frame3 &R, v3 b) { return mk(dot(R.c0, b), dot(R.c1, b), dot(R.c2, b)); }
+QR_HD frame3 mul(const frame3 &A, const frame3 &B) { frame3 C; C.c0 = mul(A, B.c0); C.c1 = mul(A, B.c1); C.c2 = mul(A, B.c2); return C; }
+QR_HD frame3 rot_x(real s, real c) { frame3 R; R.c0 = mk(1, 0, 0); R.c1 = mk(0, c, s); R.c2 = mk(0, -s, c); return R; }
+QR_HD frame3 rot_y(real s, real c) { frame3 R; R.c0 = mk(c, 0, -s); R.c1 = mk(0, 1, 0); R.c2 = mk(s, 0, c); return R; }
 // body-to-world rotation of a unit quaternion (w, x, y, z)
-QR_HD m3 quat_to_rot(real w, real x, real y, real z)
+QR_HD frame3 quat_to_rot(real w, real x, real y, real z)
 {
-    m3 R;
+    frame3 R;
     R.c0 = mk(1 - 2 * (y * y + z * z), 2 * (x * y + w * z), 2 * (x * z - w * y));
     R.c1 = mk(2 * (x * y - w * z), 1 - 2 * (x * x + z * z), 2 * (y * z + w * x));
     R.c2 = mk(2 * (x * z + w * y), 2 * (y * z - w * x), 1 - 2 * (x * x + y * y));
     return R;
 }
 
-// Spatial vector (angular; linear) and the two cross products.
-struct sv6 { v3 a, l; };
-QR_HD sv6 operator+(sv6 u, sv6 v) { sv6 o; o.a = u.a + v.a; o.l = u.l + v.l; return o; }
-QR_HD sv6 operator*(real s, sv6 v) { sv6 o; o.a = s * v.a; o.l = s * v.l; return o; }
-QR_HD real dot(sv6 u, sv6 v) { return dot(u.a, v.a) + dot(u.l, v.l); }
-QR_HD sv6 crm(sv6 v, sv6 u) { sv6 o; o.a = cross(v.a, u.a); o.l = cross(v.a, u.l) + cross(v.l, u.a); return o; }   // v x u   (motion)
-QR_HD sv6 crf(sv6 v, sv6 f) { sv6 o; o.a = cross(v.a, f.a) + cross(v.l, f.l); o.l = cross(v.a, f.l); return o; }   // v x* f  (force)
 // the axis `ax` through the point `p` as a motion vector
 QR_HD sv6 axis_at(v3 ax, v3 p) { sv6 o; o.a = ax; o.l = cross(p, ax); return o; }
 
-// Rigid-body inertia [[Ibar, [h]x], [[h]x^T, m 1]] as (m, h = m c, Ibar about the origin: xx yy zz xy xz yz).
-struct rbi { real m; v3 h; real I[6]; };
-QR_HD v3 sym_mul(const real I[6], v3 w)
-{
-    return mk(I[0] * w.x + I[3] * w.y + I[4] * w.z, I[3] * w.x + I[1] * w.y + I[5] * w.z, I[4] * w.x + I[5] * w.y + I[2] * w.z);
-}
-QR_HD rbi rbi_load(const real *p)
-{
-    rbi r; r.m = p[0]; r.h = mk(p[1], p[2], p[3]);
-#pragma unroll
-    for (int i = 0; i < 6; ++i) r.I[i] = p[4 + i];
-    return r;
-}
-QR_HD sv6 rbi_mul(const rbi &I, sv6 v) { sv6 o; o.a = sym_mul(I.I, v.a) + cross(I.h, v.l); o.l = I.m * v.l - cross(I.h, v.a); return o; }
 // s (a b^T + b a^T) added to a symmetric matrix
 QR_HD void sym_add_outer2(real I[6], real s, v3 a, v3 b)
 {
@@ -169,35 +138,35 @@ QR_HD sv6 abi_solve(const abi &A, sv6 b)
 }
 
 // R A R^T of a full 3 x 3 matrix given by its columns.
-QR_HD m3 rot_conj(const m3 &R, const m3 &A)
+QR_HD frame3 rot_conj(const frame3 &R, const frame3 &A)
 {
     const v3 b0 = mul(R, A.c0), b1 = mul(R, A.c1), b2 = mul(R, A.c2);
-    m3 o;
+    frame3 o;
     o.c0 = R.c0.x * b0 + (R.c1.x * b1 + R.c2.x * b2);
     o.c1 = R.c0.y * b0 + (R.c1.y * b1 + R.c2.y * b2);
     o.c2 = R.c0.z * b0 + (R.c1.z * b1 + R.c2.z * b2);
     return o;
 }
-QR_HD m3 sym_full(const real I[6]) { m3 o; o.c0 = mk(I[0], I[3], I[4]); o.c1 = mk(I[3], I[1], I[5]); o.c2 = mk(I[4], I[5], I[2]); return o; }
-QR_HD void full_sym(const m3 &A, real I[6])
+QR_HD frame3 sym_full(const real I[6]) { frame3 o; o.c0 = mk(I[0], I[3], I[4]); o.c1 = mk(I[3], I[1], I[5]); o.c2 = mk(I[4], I[5], I[2]); return o; }
+QR_HD void full_sym(const frame3 &A, real I[6])
 {
     I[0] = A.c0.x; I[1] = A.c1.y; I[2] = A.c2.z; I[3] = 0.5 * (A.c1.x + A.c0.y); I[4] = 0.5 * (A.c2.x + A.c0.z); I[5] = 0.5 * (A.c2.y + A.c1.z);
 }
 
 // A joint's transform: the child frame sits at r in the parent and is turned by R (child -> parent).
-struct Joint { m3 R; v3 r; };
+struct Joint { frame3 R; v3 r; };
 QR_HD sv6 to_child(const Joint &X, sv6 v) { sv6 o; o.a = mulT(X.R, v.a); o.l = mulT(X.R, v.l - cross(X.r, v.a)); return o; }      // motion vectors
 QR_HD sv6 to_parent(const Joint &X, sv6 f) { sv6 o; o.l = mul(X.R, f.l); o.a = mul(X.R, f.a) + cross(X.r, o.l); return o; }       // force vectors
 // X^T A X of an articulated inertia: turned by R, then moved by r:  M' = R M R^T,  H_p = R H R^T + [r]x M',  I_p = R I R^T - (R H R^T) [r]x + [r]x H_p^T
 QR_HD abi to_parent(const Joint &X, const abi &A)
 {
-    const m3 I = rot_conj(X.R, sym_full(A.I)), M = rot_conj(X.R, sym_full(A.M));
-    m3 H; H.c0 = A.h0; H.c1 = A.h1; H.c2 = A.h2;
+    const frame3 I = rot_conj(X.R, sym_full(A.I)), M = rot_conj(X.R, sym_full(A.M));
+    frame3 H; H.c0 = A.h0; H.c1 = A.h1; H.c2 = A.h2;
     H = rot_conj(X.R, H);
     const v3 r = X.r;
-    m3 Hp; Hp.c0 = H.c0 + cross(r, M.c0); Hp.c1 = H.c1 + cross(r, M.c1); Hp.c2 = H.c2 + cross(r, M.c2);
+    frame3 Hp; Hp.c0 = H.c0 + cross(r, M.c0); Hp.c1 = H.c1 + cross(r, M.c1); Hp.c2 = H.c2 + cross(r, M.c2);
     // H [r]x: column k = H (r x e_k);   [r]x Hp^T: column k = r x (row k of Hp)
-    m3 Ip;
+    frame3 Ip;
     Ip.c0 = (I.c0 - mul(H, mk(0, r.z, -r.y))) + cross(r, mk(Hp.c0.x, Hp.c1.x, Hp.c2.x));
     Ip.c1 = (I.c1 - mul(H, mk(-r.z, 0, r.x))) + cross(r, mk(Hp.c0.y, Hp.c1.y, Hp.c2.y));
     Ip.c2 = (I.c2 - mul(H, mk(r.y, -r.x, 0))) + cross(r, mk(Hp.c0.z, Hp.c1.z, Hp.c2.z));
@@ -341,7 +310,7 @@ QR_HD void base_start(const WbcConst &K, sv6 v0, abi &IA, sv6 &pA)
     pA = crf(v0, rbi_mul(I0, v0));
 }
 // afb = d/dt of the components of (omega_body, v_body); a0 = afb + gravity's fictitious acceleration, what the legs' outward pass takes.
-QR_HD void base_solve(const abi &IA, sv6 pA, const m3 &R, sv6 &afb, sv6 &a0)
+QR_HD void base_solve(const abi &IA, sv6 pA, const frame3 &R, sv6 &afb, sv6 &a0)
 {
     sv6 ag; ag.a = mk(0, 0, 0); ag.l = mulT(R, mk(0, 0, QR_PL_GRAVITY));
     const sv6 rhs = -1.0 * (pA + abi_mul(IA, ag));

@@ -44,14 +44,8 @@ namespace qrgpu {
 #define PP_FN inline
 #else
 #define PP_LANES(cond) if (cond)
-#define PP_SYNC() pp_vsync()
+#define PP_SYNC() wave_sync()
 #define PP_FN __device__ __forceinline__
-__device__ __forceinline__ void pp_vsync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 #endif
 
 struct PoseWork {

@@ -21,13 +21,6 @@
 namespace qrgpu {
 
 namespace {
-__device__ __forceinline__ void vsync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 __device__ __forceinline__ float chain3(float a0, float b0, float a1, float b1, float a2, float b2)
 {
 #pragma clang fp contract(off)
@@ -44,9 +37,9 @@ __device__ __forceinline__ void vmc_assemble(int lane, const qrgpu_vmc_desc &C, 
     const float *pb = sIn, *acc_des = sIn + 12, *ct = sIn + 18, *R = sIn + 22, *gv = sIn + 31, *nrm = sIn + 34;
     float *T = sA, *Ic = sA + 9, *Iinv = sA + 18;
     if (lane < 9) { const int i = lane / 3, j = lane - 3 * i; T[lane] = chain3(R[3 * i], C.inertia[0 + 3 * j], R[3 * i + 1], C.inertia[1 + 3 * j], R[3 * i + 2], C.inertia[2 + 3 * j]); }
-    vsync();
+    wave_sync();
     if (lane < 9) { const int i = lane / 3, j = lane - 3 * i; Ic[lane] = chain3(T[3 * i], R[3 * j], T[3 * i + 1], R[3 * j + 1], T[3 * i + 2], R[3 * j + 2]); }
-    vsync();
+    wave_sync();
     {
         float cof[9];
 #pragma unroll
@@ -64,7 +57,7 @@ __device__ __forceinline__ void vmc_assemble(int lane, const qrgpu_vmc_desc &C, 
             Iinv[lane] = v * idet; }
         if (lane >= 16 && lane < 28) { const int e = lane - 16, l = e / 3, i = e - 3 * l; xc[e] = chain3(R[3 * i], pb[3 * l], R[3 * i + 1], pb[3 * l + 1], R[3 * i + 2], pb[3 * l + 2]); }
     }
-    vsync();
+    wave_sync();
     const float im = 1.f / C.mass;
     for (int e = lane; e < 72; e += 64) {
         const int k = e / 12, col = e - 12 * k, l = col / 3, j = col - 3 * l;
@@ -79,7 +72,7 @@ __device__ __forceinline__ void vmc_assemble(int lane, const qrgpu_vmc_desc &C, 
         }
         Mm[e] = v;
     }
-    vsync();
+    wave_sync();
     for (int e = lane; e < 144; e += 64) {
         const int i = e / 12, j = e - 12 * i;
         float acc = 0.f;
@@ -122,7 +115,7 @@ __device__ __forceinline__ void vmc_assemble(int lane, const qrgpu_vmc_desc &C, 
         }
         bf[lane] = b;
     }
-    vsync();
+    wave_sync();
 }
 }  // namespace
 
@@ -145,12 +138,12 @@ __global__ void __launch_bounds__(64) qr_vmc_kernel(VmcLaunch P, const int *__re
 
     if (lane < 37) sIn[lane] = g_in[(size_t)lane * n + rid];
     if (P.ratio && lane >= 40 && lane < 48) sIn[lane] = P.ratio[(size_t)(lane - 40) * n + rid];
-    vsync();
+    wave_sync();
     vmc_assemble(lane, C, sIn, sA, xc, Mm, Gf, af, cn, bf, P.ratio ? sIn + 40 : nullptr);
 
     // ---- G (mirrored lower triangle) -> fp64, c1 = tr G
     for (int e = lane; e < 144; e += 64) { const int i = e / 12, j = e - 12 * i; Md[e] = (double)Gf[12 * (i > j ? i : j) + (i > j ? j : i)]; }
-    vsync();
+    wave_sync();
     double c1 = 0.0, c2 = 0.0;
 #pragma unroll
     for (int i = 0; i < 12; ++i) c1 += Md[13 * i];
@@ -158,7 +151,7 @@ __global__ void __launch_bounds__(64) qr_vmc_kernel(VmcLaunch P, const int *__re
     int st = bad_type ? QRGPU_ST_BAD_TYPE : 0;
     for (int k = 0; k < 12; ++k) {
         if (lane < 12) colv[lane] = Md[12 * lane + k];
-        vsync();
+        wave_sync();
         const double piv = colv[k];
         if (!(piv > 0.0)) st |= QRGPU_ST_VMC_INFEAS;
         c2 += 1.0 / __builtin_sqrt(piv);
@@ -171,16 +164,16 @@ __global__ void __launch_bounds__(64) qr_vmc_kernel(VmcLaunch P, const int *__re
             else v = Md[e] - colv[i] * colv[j] * ip;
             Md[e] = v;
         }
-        vsync();
+        wave_sync();
     }
     for (int e = lane; e < 144; e += 64) Md[e] = -Md[e];          // M = +G^-1
-    vsync();
+    wave_sync();
     // ---- x = -G^-1 g0 = M a   (g0 = -a, :249-252)
     if (lane < 12) { double acc = 0.0;
 #pragma unroll
         for (int k = 0; k < 12; ++k) acc += Md[12 * lane + k] * (double)af[k];
         xd[lane] = acc; }
-    vsync();
+    wave_sync();
 
     // ---- dual active set.  lane c < 24 is inequality row c: foot lc, normal nc, offset ci0 = -b.
     const bool isrow = lane < 24;
@@ -209,12 +202,12 @@ __global__ void __launch_bounds__(64) qr_vmc_kernel(VmcLaunch P, const int *__re
             if (++iter > maxit) { st |= QRGPU_ST_VMC_MAXITER; stop = true; break; }
             // w = M n_p ; d = N_A' w ; r = S^-1 d ; z = w - M N_A r
             if (lane < 12) wd[lane] = Md[12 * lane + 3 * lp] * p0 + Md[12 * lane + 3 * lp + 1] * p1 + Md[12 * lane + 3 * lp + 2] * p2;
-            vsync();
+            wave_sync();
             if (lane < q) {
                 const int c = act[lane], l = (c < 8) ? c >> 1 : (c - 8) >> 2;
                 dd[lane] = (double)cn[3 * c] * wd[3 * l] + (double)cn[3 * c + 1] * wd[3 * l + 1] + (double)cn[3 * c + 2] * wd[3 * l + 2];
             }
-            vsync();
+            wave_sync();
             if (lane < q) {
                 double sv[12], dv[12];                       // every load is issued before the first use (q <= 12)
 #pragma unroll
@@ -224,7 +217,7 @@ __global__ void __launch_bounds__(64) qr_vmc_kernel(VmcLaunch P, const int *__re
                 for (int j = 0; j < 12; j += 3) { a0 += sv[j] * dv[j]; a1 += sv[j + 1] * dv[j + 1]; a2 += sv[j + 2] * dv[j + 2]; }
                 rr[lane] = (a0 + a1) + a2;
             }
-            vsync();
+            wave_sync();
             if (lane < 12) {
                 double mv[12], rv[12];
 #pragma unroll
@@ -234,7 +227,7 @@ __global__ void __launch_bounds__(64) qr_vmc_kernel(VmcLaunch P, const int *__re
                 for (int i = 0; i < 12; i += 3) { a0 += mv[i] * rv[i]; a1 += mv[i + 1] * rv[i + 1]; a2 += mv[i + 2] * rv[i + 2]; }
                 zd[lane] = wd[lane] - ((a0 + a1) + a2);
             }
-            vsync();
+            wave_sync();
             const double znp = zd[3 * lp] * p0 + zd[3 * lp + 1] * p1 + zd[3 * lp + 2] * p2;
             double tt = INF;
             if (lane < q) { const double rj = rr[lane]; if (rj > 0.0) tt = uu[lane] / rj; }
@@ -254,7 +247,7 @@ __global__ void __launch_bounds__(64) qr_vmc_kernel(VmcLaunch P, const int *__re
             if (!dual_only && lane < 12) xd[lane] += t * zd[lane];
             if (lane < q) uu[lane] -= t * rr[lane];
             unew += t;
-            vsync();
+            wave_sync();
             if (!dual_only && t == t2) {
                 // full step: row ip joins the working set at position q (bordered update of S^-1 with 1 / z'n_p)
                 const double isg = 1.0 / znp;
@@ -264,7 +257,7 @@ __global__ void __launch_bounds__(64) qr_vmc_kernel(VmcLaunch P, const int *__re
                 if (lane < 12) mna[12 * q + lane] = wd[lane];                            // M n_p, kept for z
                 active |= 1u << ip; excluded = 0;
                 ++q;
-                vsync();
+                wave_sync();
                 break;
             }
             // partial or dual-only step: position l leaves the working set
@@ -272,21 +265,21 @@ __global__ void __launch_bounds__(64) qr_vmc_kernel(VmcLaunch P, const int *__re
                 const int last = q - 1;
                 const int cl = __builtin_amdgcn_readfirstlane(act[l]);
                 if (lane < q) dd[lane] = Sq[13 * lane + l];
-                vsync();
+                wave_sync();
                 const double isl = 1.0 / dd[l];
                 { const int rq_ = (65536 + q - 1) / q; for (int e = lane; e < q * q; e += 64) { const int i = (e * rq_) >> 16, j = e - i * q; if (i != l && j != l) Sq[13 * i + j] -= dd[i] * dd[j] * isl; } }
-                vsync();
+                wave_sync();
                 if (l != last) {
                     if (lane < last) rr[lane] = (lane == l) ? Sq[13 * last + last] : Sq[13 * last + lane];
                     double mv = (lane < 12) ? mna[12 * last + lane] : 0.0;
-                    vsync();
+                    wave_sync();
                     if (lane < last) { Sq[13 * l + lane] = rr[lane]; Sq[13 * lane + l] = rr[lane]; }
                     if (lane < 12) mna[12 * l + lane] = mv;
                     if (lane == 0) { act[l] = act[last]; uu[l] = uu[last]; }
                 }
                 active &= ~(1u << cl);
                 --q;
-                vsync();
+                wave_sync();
                 if (!dual_only) sip = readlane_d(ci0, ip) + p0 * xd[3 * lp] + p1 * xd[3 * lp + 1] + p2 * xd[3 * lp + 2];
             }
         }
@@ -301,7 +294,7 @@ __global__ void __launch_bounds__(64) qr_vmc_kernel(VmcLaunch P, const int *__re
         g_force[(size_t)lane * n + rid] = f;
         Gf[lane] = f;
     }
-    vsync();
+    wave_sync();
     if (g_tau && g_q && lane < 12) {
         const int leg = lane / 3, j = lane - 3 * leg;
         const float t0 = g_q[(size_t)(3 * leg) * n + rid], t1 = g_q[(size_t)(3 * leg + 1) * n + rid], t2 = g_q[(size_t)(3 * leg + 2) * n + rid];

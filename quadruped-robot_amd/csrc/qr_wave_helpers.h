@@ -1,9 +1,46 @@
 // Cross-lane helpers for wave64 on gfx950: DPP row all-reduce + v_readlane combine (no LDS traffic, no
-// ds_bpermute), uniform broadcasts, fast reciprocal.  Shared by the MPC and WBC kernels.
+// ds_bpermute), uniform broadcasts, fast reciprocal; the wave fence, the write-through store, the robot-type rule and the torque tail every
+// kernel shares.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "../../include/qrgpu.h"
 
 namespace qrgpu {
+
+// The fence between the lanes of one wavefront: what a lane stored to LDS in front of it, the wave's other lanes read behind it.
+__device__ __forceinline__ void wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// A plain store, or -- `through`: another launch reads the value while this one still runs -- an agent-scope one (global_store ... sc1, written
+// through to memory).
+template <typename T> __device__ __forceinline__ void st_through(T *p, T v, bool through)
+{
+    if (through) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); else *p = v;
+}
+
+// A robot whose type id is out of range or names a type that was never set up (bit t of type_ready: type t was) is computed with the first
+// valid type and flagged: -> true, tyid replaced.
+__device__ __forceinline__ bool resolve_type(int &tyid, int type_ready)
+{
+    const bool bad_type = tyid < 0 || tyid >= QRGPU_MAX_TYPES || !((type_ready >> (tyid & (QRGPU_MAX_TYPES - 1))) & 1);
+    if (bad_type) tyid = __builtin_ctz(type_ready | (1 << QRGPU_MAX_TYPES));
+    return bad_type;
+}
+
+// K14 torque tail: bit 0 of `epilogue` = the +-0.9 N m abad compensation of qrFSMStateLocomotion::Run (QS/fsm/qr_fsm_state_locomotion.cpp:141-151),
+// on the motors the caller says it survives on (comp); bit 1 = the +-23 N m clip of qrSafetyChecker::CheckForceFeedForward
+// (QS/fsm/qr_safety_checker.cpp:48-66); legCmd.tua is a double there.
+__device__ __forceinline__ float torque_epilogue(float tau, int motor, bool comp, int epilogue)
+{
+    double t = (double)tau;
+    if (comp && (epilogue & 1) && motor % 3 == 0) t += (double)(((motor / 3) & 1) ? 0.9f : -0.9f);     // tua_ * pow(-1, (leg + 1) % 2)
+    if (epilogue & 2) t = t > 23.0 ? 23.0 : (t < -23.0 ? -23.0 : t);
+    return (float)t;
+}
 
 // 1/x by v_rcp_f64 + two Newton steps (<= 1 ulp-ish; the active-set step lengths do not need IEEE division)
 __device__ __forceinline__ double fast_rcp(double x)

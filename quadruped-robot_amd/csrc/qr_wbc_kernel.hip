@@ -28,6 +28,7 @@
 #include "qr_device_types.h"
 #include "qr_wave_helpers.h"
 #include "qr_kernels.h"
+#include "qr_wbc_rigid_body.h"
 
 namespace qrgpu {
 
@@ -40,133 +41,6 @@ namespace qrgpu {
 #define QW_P_TLR ((int *)nullptr)
 #endif
 
-typedef double real;
-
-struct v3 { real x, y, z; };
-__device__ __forceinline__ v3 mk(real x, real y, real z) { v3 r = {x, y, z}; return r; }
-__device__ __forceinline__ v3 operator+(v3 a, v3 b) { return mk(a.x + b.x, a.y + b.y, a.z + b.z); }
-__device__ __forceinline__ v3 operator-(v3 a, v3 b) { return mk(a.x - b.x, a.y - b.y, a.z - b.z); }
-__device__ __forceinline__ v3 operator*(real s, v3 a) { return mk(s * a.x, s * a.y, s * a.z); }
-__device__ __forceinline__ v3 cross(v3 a, v3 b) { return mk(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
-__device__ __forceinline__ real dot(v3 a, v3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-struct m3 { real m[3][3]; };
-__device__ __forceinline__ v3 mul(const m3 &A, v3 b)
-{
-    return mk(A.m[0][0] * b.x + A.m[0][1] * b.y + A.m[0][2] * b.z, A.m[1][0] * b.x + A.m[1][1] * b.y + A.m[1][2] * b.z,
-              A.m[2][0] * b.x + A.m[2][1] * b.y + A.m[2][2] * b.z);
-}
-__device__ __forceinline__ v3 mulT(const m3 &A, v3 b)
-{
-    return mk(A.m[0][0] * b.x + A.m[1][0] * b.y + A.m[2][0] * b.z, A.m[0][1] * b.x + A.m[1][1] * b.y + A.m[2][1] * b.z,
-              A.m[0][2] * b.x + A.m[1][2] * b.y + A.m[2][2] * b.z);
-}
-__device__ __forceinline__ m3 mul(const m3 &A, const m3 &B)
-{
-    m3 C;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) C.m[i][j] = A.m[i][0] * B.m[0][j] + A.m[i][1] * B.m[1][j] + A.m[i][2] * B.m[2][j];
-    return C;
-}
-__device__ __forceinline__ m3 transpose(const m3 &A)
-{
-    m3 C;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) C.m[i][j] = A.m[j][i];
-    return C;
-}
-// coordinateRotation (QI/utils/qr_se3.h:72-89): the coordinate-transform (transposed) matrix.
-__device__ __forceinline__ m3 coord_rot(int axis, real th)
-{
-    real s, c;
-    sincos(th, &s, &c);
-    m3 R;
-    if (axis == 0)      { R = {{{1, 0, 0}, {0, c, s}, {0, -s, c}}}; }
-    else if (axis == 1) { R = {{{c, 0, -s}, {0, 1, 0}, {s, 0, c}}}; }
-    else                { R = {{{c, s, 0}, {-s, c, 0}, {0, 0, 1}}}; }
-    return R;
-}
-__device__ __forceinline__ m3 coord_rot_sc(int axis, real s, real c)
-{
-    m3 R;
-    if (axis == 0)      { R = {{{1, 0, 0}, {0, c, s}, {0, -s, c}}}; }
-    else if (axis == 1) { R = {{{c, 0, -s}, {0, 1, 0}, {s, 0, c}}}; }
-    else                { R = {{{c, s, 0}, {-s, c, 0}, {0, 0, 1}}}; }
-    return R;
-}
-// quaternionToRotationMatrix (:186-203): world -> body.
-__device__ __forceinline__ m3 quat_to_rot_wb(const real *q)
-{
-    const real e0 = q[0], e1 = q[1], e2 = q[2], e3 = q[3];
-    m3 R;
-    R.m[0][0] = 1 - 2 * (e2 * e2 + e3 * e3); R.m[1][0] = 2 * (e1 * e2 - e0 * e3); R.m[2][0] = 2 * (e1 * e3 + e0 * e2);
-    R.m[0][1] = 2 * (e1 * e2 + e0 * e3); R.m[1][1] = 1 - 2 * (e1 * e1 + e3 * e3); R.m[2][1] = 2 * (e2 * e3 - e0 * e1);
-    R.m[0][2] = 2 * (e1 * e3 - e0 * e2); R.m[1][2] = 2 * (e2 * e3 + e0 * e1); R.m[2][2] = 1 - 2 * (e1 * e1 + e2 * e2);
-    return R;
-}
-
-// Rigid-body spatial inertia [[Ibar, [h]x],[[h]x^T, m 1]] as (m, h, Ibar sym: xx yy zz xy xz yz).
-struct rbi { real m; v3 h; real I[6]; };
-__device__ __forceinline__ rbi rbi_load(const real *p)
-{
-    rbi r; r.m = p[0]; r.h = mk(p[1], p[2], p[3]);
-#pragma unroll
-    for (int i = 0; i < 6; ++i) r.I[i] = p[4 + i];
-    return r;
-}
-__device__ __forceinline__ v3 rbi_Iw(const rbi &a, v3 w)
-{
-    return mk(a.I[0] * w.x + a.I[3] * w.y + a.I[4] * w.z, a.I[3] * w.x + a.I[1] * w.y + a.I[5] * w.z, a.I[4] * w.x + a.I[5] * w.y + a.I[2] * w.z);
-}
-__device__ __forceinline__ rbi rbi_add(const rbi &a, const rbi &b)
-{
-    rbi r; r.m = a.m + b.m; r.h = a.h + b.h;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) r.I[i] = a.I[i] + b.I[i];
-    return r;
-}
-// Express a child-frame inertia in the parent frame: X^T I X with X = (E, r)  (createSXform(E, r)).
-__device__ __forceinline__ rbi rbi_to_parent(const rbi &a, const m3 &E, v3 r)
-{
-    rbi o;
-    o.m = a.m;
-    const v3 hr = mulT(E, a.h);                    // E^T h
-    o.h = hr + a.m * r;
-    // Ibar' = E^T Ibar E - [r]x[hr]x - [h']x[r]x
-    m3 I; I.m[0][0] = a.I[0]; I.m[1][1] = a.I[1]; I.m[2][2] = a.I[2];
-    I.m[0][1] = I.m[1][0] = a.I[3]; I.m[0][2] = I.m[2][0] = a.I[4]; I.m[1][2] = I.m[2][1] = a.I[5];
-    m3 Ir = mul(transpose(E), mul(I, E));
-    // -[a]x[b]x = (a.b) 1 - b a^T
-    auto add_outer = [&](v3 a_, v3 b_) {
-        const real ab = dot(a_, b_);
-        const real av[3] = {a_.x, a_.y, a_.z}, bv[3] = {b_.x, b_.y, b_.z};
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) Ir.m[i][j] += (i == j ? ab : 0.0) - bv[i] * av[j];
-    };
-    add_outer(r, hr);
-    add_outer(o.h, r);
-    o.I[0] = Ir.m[0][0]; o.I[1] = Ir.m[1][1]; o.I[2] = Ir.m[2][2];
-    o.I[3] = 0.5 * (Ir.m[0][1] + Ir.m[1][0]); o.I[4] = 0.5 * (Ir.m[0][2] + Ir.m[2][0]); o.I[5] = 0.5 * (Ir.m[1][2] + Ir.m[2][1]);
-    return o;
-}
-struct sv6 { v3 a, l; };      // spatial vector (angular; linear)
-__device__ __forceinline__ sv6 xmotion(const m3 &E, v3 r, sv6 v) { sv6 o; o.a = mul(E, v.a); o.l = mul(E, v.l - cross(r, v.a)); return o; }   // X v
-__device__ __forceinline__ sv6 xforceT(const m3 &E, v3 r, sv6 f) { sv6 o; o.l = mulT(E, f.l); o.a = mulT(E, f.a) + cross(r, o.l); return o; }   // X^T f
-__device__ __forceinline__ sv6 rbi_mul(const rbi &I, sv6 v) { sv6 o; o.a = rbi_Iw(I, v.a) + cross(I.h, v.l); o.l = I.m * v.l - cross(I.h, v.a); return o; }
-__device__ __forceinline__ sv6 crf(sv6 v, sv6 f) { sv6 o; o.a = cross(v.a, f.a) + cross(v.l, f.l); o.l = cross(v.a, f.l); return o; }   // v x* f
-__device__ __forceinline__ sv6 crm(sv6 v, sv6 u) { sv6 o; o.a = cross(v.a, u.a); o.l = cross(v.a, u.l) + cross(v.l, u.a); return o; }   // v x u
-
-__device__ __forceinline__ void wsync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 __device__ __forceinline__ real wsum(real v) { return wave_sum_d(v); }
 
 // sum_{t<k} a[t*as] b[t*bs], k <= 18: every load is issued before the first use
@@ -185,7 +59,7 @@ __device__ __forceinline__ real dot18(const real *a, int as, const real *b, int 
 __device__ __forceinline__ int fdiv16(int e, int rcp) { return (e * rcp) >> 16; }
 __device__ __forceinline__ int rcp16(int n) { return (65536 + n - 1) / n; }
 
-// C(m x n) = alpha * op(A)(m x k) * op(B)(k x n) + beta * C0 ; lane-parallel over outputs, ends with wsync.
+// C(m x n) = alpha * op(A)(m x k) * op(B)(k x n) + beta * C0 ; lane-parallel over outputs, ends with wave_sync.
 // tA: A stored k x m (use A^T);  tB: B stored n x k (use B^T).  k <= KMAX: the k-loop is fully unrolled and
 // predicated so that all 2k LDS loads of an output are in flight together (one wave per SIMD: latency is everything).
 template <int KMAX>
@@ -212,7 +86,7 @@ __device__ __forceinline__ void gemm(int lane, real *C, int ldc, const real *A, 
         if (C0) v += beta * C0[i * ldc0 + j];
         C[i * ldc + j] = v;
     }
-    wsync();
+    wave_sync();
 }
 
 // In-place inverse of a symmetric positive definite n x n matrix (full storage, ld) by symmetric sweeps.
@@ -236,7 +110,7 @@ __device__ __forceinline__ real spd_inverse(int lane, real *A, int ld, int n, re
     for (int k = 0; k < n; ++k) {
 #pragma unroll
         for (int u = 0; u < UMAX; ++u) if (ej[u] == k) col[ei[u]] = a[u];
-        wsync();
+        wave_sync();
         const real piv = col[k];
         minpiv = piv < minpiv ? piv : minpiv;
         const real ip = fast_rcp(piv);
@@ -249,11 +123,11 @@ __device__ __forceinline__ real spd_inverse(int lane, real *A, int ld, int n, re
             else if (ej[u] == k) a[u] = ci[u] * ip;
             else a[u] -= ci[u] * cj[u] * ip;
         }
-        wsync();                                   // col is rewritten by the next pivot
+        wave_sync();                                   // col is rewritten by the next pivot
     }
 #pragma unroll
     for (int u = 0; u < UMAX; ++u) if (ei[u] >= 0) A[ei[u] * ld + ej[u]] = -a[u];
-    wsync();
+    wave_sync();
     return minpiv;
 }
 
@@ -266,11 +140,11 @@ __device__ __forceinline__ void psd_pinv(int lane, const real *W, int n, real th
 {
     if (n == 1) {   // 1x1 special case compares the entry itself (quirk 7)
         if (lane == 0) Winv[0] = (W[0] > thr) ? 1.0 / W[0] : 0.0;
-        wsync();
+        wave_sync();
         return;
     }
     for (int e = lane; e < n * n; e += 64) Winv[e] = W[e];
-    wsync();
+    wave_sync();
     const real minpiv = spd_inverse<UMAX>(lane, Winv, n, n, scr);     // n * n <= 64 * UMAX (n <= 12: 144 elements)
     real fro = 0.0;
     for (int e = lane; e < n * n; e += 64) fro += Winv[e] * Winv[e];
@@ -308,7 +182,7 @@ __device__ __forceinline__ void psd_pinv(int lane, const real *W, int n, real th
         for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) { real a = 0; for (int k = 0; k < n; ++k) a += Am[i * n + k] * V[j * n + k]; tmp[i * n + j] = a; }
         for (int e = 0; e < n * n; ++e) Winv[e] = tmp[e];
     }
-    wsync();
+    wave_sync();
 }
 
 // Inverse of a symmetric 3 x 3 W (row-major; the lower triangle is read) by cofactors, every lane for itself: iv = {00, 10, 11, 20, 21, 22}.
@@ -341,20 +215,28 @@ __device__ __forceinline__ bool sym3_inverse(const real *W, real thr, real iv[6]
 #define QR_WBC_SHARED_DOUBLES 1392
 #define QR_WBC_LDS_DOUBLES (QR_WBC_SHARED_DOUBLES + 2 * QW_SIZE)       // 4884 doubles = 39 072 B: four workgroups per CU
 
+// The relaxation QP's names for a wave's workspace W (the one place the QW_* offsets turn into its pointers).
+struct QpWork {
+    real *tv;       // 18 gen = A qdd + C + G - Jc^T Fr_des (rows 6.. become the torque)
+    real *Nq;       // 30 x 18 QP constraint normals
+    real *Sq;       // 18 x 18 S^-1
+    real *qd_, *qr_, *qu_, *qc0;      // 32 each: d, r, u, constraint offsets
+    real *qx;       // 18 z
+};
+__device__ __forceinline__ QpWork qp_work(real *W)
+{
+    QpWork q;
+    q.tv = W + QW_VEC + 18; q.Nq = W + QW_NP; q.Sq = W + QW_JB;
+    q.qd_ = W + QW_QP; q.qr_ = q.qd_ + 32; q.qu_ = q.qr_ + 32; q.qc0 = q.qu_ + 32; q.qx = q.qc0 + 32;
+    return q;
+}
+
 // leg ids of the contacts / swing-foot tasks, 4 bits each in `cpack` / `tpack` (no indexed local arrays -> no scratch)
 #define CLEG(k) ((int)((cpack >> (4 * (k))) & 15u))
 #define TLEG(k) ((int)((tpack >> (4 * (k))) & 15u))
 
 // Output stores of a pipelined tick are written through (agent scope, sc1) so that the wave can tell the tick's join when they are in memory
-// (wbc_signal_done): a plain store otherwise.
-__device__ __forceinline__ void st_w(float *p, float v, bool through)
-{
-    if (through) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); else *p = v;
-}
-__device__ __forceinline__ void st_w(int *p, int v, bool through)
-{
-    if (through) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); else *p = v;
-}
+// (wbc_signal_done): st_through.
 __device__ __forceinline__ void wbc_signal_done(int *finished, int lane)
 {
     if (!finished) return;
@@ -374,11 +256,8 @@ __device__ __forceinline__ bool wbc_qp_setup(const int lane, const WbcConst &K, 
                                              real *W, int *sI)
 {
     const int dimFr = 3 * nc;
-    real *tv = W + QW_VEC + 18;
-    real *Nq = W + QW_NP;          // 30 x 18 QP constraint normals
-    real *Sq = W + QW_JB;          // 18 x 18 S^-1
-    real *qd_ = W + QW_QP;         // 32 d
-    real *qx = qd_ + 128;          // 18 z
+    const QpWork Q = qp_work(W);
+    real *tv = Q.tv, *Nq = Q.Nq, *Sq = Q.Sq, *qd_ = Q.qd_, *qx = Q.qx;
     const int nz = 6 + dimFr, np_ = 6, mi = 6 * nc;
     // gen (tv) = A qdd + C + G - Jc^T Fr_des  (all 18 rows; rows 6.. are reused for the torque): here without the last term
     if (lane < 18) {
@@ -405,7 +284,7 @@ __device__ __forceinline__ bool wbc_qp_setup(const int lane, const WbcConst &K, 
     }
     if (lane < 18) qx[lane] = 0.0;        // g0 = 0  =>  unconstrained minimiser z = 0
     if (lane < 32) sI[32 + lane] = -1;    // constraint -> position or -1
-    wsync();
+    wave_sync();
     // The six floating-base equalities enter together instead of one active-set iteration each: with S_e = N_e M N_e' (6 x 6),
     // u_e = -S_e^-1 c_e, z = M N_e' u_e, S^-1 = S_e^-1, working set = {0..5}.  Same point the six equality iterations reach.
     const real iw_fb = 1.0 / (real)K.w_fb, iw_fr = 1.0 / (real)K.w_fr;
@@ -415,7 +294,7 @@ __device__ __forceinline__ bool wbc_qp_setup(const int lane, const WbcConst &K, 
         for (int j = 0; j < nz; ++j) acc += Nq[a * 18 + j] * ((j < 6) ? iw_fb : iw_fr) * Nq[b2 * 18 + j];
         Sq[a * 18 + b2] = acc;
     }
-    wsync();
+    wave_sync();
     real tr = 0.0;
 #pragma unroll
     for (int a = 0; a < 6; ++a) tr += Sq[a * 18 + a];
@@ -431,14 +310,8 @@ __device__ __forceinline__ void wbc_qp_and_store(const int lane, const int rid, 
 #define QW_TSF(i) do { if (dbgT && (threadIdx.x & 63) == 0 && threadIdx.x < 64) dbgT[(size_t)blockIdx.x * 16 + (i)] = clock64(); } while (0)
     int qp_iters = 0;
     const int dimFr = 3 * nc;
-    real *tv = W + QW_VEC + 18;
-    real *Nq = W + QW_NP;          // 30 x 18 QP constraint normals
-    real *Sq = W + QW_JB;          // 18 x 18 S^-1
-    real *qd_ = W + QW_QP;         // 32 d
-    real *qr_ = qd_ + 32;          // 32 r
-    real *qu_ = qr_ + 32;          // 32 u
-    real *qc0 = qu_ + 32;          // 32 constraint offsets
-    real *qx = qc0 + 32;           // 18 z
+    const QpWork Q = qp_work(W);
+    real *tv = Q.tv, *Nq = Q.Nq, *Sq = Q.Sq, *qd_ = Q.qd_, *qr_ = Q.qr_, *qu_ = Q.qu_, *qc0 = Q.qc0, *qx = Q.qx;
     // ---------------- relaxation QP (SetCost/SetEqualityConstraint/SetInequalityConstraint :129-167,232-247) ----------------
     //   min 1/2 z' W z,  W = diag(w_fb x6, w_fr x dimFr)
     //   equalities  i<6 :  A[i,0:6] z_fb - Jc[:,i]' z_f + gen_i = 0,   gen = (A qdd + C + G - Jc' Fr_des)[0:6]
@@ -449,7 +322,7 @@ __device__ __forceinline__ void wbc_qp_and_store(const int lane, const int rid, 
         for (int k = 0; k < dimFr; ++k) acc -= JC[k * 18 + lane] * cm[51 + 3 * CLEG(k / 3) + k % 3];
         tv[lane] = acc;
     }
-    wsync();
+    wave_sync();
     // offsets qc0[c]
     if (lane < np_ + mi) {
         const int c = lane;
@@ -463,7 +336,7 @@ __device__ __forceinline__ void wbc_qp_and_store(const int lane, const int rid, 
         }
         qc0[c] = v;
     }
-    wsync();
+    wave_sync();
     int stw = bad_type ? QRGPU_ST_BAD_TYPE : 0;
     {
         // Goldfarb-Idnani, Schur-complement form, M = W^-1 diagonal, dense normals.
@@ -487,7 +360,7 @@ __device__ __forceinline__ void wbc_qp_and_store(const int lane, const int rid, 
                 for (int b2 = 0; b2 < 6; ++b2) acc -= Sq[lane * 18 + b2] * qc0[b2];
                 qu_[lane] = acc; act[lane] = lane; posi[lane] = lane;
             }
-            wsync();
+            wave_sync();
             if (lane < nz) {
                 real acc = 0.0;
 #pragma unroll
@@ -495,7 +368,7 @@ __device__ __forceinline__ void wbc_qp_and_store(const int lane, const int rid, 
                 qx[lane] = Minv(lane) * acc;
             }
             q = 6; next_eq = np_;
-            wsync();
+            wave_sync();
         }
         // Working-set vectors in registers: position i lives in lane i (constraint id act_r, multiplier u_r, and d, r of the current
         // change); lane c also knows whether constraint c is active.  Only S^-1, the normals and x go through LDS; uniform gathers are
@@ -582,14 +455,14 @@ __device__ __forceinline__ void wbc_qp_and_store(const int lane, const int rid, 
                 if (have_z && t == t2) {
                     const real isg = izc;
                     if (lane < q) qr_[lane] = rq_;
-                    wsync();                                                    // r and the new x are in LDS
+                    wave_sync();                                                    // r and the new x are in LDS
                     { const int rq2 = rcp16(q); for (int e = lane; e < q * q; e += 64) { const int i = fdiv16(e, rq2), j = e - i * q; Sq[i * 18 + j] += qr_[i] * qr_[j] * isg; } }
                     if (lane < q) { Sq[q * 18 + lane] = -rq_ * isg; Sq[lane * 18 + q] = -rq_ * isg; }
                     if (lane == 0) Sq[q * 18 + q] = isg;
                     if (lane == q) { act_r = p; u_r = up; }
                     if (lane == p) active_c = true;
                     ++q;
-                    wsync();
+                    wave_sync();
                     break;
                 }
                 // partial or dual-only step: position lpos leaves
@@ -598,19 +471,19 @@ __device__ __forceinline__ void wbc_qp_and_store(const int lane, const int rid, 
                     const int cdrop = __builtin_amdgcn_readlane(act_r, l), alast = __builtin_amdgcn_readlane(act_r, last);
                     const real ulast = readlane_d(u_r, last);
                     if (lane < q) qd_[lane] = Sq[lane * 18 + l];
-                    wsync();
+                    wave_sync();
                     const real isl = 1.0 / qd_[l];
                     { const int rq2 = rcp16(q); for (int e = lane; e < q * q; e += 64) { const int i = fdiv16(e, rq2), j = e - i * q; if (i != l && j != l) Sq[i * 18 + j] -= qd_[i] * qd_[j] * isl; } }
-                    wsync();
+                    wave_sync();
                     if (l != last) {
                         if (lane < last) qr_[lane] = (lane == l) ? Sq[last * 18 + last] : Sq[last * 18 + lane];
-                        wsync();
+                        wave_sync();
                         if (lane < last) { Sq[l * 18 + lane] = qr_[lane]; Sq[lane * 18 + l] = qr_[lane]; }
                         if (lane == l) { act_r = alast; u_r = ulast; }
                     }
                     if (lane == cdrop) active_c = false;
                     --q;
-                    wsync();
+                    wave_sync();
                 }
             }
         }
@@ -635,23 +508,21 @@ __device__ __forceinline__ void wbc_qp_and_store(const int lane, const int rid, 
         const int leg = lane / 3;
         const bool stance = cm[63 + leg] != 0.0;
         if (!epilogue) {
-            if (!merge_tau || stance) st_w(&g_tau[(size_t)lane * n + rid], (float)acc, piped);
+            if (!merge_tau || stance) st_through(&g_tau[(size_t)lane * n + rid], (float)acc, piped);
         } else {
             // K14 tail (fused tick): UpdateLegCMD overwrites the stance legs (:205-219) AFTER qrFSMStateLocomotion::Run added the +-0.9 N m abad
             // compensation to every leg (QS/fsm/qr_fsm_state_locomotion.cpp:141-151), so the compensation survives on swing legs only (their
             // command is what the MPC kernel left in g_tau); then the +-23 N m clip (QS/fsm/qr_safety_checker.cpp:48-66).  legCmd.tua is a double.
-            double t = stance ? (double)(float)acc
-                              : (double)(piped ? __hip_atomic_load(g_tau + (size_t)lane * n + rid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : g_tau[(size_t)lane * n + rid]);
-            if (!stance && (epilogue & 1) && lane % 3 == 0) t += (double)((leg & 1) ? 0.9f : -0.9f);
-            if (epilogue & 2) t = t > 23.0 ? 23.0 : (t < -23.0 ? -23.0 : t);
-            st_w(&g_tau[(size_t)lane * n + rid], (float)t, piped);
+            const float t = stance ? (float)acc
+                                   : (piped ? __hip_atomic_load(g_tau + (size_t)lane * n + rid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : g_tau[(size_t)lane * n + rid]);
+            st_through(&g_tau[(size_t)lane * n + rid], torque_epilogue(t, lane, !stance, epilogue), piped);
         }
     }
-    if (g_prev && lane < 3) st_w(&g_prev[(size_t)lane * n + rid], (float)cm[12 + lane], piped);          // desiredVel of the orientation task (quirk 4's memory)
+    if (g_prev && lane < 3) st_through(&g_prev[(size_t)lane * n + rid], (float)cm[12 + lane], piped);          // desiredVel of the orientation task (quirk 4's memory)
     if (lane == 0 && g_status) {
         if (status_or & 2) stw |= QRGPU_ST_PIPE_TIMEOUT;
-        if (status_or & 1) st_w(&g_status[rid], stw | (piped ? __hip_atomic_load(g_status + rid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : g_status[rid]), piped);
-        else st_w(&g_status[rid], stw, piped);
+        if (status_or & 1) st_through(&g_status[rid], stw | (piped ? __hip_atomic_load(g_status + rid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : g_status[rid]), piped);
+        else st_through(&g_status[rid], stw, piped);
     }
     QW_TSF(9);
 #undef QW_TSF
@@ -660,7 +531,7 @@ __device__ __forceinline__ void wbc_qp_and_store(const int lane, const int rid, 
 // Two wavefronts per robot, 39 KB of LDS: 4 workgroups per CU = 2 waves per SIMD, 256 VGPRs each.
 //   wave 0: Jacobians, composite inertias, H, G -> A^-1                    -> prioritized acceleration recursion -> relaxation QP -> torques
 //   wave 1: velocities, foot kinematics, Jcdqd, Coriolis -> the task set   -> K12 kinematic projection (when asked for) -> q_des, qd_des
-// One workgroup barrier after the load, one where the two meet; everything else is wave-local (wsync).
+// One workgroup barrier after the load, one where the two meet; everything else is wave-local (wave_sync).
 #ifdef QR_WBC_DBG_BUILD
 #define qr_wbc_kernel qr_wbc_kernel_dbg
 #endif
@@ -701,8 +572,7 @@ void qr_wbc_kernel(int n, const WbcConst *__restrict__ types, const int *__restr
     if (pipe.order && !pipe.second) rid = pipe.order[rid];        // (a permutation inside the XCD chunk: qr_mpc_kernel.hip, finish_order_chunk)
     if (QW_P_TLR && threadIdx.x == 0 && !pipe.second) QW_P_TLR[rid] = (int)wall_clock64();
     int tyid = type_id ? type_id[rid] : 0;
-    const bool bad_type = tyid < 0 || tyid >= QRGPU_MAX_TYPES || !((type_ready >> (tyid & (QRGPU_MAX_TYPES - 1))) & 1);
-    if (bad_type) tyid = __builtin_ctz(type_ready | (1 << QRGPU_MAX_TYPES));     // computed with the first valid type, flagged QRGPU_ST_BAD_TYPE
+    const bool bad_type = resolve_type(tyid, type_ready);      // computed with the first valid type, flagged QRGPU_ST_BAD_TYPE
     const WbcConst &K = types[tyid & (QRGPU_MAX_TYPES - 1)];
 
     __shared__ real sm[QR_WBC_LDS_DOUBLES];
@@ -727,13 +597,6 @@ void qr_wbc_kernel(int n, const WbcConst *__restrict__ types, const int *__restr
     real *lam = W + QW_LAM, *lamI = W + QW_LAMI, *scr = W + QW_SCR;
     real *qdd = W + QW_VEC, *tv = qdd + 18;
     real *dq1 = qdd, *dq2 = tv;                       // (wave 1's names for the same slots)
-    real *Nq = W + QW_NP;          // 30 x 18 QP constraint normals
-    real *Sq = W + QW_JB;          // 18 x 18 S^-1
-    real *qd_ = W + QW_QP;         // 32 d
-    real *qr_ = qd_ + 32;          // 32 r
-    real *qu_ = qr_ + 32;          // 32 u
-    real *qc0 = qu_ + 32;          // 32 constraint offsets
-    real *qx = qc0 + 32;           // 18 z
     __shared__ int sI[64];         // active list of the QP
     __shared__ int sPipe;          // overlapped ticks: wave 1's wait for the robot's previous WBC pass gave up (read by wave 0 behind the meeting barrier)
     if (threadIdx.x == 0) sPipe = 0;
@@ -749,7 +612,7 @@ void qr_wbc_kernel(int n, const WbcConst *__restrict__ types, const int *__restr
     }
     __syncthreads();
     const real *quat = st, *pos = st + 4, *bv = st + 7, *qj = st + 13, *qdj = st + 25;
-    const m3 Rwb = quat_to_rot_wb(quat);        // world -> body  (E of Xup[5])
+    const xform3 Rwb = quat_to_rot_wb(quat);        // world -> body  (E of Xup[5])
     // contacts: stance feet; task list: 0 = body orientation, 1 = body position, then swing feet in leg order
     int nc = 0, nt = 2;
     unsigned cpack = 0, tpack = 0;      // leg ids of the contacts / swing-foot tasks, 4 bits each (no indexed local arrays -> no scratch)
@@ -772,204 +635,25 @@ void qr_wbc_kernel(int n, const WbcConst *__restrict__ types, const int *__restr
             sincos(th, &s_, &c_);
             sS[lane] = s_; sC[lane] = c_;
         }
-        wsync();
+        wave_sync();
     }
     const real *sS = scr + 160, *sC = scr + 176;
 
     QW_TS(1);
-    // ---------------- K8-K10 per leg (lanes 0-3 of both waves) ----------------
+    // ---------------- K8-K10 per leg (lanes 0-3 of both waves; the chains themselves: qr_wbc_rigid_body.h) ----------------
     // Wave 0 takes what the mass matrix needs (contact Jacobians, composite inertias, H, gravity), wave 1 what depends on the velocities
     // (bias accelerations, foot position / velocity, Jcdqd, Coriolis) and then the task set: two chains of half the length side by side.
-    struct LegFrames { v3 r_a, r_h, r_k, loc; m3 Ea, Eh, Ek, Eabs_a, Eabs_h, Eabs_k; };
-    auto leg_frames = [&](int leg) {
-        LegFrames F;
-        const int side = leg & 1;           // side 0: right (legs 0,2; sideSign<0), 1: left
-        const real sx = (leg < 2) ? 1.0 : -1.0, sy = side ? 1.0 : -1.0;
-        F.r_a = mk(sx * K.abad_loc[0], sy * K.abad_loc[1], K.abad_loc[2]);
-        F.r_h = mk(0.0, sy * K.hip_l, 0.0);
-        F.r_k = mk(0.0, 0.0, -K.upper_l);
-        F.loc = mk(0.0, side ? -K.foot_y : K.foot_y, -K.lower_l);
-        F.Ea = coord_rot_sc(0, sS[3 * leg], sC[3 * leg]); F.Eh = coord_rot_sc(1, sS[3 * leg + 1], sC[3 * leg + 1]); F.Ek = coord_rot_sc(1, sS[3 * leg + 2], sC[3 * leg + 2]);
-        // absolute rotations (world -> link)
-        F.Eabs_a = mul(F.Ea, Rwb); F.Eabs_h = mul(F.Eh, F.Eabs_a); F.Eabs_k = mul(F.Ek, F.Eabs_h);
-        return F;
-    };
-    const v3 ex = mk(1, 0, 0), ey = mk(0, 1, 0);
     if (wv == 0) {
-      if (lane < 4) {
-        const int leg = lane, side = leg & 1;
-        const LegFrames F = leg_frames(leg);
-        const v3 r_a = F.r_a, r_h = F.r_h, r_k = F.r_k, loc = F.loc;
-        const m3 &Ea = F.Ea, &Eh = F.Eh, &Ek = F.Ek, &Eabs_a = F.Eabs_a, &Eabs_h = F.Eabs_h, &Eabs_k = F.Eabs_k;
-        // contact Jacobian columns: world velocity of the foot per unit generalized velocity
-        {
-            real *J = JcA + 54 * leg;
-            const v3 lk = loc;                               // foot in knee frame
-            const v3 lh = r_k + mulT(Ek, lk);                // foot in hip frame
-            const v3 la = r_h + mulT(Eh, lh);                // foot in abad frame
-            const v3 lb = r_a + mulT(Ea, la);                // foot in base frame
-            const v3 ck_ = mulT(Eabs_k, cross(ey, lk)), ch_ = mulT(Eabs_h, cross(ey, lh)), ca_ = mulT(Eabs_a, cross(ex, la));
-            const int c0 = 6 + 3 * leg;
-            J[0 * 18 + c0] = ca_.x; J[1 * 18 + c0] = ca_.y; J[2 * 18 + c0] = ca_.z;
-            J[0 * 18 + c0 + 1] = ch_.x; J[1 * 18 + c0 + 1] = ch_.y; J[2 * 18 + c0 + 1] = ch_.z;
-            J[0 * 18 + c0 + 2] = ck_.x; J[1 * 18 + c0 + 2] = ck_.y; J[2 * 18 + c0 + 2] = ck_.z;
-            // base: angular columns Rbw (e_i x lb), linear columns Rbw e_i
-            const v3 e[3] = {mk(1, 0, 0), mk(0, 1, 0), mk(0, 0, 1)};
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                const v3 ang = mulT(Rwb, cross(e[i], lb)), lin = mulT(Rwb, e[i]);
-                J[0 * 18 + i] = ang.x; J[1 * 18 + i] = ang.y; J[2 * 18 + i] = ang.z;
-                J[0 * 18 + 3 + i] = lin.x; J[1 * 18 + 3 + i] = lin.y; J[2 * 18 + 3 + i] = lin.z;
-            }
-        }
-        // composite inertias (rotor constants are folded into the *_eff parents on the host)
-        const rbi ICk = rbi_load(K.rb[QR_RB_KNEE]);
-        const rbi Ih_e = rbi_load(K.rb[QR_RB_HIP_EFF + side]);
-        const rbi Ia_e = rbi_load(K.rb[QR_RB_ABAD_EFF + side]);
-        const rbi ICh = rbi_add(Ih_e, rbi_to_parent(ICk, Ek, r_k));
-        const rbi ICa = rbi_add(Ia_e, rbi_to_parent(ICh, Eh, r_h));
-        const rbi ICa_b = rbi_to_parent(ICa, Ea, r_a);
-        real *LB = legB + 16 * leg;
-        LB[0] = ICa_b.m; LB[1] = ICa_b.h.x; LB[2] = ICa_b.h.y; LB[3] = ICa_b.h.z;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) LB[4 + i] = ICa_b.I[i];
-        // mass-matrix columns (massMatrix :774-806)
-        const real kr = K.k_rot;
-        const int ja = 6 + 3 * leg, jh = ja + 1, jk = ja + 2;
-        auto base_col = [&](int j, sv6 f) {     // f expressed in the base frame
-            const real fv[6] = {f.a.x, f.a.y, f.a.z, f.l.x, f.l.y, f.l.z};
-#pragma unroll
-            for (int i = 0; i < 6; ++i) { A[i * 18 + j] = fv[i]; A[j * 18 + i] = fv[i]; }
-        };
-        {   // knee
-            sv6 S; S.a = ey; S.l = mk(0, 0, 0);
-            sv6 f = rbi_mul(ICk, S);
-            A[jk * 18 + jk] = f.a.y + kr;
-            f = xforceT(Ek, r_k, f); f.a.y += kr;                 // + Xuprot^T (Irot Srot): knee rotor, E_rot = 1
-            A[jh * 18 + jk] = A[jk * 18 + jh] = f.a.y;
-            f = xforceT(Eh, r_h, f);
-            A[ja * 18 + jk] = A[jk * 18 + ja] = f.a.x;
-            f = xforceT(Ea, r_a, f);
-            base_col(jk, f);
-        }
-        {   // hip
-            sv6 S; S.a = ey; S.l = mk(0, 0, 0);
-            sv6 f = rbi_mul(ICh, S);
-            A[jh * 18 + jh] = f.a.y + kr;
-            f = xforceT(Eh, r_h, f); f.a.x += kr * K.hiprot_ex; f.a.y += kr * K.hiprot_ey;   // hip rotor: E_rot = Rz(pi)
-            A[ja * 18 + jh] = A[jh * 18 + ja] = f.a.x;
-            f = xforceT(Ea, r_a, f);
-            base_col(jh, f);
-        }
-        {   // abad
-            sv6 S; S.a = ex; S.l = mk(0, 0, 0);
-            sv6 f = rbi_mul(ICa, S);
-            A[ja * 18 + ja] = f.a.x + kr;
-            f = xforceT(Ea, r_a, f); f.a.x += kr;
-            base_col(ja, f);
-        }
-        // gravity (:607-626): ag_i = [0; E_abs_i g], G[i] = -S_i . (IC_i ag_i) = -axis . (h_i x a_i)
-        {
-            const v3 gw = mk(0, 0, -9.81);
-            const v3 g_a = mul(Eabs_a, gw), g_h = mul(Eabs_h, gw), g_k = mul(Eabs_k, gw);
-            Gv[ja] = -cross(ICa.h, g_a).x;
-            Gv[jh] = -cross(ICh.h, g_h).y;
-            Gv[jk] = -cross(ICk.h, g_k).y;
-        }
-      }
-      wsync();
+      if (lane < 4) wbc_leg_inertia_chain(K, Rwb, sS, sC, lane, A, JcA, Gv, legB);
+      wave_sync();
       QW_TS(2);
       // ---------------- base block of H and G (lane 0) ----------------
-      if (lane == 0) {
-        rbi IC5 = rbi_load(K.rb[QR_RB_BASE_EFF]);
-        for (int l = 0; l < 4; ++l) IC5 = rbi_add(IC5, rbi_load(legB + 16 * l));
-        // H[0:6,0:6] = IC5 as a 6x6
-        const real I6[3][3] = {{IC5.I[0], IC5.I[3], IC5.I[4]}, {IC5.I[3], IC5.I[1], IC5.I[5]}, {IC5.I[4], IC5.I[5], IC5.I[2]}};
-        const real hx[3][3] = {{0, -IC5.h.z, IC5.h.y}, {IC5.h.z, 0, -IC5.h.x}, {-IC5.h.y, IC5.h.x, 0}};
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                A[i * 18 + j] = I6[i][j];
-                A[i * 18 + 3 + j] = hx[i][j];
-                A[(3 + i) * 18 + j] = hx[j][i];
-                A[(3 + i) * 18 + 3 + j] = (i == j) ? IC5.m : 0.0;
-            }
-        // G[0:6] = -IC5 [0; a5],  a5 = Rwb g
-        const v3 a5 = mul(Rwb, mk(0, 0, -9.81));
-        const v3 gt = cross(IC5.h, a5);
-        Gv[0] = -gt.x; Gv[1] = -gt.y; Gv[2] = -gt.z; Gv[3] = -IC5.m * a5.x; Gv[4] = -IC5.m * a5.y; Gv[5] = -IC5.m * a5.z;
-      }
-      wsync();
+      if (lane == 0) wbc_base_block(K, Rwb, legB, A, Gv);
+      wave_sync();
       QW_TS(3);
     } else {
-      if (lane < 4) {
-        const int leg = lane, side = leg & 1;
-        const LegFrames F = leg_frames(leg);
-        const v3 r_a = F.r_a, r_h = F.r_h, r_k = F.r_k, loc = F.loc;
-        const m3 &Ea = F.Ea, &Eh = F.Eh, &Ek = F.Ek, &Eabs_a = F.Eabs_a, &Eabs_h = F.Eabs_h, &Eabs_k = F.Eabs_k;
-        const real d0 = qdj[3 * leg], d1 = qdj[3 * leg + 1], d2 = qdj[3 * leg + 2];
-        // velocities, bias accelerations
-        sv6 v5; v5.a = mk(bv[0], bv[1], bv[2]); v5.l = mk(bv[3], bv[4], bv[5]);
-        sv6 va = xmotion(Ea, r_a, v5); sv6 vJa; vJa.a = d0 * ex; vJa.l = mk(0, 0, 0); va.a = va.a + vJa.a;
-        sv6 ca = crm(va, vJa);
-        sv6 vh = xmotion(Eh, r_h, va); sv6 vJh; vJh.a = d1 * ey; vJh.l = mk(0, 0, 0); vh.a = vh.a + vJh.a;
-        sv6 ch = crm(vh, vJh);
-        sv6 vk = xmotion(Ek, r_k, vh); sv6 vJk; vJk.a = d2 * ey; vJk.l = mk(0, 0, 0); vk.a = vk.a + vJk.a;
-        sv6 ck = crm(vk, vJk);
-        sv6 aa = ca;
-        sv6 ah = xmotion(Eh, r_h, aa); ah.a = ah.a + ch.a; ah.l = ah.l + ch.l;
-        sv6 ak = xmotion(Ek, r_k, ah); ak.a = ak.a + ck.a; ak.l = ak.l + ck.l;
-        // Foot position / velocity exactly as forwardKinematics does it (:506-521): through the bottom-left
-        // block of Xa and invertSXform / sXFormPoint, which use E^T as E^-1.  With the float-rounded (not
-        // exactly unit) quaternion of the state this differs from the textbook sum of offsets by O(|q|^2-1) * 1 m,
-        // which the foot task's Kp = 500 would turn into 1e-5 N m.
-        {
-            auto skewm = [](v3 r) { m3 S = {{{0, -r.z, r.y}, {r.z, 0, -r.x}, {-r.y, r.x, 0}}}; return S; };
-            auto neg = [](const m3 &A_) { m3 C_; for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) C_.m[i][j] = -A_.m[i][j]; return C_; };
-            auto addm = [](const m3 &A_, const m3 &B_) { m3 C_; for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) C_.m[i][j] = A_.m[i][j] + B_.m[i][j]; return C_; };
-            auto unskew = [](const m3 &M_) { return mk(0.5 * (M_.m[2][1] - M_.m[1][2]), 0.5 * (M_.m[0][2] - M_.m[2][0]), 0.5 * (M_.m[1][0] - M_.m[0][1])); };   // matToSkewVec
-            const v3 p5 = mk(pos[0], pos[1], pos[2]);
-            const m3 B5 = neg(mul(Rwb, skewm(p5)));                                              // createSXform(R, pos) bottom-left
-            const m3 Ba = addm(mul(neg(mul(Ea, skewm(r_a))), Rwb), mul(Ea, B5));                 // Xup[a] * Xa[5]
-            const m3 Bh = addm(mul(neg(mul(Eh, skewm(r_h))), Eabs_a), mul(Eh, Ba));
-            const m3 Bk = addm(mul(neg(mul(Ek, skewm(r_k))), Eabs_h), mul(Ek, Bh));
-            const m3 E = Eabs_k, Et = transpose(Eabs_k);
-            const v3 r1 = (-1.0) * unskew(mul(Et, Bk));                                          // invertSXform: r
-            const v3 Er1 = mul(E, r1);
-            const m3 BLi = mul(Et, skewm(Er1));                                                  // Xai bottom-left = -E^T [-E r]x
-            const v3 rp = (-1.0) * unskew(mul(E, BLi));                                          // translationFromSXform(Xai)
-            const v3 pf = mul(Et, loc - rp);                                                     // sXFormPoint
-            const v3 wS = mul(Et, vk.a);
-            const v3 vS = mul(BLi, vk.a) + mul(Et, vk.l);
-            const v3 vf = vS + cross(wS, pf);                                                    // spatialToLinearVelocity
-            pGC[3 * leg] = pf.x; pGC[3 * leg + 1] = pf.y; pGC[3 * leg + 2] = pf.z;
-            vGC[3 * leg] = vf.x; vGC[3 * leg + 1] = vf.y; vGC[3 * leg + 2] = vf.z;
-        }
-        // Jcdqd = Rai [ (a_lin + a_ang x loc) + w x (v_lin + w x loc) ]
-        {
-            const v3 t = (ak.l + cross(ak.a, loc)) + cross(vk.a, vk.l + cross(vk.a, loc));
-            const v3 jd = mulT(Eabs_k, t);
-            Jcd[3 * leg] = jd.x; Jcd[3 * leg + 1] = jd.y; Jcd[3 * leg + 2] = jd.z;
-        }
-        // Coriolis (:633-665) with link inertias
-        {
-            const rbi Ik = rbi_load(K.rb[QR_RB_KNEE]), Ih = rbi_load(K.rb[QR_RB_HIP + side]), Ia = rbi_load(K.rb[QR_RB_ABAD + side]);
-            const int ja = 6 + 3 * leg, jh = ja + 1, jk = ja + 2;
-            sv6 fk = rbi_mul(Ik, ak); { sv6 c = crf(vk, rbi_mul(Ik, vk)); fk.a = fk.a + c.a; fk.l = fk.l + c.l; }
-            sv6 fh = rbi_mul(Ih, ah); { sv6 c = crf(vh, rbi_mul(Ih, vh)); fh.a = fh.a + c.a; fh.l = fh.l + c.l; }
-            sv6 fa = rbi_mul(Ia, aa); { sv6 c = crf(va, rbi_mul(Ia, va)); fa.a = fa.a + c.a; fa.l = fa.l + c.l; }
-            Cv[jk] = fk.a.y;
-            { sv6 t = xforceT(Ek, r_k, fk); fh.a = fh.a + t.a; fh.l = fh.l + t.l; }
-            Cv[jh] = fh.a.y;
-            { sv6 t = xforceT(Eh, r_h, fh); fa.a = fa.a + t.a; fa.l = fa.l + t.l; }
-            Cv[ja] = fa.a.x;
-            sv6 t = xforceT(Ea, r_a, fa);
-            real *LB = legB + 16 * leg;
-            LB[10] = t.a.x; LB[11] = t.a.y; LB[12] = t.a.z; LB[13] = t.l.x; LB[14] = t.l.y; LB[15] = t.l.z;
-        }
-      }
-      wsync();
+      if (lane < 4) wbc_leg_velocity_chain(K, Rwb, pos, bv, qdj, sS, sC, lane, pGC, vGC, Jcd, Cv, legB);
+      wave_sync();
     }
     if (wv == 0) {
     // ---------------- K13 GetModelRes: A^-1 ----------------
@@ -989,13 +673,13 @@ void qr_wbc_kernel(int n, const WbcConst *__restrict__ types, const int *__restr
             const real c = (lo == 0) ? (hi == 0 ? c00 : (hi == 1 ? c01 : c02)) : (lo == 1 ? (hi == 1 ? c11 : c12) : c22);
             Um[lane] = c * idet;                                    // Li, leg-major 3 x 3 blocks (parked in Um until T is formed)
         }
-        wsync();
+        wave_sync();
         for (int e = lane; e < 72; e += 64) {
             const int a = e / 12, c = e - 12 * a, l = c / 3, cc = c - 3 * l;
             const real *Ar = A + a * 18 + 6 + 3 * l, *Li = Um + 9 * l;
             Tm[e] = Ar[0] * Li[cc] + Ar[1] * Li[3 + cc] + Ar[2] * Li[6 + cc];
         }
-        wsync();
+        wave_sync();
         for (int e = lane; e < 144; e += 64) {                      // leg-leg part starts as blockdiag(Li); everything else of Ai is written below
             const int c = e / 12, d = e - 12 * c;
             Ai[(6 + c) * 18 + 6 + d] = (c / 3 == d / 3) ? Um[9 * (c / 3) + 3 * (c % 3) + d % 3] : 0.0;
@@ -1007,7 +691,7 @@ void qr_wbc_kernel(int n, const WbcConst *__restrict__ types, const int *__restr
             for (int c = 0; c < 12; ++c) acc -= Tm[a * 12 + c] * A[b2 * 18 + 6 + c];
             Ai[a * 18 + b2] = acc;
         }
-        wsync();
+        wave_sync();
         spd_inverse<1>(lane, Ai, 18, 6, tv);
         for (int e = lane; e < 72; e += 64) {
             const int a = e / 12, c = e - 12 * a;
@@ -1017,7 +701,7 @@ void qr_wbc_kernel(int n, const WbcConst *__restrict__ types, const int *__restr
             Um[e] = acc;                                            // U = Sb^-1 T
             Ai[a * 18 + 6 + c] = -acc; Ai[(6 + c) * 18 + a] = -acc;
         }
-        wsync();
+        wave_sync();
         for (int e = lane; e < 144; e += 64) {
             const int c = e / 12, d = e - 12 * c;
             real acc = Ai[(6 + c) * 18 + 6 + d];
@@ -1025,7 +709,7 @@ void qr_wbc_kernel(int n, const WbcConst *__restrict__ types, const int *__restr
             for (int a = 0; a < 6; ++a) acc += Tm[a * 12 + c] * Um[a * 12 + d];
             Ai[(6 + c) * 18 + 6 + d] = acc;
         }
-        wsync();
+        wave_sync();
     }
 
       QW_TS(4);
@@ -1035,23 +719,15 @@ void qr_wbc_kernel(int n, const WbcConst *__restrict__ types, const int *__restr
       for (int e = 0; e < 9; ++e) if (lane == e) sRT[e] = Rwb.m[e % 3][e / 3];
     } else {
       // ---------------- base block of C (lane 0): fvp5 + the legs' contributions; fvp5 = v5 x* (I5 v5)  (avp5 = 0) ----------------
-      if (lane == 0) {
-        sv6 fb; fb.a = mk(0, 0, 0); fb.l = mk(0, 0, 0);
-        for (int l = 0; l < 4; ++l) { const real *LB = legB + 16 * l; fb.a = fb.a + mk(LB[10], LB[11], LB[12]); fb.l = fb.l + mk(LB[13], LB[14], LB[15]); }
-        const rbi I5 = rbi_load(K.rb[QR_RB_BASE]);
-        sv6 v5; v5.a = mk(bv[0], bv[1], bv[2]); v5.l = mk(bv[3], bv[4], bv[5]);
-        const sv6 c5 = crf(v5, rbi_mul(I5, v5));
-        Cv[0] = c5.a.x + fb.a.x; Cv[1] = c5.a.y + fb.a.y; Cv[2] = c5.a.z + fb.a.z;
-        Cv[3] = c5.l.x + fb.l.x; Cv[4] = c5.l.y + fb.l.y; Cv[5] = c5.l.z + fb.l.z;
-      }
+      if (lane == 0) wbc_base_coriolis(K, bv, legB, Cv);
       // ---------------- K11 tasks (lane 0) ----------------
       if (lane == 0 && g_tau) {
-        const m3 RotT = transpose(Rwb);
+        const xform3 RotT = transpose(Rwb);
         // --- orientation task (qr_task_body_orientation.cpp:43-81)
         {
             // quatDes = rpyToQuat(pBody_RPY_des): rotationMatrixToQuaternion(rpyToRotMat(rpy))
-            const m3 Rr = mul(mul(coord_rot_sc(0, sS[12], sC[12]), coord_rot_sc(1, sS[13], sC[13])), coord_rot_sc(2, sS[14], sC[14]));
-            const m3 r = transpose(Rr);
+            const xform3 Rr = mul(mul(coord_rot_sc(0, sS[12], sC[12]), coord_rot_sc(1, sS[13], sC[13])), coord_rot_sc(2, sS[14], sC[14]));
+            const xform3 r = transpose(Rr);
             real qd4[4];
             const real tr = r.m[0][0] + r.m[1][1] + r.m[2][2];
             if (tr > 0.0) {
@@ -1161,7 +837,7 @@ void qr_wbc_kernel(int n, const WbcConst *__restrict__ types, const int *__restr
             const real *nr = Np + c0 * 18 + j, *jr = J3 + i * ld;
             JtP[lane] = (jr[0] * nr[0] + jr[1] * nr[18]) + jr[2] * nr[36];
         }
-        wsync();
+        wave_sync();
     };
     // N_pre <- N_pre - T JtPre  (T = N_pre pinv, 18 x 3): the rank-3 form of N_pre (I - pinv JtPre)
     auto npre_update = [&](const real *T) {
@@ -1173,7 +849,7 @@ void qr_wbc_kernel(int n, const WbcConst *__restrict__ types, const int *__restr
                 Np[e] -= (T[3 * i] * JtP[j] + T[3 * i + 1] * JtP[18 + j]) + T[3 * i + 2] * JtP[36 + j];
             }
         }
-        wsync();
+        wave_sync();
     };
     // lamI (registers, every lane) <- pinv of the 3 x 3 in `lam` with eigenvalue cut thr
     auto pinv3 = [&](real thr, real iv[6]) {
@@ -1191,13 +867,13 @@ void qr_wbc_kernel(int n, const WbcConst *__restrict__ types, const int *__restr
         constexpr int UM = (D * D + 63) / 64;
         if (dynamic) {
             for (int e = lane; e < 18 * D; e += 64) { const int i = e / D, j = e - D * i; T1[e] = dot18(Ai + i * 18, 1, JC + j * 18, 1, 18); }      // temp = Ainv Jc' (18 x D)
-            wsync();
+            wave_sync();
         }
         for (int e = lane; e < D * D; e += 64) {                                                    // lambda^-1 = Jc temp  /  Jc Jc'
             const int i = e / D, j = e - D * i;
             lam[e] = dynamic ? dot18(JC + i * 18, 1, T1 + j, D, 18) : dot18(JC + i * 18, 1, JC + j * 18, 1, 18);
         }
-        wsync();
+        wave_sync();
         psd_pinv<UM>(lane, lam, D, thr, lamI, scr);
         for (int e = lane; e < 18 * D; e += 64) {                                                   // JcBar = temp lambda  /  pinv = Jc' W^+
             const int i = e / D, j = e - D * i;
@@ -1209,7 +885,7 @@ void qr_wbc_kernel(int n, const WbcConst *__restrict__ types, const int *__restr
             for (int k = 0; k < D; k += 3) { a0 += av[k] * bv[k]; a1 += av[k + 1] * bv[k + 1]; a2 += av[k + 2] * bv[k + 2]; }
             JB[e] = (a0 + a1) + a2;
         }
-        wsync();
+        wave_sync();
         if (dynamic && lane < 18) {
             real acc = 0.0;
 #pragma unroll
@@ -1230,7 +906,7 @@ void qr_wbc_kernel(int n, const WbcConst *__restrict__ types, const int *__restr
                 Np[e] = ((i == j) ? 1.0 : 0.0) - ((a0 + a1) + a2);
             }
         }
-        wsync();
+        wave_sync();
     };
 
     QW_TS(5);
@@ -1246,13 +922,13 @@ void qr_wbc_kernel(int n, const WbcConst *__restrict__ types, const int *__restr
             case 4: contact_part(std::integral_constant<int, 12>{}, false, thr2); break;
             default:
                 for (int e = lane; e < 324; e += 64) Np[e] = ((e / 18) == (e % 18)) ? 1.0 : 0.0;
-                wsync();
+                wave_sync();
         }
         for (int t = 0; t < nt; ++t) {
             TASK_COLS(t, c0, J3, ld);
             jt_npre(J3, ld, c0);
             if (lane < 9) { const int a = lane / 3, b2 = lane - 3 * a; lam[lane] = dot18(JtP + a * 18, 1, JtP + b2 * 18, 1, 18); }
-            wsync();
+            wave_sync();
             real iv[6];
             pinv3(thr2, iv);
             if (lane < 54) {                                                                  // pinv(JtPre) = JtPre^T W^+ (18 x 3)
@@ -1260,7 +936,7 @@ void qr_wbc_kernel(int n, const WbcConst *__restrict__ types, const int *__restr
                 const real i0 = j == 0 ? iv[0] : j == 1 ? iv[1] : iv[3], i1 = j == 0 ? iv[1] : j == 1 ? iv[2] : iv[4], i2 = j == 0 ? iv[3] : j == 1 ? iv[4] : iv[5];
                 JtB[lane] = (JtP[r] * i0 + JtP[18 + r] * i1) + JtP[36 + r] * i2;
             }
-            wsync();
+            wave_sync();
             // delta_q = prev + pinv (posErr - Jt prev),  qdot likewise (lanes 0-17 / 18-35); T1 = N_pre pinv for the projector update
             real upd = 0.0;
             if (lane < 36) {
@@ -1276,13 +952,13 @@ void qr_wbc_kernel(int n, const WbcConst *__restrict__ types, const int *__restr
                 upd = ((t > 0) ? prevv[i] : 0.0) + ((JtB[3 * i] * tv3[0] + JtB[3 * i + 1] * tv3[1]) + JtB[3 * i + 2] * tv3[2]);
             }
             if (t < nt - 1 && lane < 54) { const int r = lane / 3, j = lane - 3 * r; T1[lane] = dot18(Np + r * 18, 1, JtB + j, 3, 18); }
-            wsync();
+            wave_sync();
             if (lane < 36) { if (lane < 18) dq1[lane] = upd; else dq2[lane - 18] = upd; }
-            if (t < nt - 1) npre_update(T1); else wsync();
+            if (t < nt - 1) npre_update(T1); else wave_sync();
         }
         if (lane < 12) {
-            st_w(&g_qdes[(size_t)lane * n + rid], (float)(qj[lane] + dq1[6 + lane]), pipe.flag != nullptr);
-            st_w(&g_qdes[(size_t)(12 + lane) * n + rid], (float)dq2[6 + lane], pipe.flag != nullptr);
+            st_through(&g_qdes[(size_t)lane * n + rid], (float)(qj[lane] + dq1[6 + lane]), pipe.flag != nullptr);
+            st_through(&g_qdes[(size_t)(12 + lane) * n + rid], (float)dq2[6 + lane], pipe.flag != nullptr);
         }
       }
       QW_TS1(13);
@@ -1300,7 +976,7 @@ void qr_wbc_kernel(int n, const WbcConst *__restrict__ types, const int *__restr
         default:
             if (lane < 18) qdd[lane] = 0.0;
             for (int e = lane; e < 324; e += 64) Np[e] = ((e / 18) == (e % 18)) ? 1.0 : 0.0;
-            wsync();
+            wave_sync();
     }
     QW_TS(12);
     for (int t = 0; t < nt; ++t) {
@@ -1308,9 +984,9 @@ void qr_wbc_kernel(int n, const WbcConst *__restrict__ types, const int *__restr
         TASK_COLS(t, c0, J3, ld);
         jt_npre(J3, ld, c0);
         if (lane < 54) { const int r = lane / 3, i = lane - 3 * r; T1[lane] = dot18(Ai + r * 18, 1, JtP + i * 18, 1, 18); }      // temp = Ainv JtPre^T (18 x 3)
-        wsync();
+        wave_sync();
         if (lane < 9) { const int a = lane / 3, b2 = lane - 3 * a; lam[lane] = dot18(JtP + a * 18, 1, T1 + b2, 3, 18); }        // lambda^-1 = JtPre temp
-        wsync();
+        wave_sync();
         real iv[6];
         pinv3(thrW, iv);
         if (lane < 54) {                                                                                                      // JtBar = temp lambda
@@ -1318,7 +994,7 @@ void qr_wbc_kernel(int n, const WbcConst *__restrict__ types, const int *__restr
             const real i0 = j == 0 ? iv[0] : j == 1 ? iv[1] : iv[3], i1 = j == 0 ? iv[1] : j == 1 ? iv[2] : iv[4], i2 = j == 0 ? iv[3] : j == 1 ? iv[4] : iv[5];
             JtB[lane] = (T1[3 * r] * i0 + T1[3 * r + 1] * i1) + T1[3 * r + 2] * i2;
         }
-        wsync();
+        wave_sync();
         // qdd += JtBar (xddot - JtDotQdot - Jt qdd): every lane forms the three residuals itself; T2 = Npre JtBar for the projector update
         real upd = 0.0;
         if (lane < 18) {
@@ -1329,9 +1005,9 @@ void qr_wbc_kernel(int n, const WbcConst *__restrict__ types, const int *__restr
             upd = qdd[lane] + ((JtB[3 * lane] * tv3[0] + JtB[3 * lane + 1] * tv3[1]) + JtB[3 * lane + 2] * tv3[2]);
         }
         if (t < nt - 1 && lane < 54) { const int r = lane / 3, j = lane - 3 * r; T2[lane] = dot18(Np + r * 18, 1, JtB + j, 3, 18); }
-        wsync();
+        wave_sync();
         if (lane < 18) qdd[lane] = upd;
-        if (t < nt - 1) npre_update(T2); else wsync();
+        if (t < nt - 1) npre_update(T2); else wave_sync();
     }
 
     QW_TS(7);
@@ -1361,7 +1037,7 @@ void qr_wbc_kernel(int n, const WbcConst *__restrict__ types, const int *__restr
         if (QW_P_TLR && lane == 0) QW_P_TLR[n + rid] = (int)wall_clock64();
         if (!pipe_st && (v & 1u)) { wbc_signal_done(pipe.finished, lane); return; }              // on the MPC's list pass: the second WBC pass behind that launch takes this robot
         if (lane < 12) cm[51 + lane] = (real)__hip_atomic_load(g_fr + (size_t)lane * n + rid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        wsync();
+        wave_sync();
     }
     if (pipe.wait_epoch && ((volatile int *)&sPipe)[0]) pipe_st = QRGPU_ST_PIPE_TIMEOUT;
     wbc_qp_and_store(lane, rid, n, K, nc, cpack, bad_type, eq_dependent, A, JC, cm, W, sI, g_tau, g_status, merge_tau, status_or | (pipe_st ? 2 : 0), epilogue, dbgT, g_qp,

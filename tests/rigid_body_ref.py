@@ -321,3 +321,69 @@ def wbc_cases(pkg, oracle, robot):
             raise AssertionError("no well-conditioned state found for row %d of %s" % (i, robot))
     _wbc_cache[robot] = dict(state=state, cmd=cmd, prev=prev, amp=amp, redrawn=redrawn)
     return _wbc_cache[robot]
+
+
+# ---- the mixed batch of the kernel test (tests/test_gpu_rigid_body.py) and of the host build of its chains (tests/test_wbc_rigid_body_host.py)
+MIXED_ROBOTS = ("a1", "lite3")       # type 0, type 1
+# the project's bars, each times max(1, max|ref|)
+BARS = (("H", 2e-6), ("G", 2e-5), ("C", 2e-6), ("Jc", 1e-6), ("Jcdqd", 2e-5), ("pGC", 1e-6), ("vGC", 1e-6))
+
+
+def interleave(rows_a1, rows_lite3):
+    """A1 rows at even places, Lite3 rows at odd ones (A1 may have one more)."""
+    na, nl = len(rows_a1), len(rows_lite3)
+    assert na in (nl, nl + 1)
+    out = np.empty((na + nl,) + rows_a1.shape[1:], rows_a1.dtype)
+    out[0::2] = rows_a1; out[1::2] = rows_lite3
+    return out
+
+
+_mixed_cache = {}
+
+
+def mixed_batch(pkg, oracle):
+    """One mixed batch, A1 = type 0 and Lite3 = type 1 interleaved through type_id, each robot with the stand (make_batch), wide and edge
+    families; n = 239 is odd and above 64.  With it the float64 oracle on the same raw float32 rows and the model on the normalised ones.
+    -> dict n, state [n,37] float32, tid, family[i] / row[i] (which family robot i's state is from and its row there), oracle, model.
+    Computed once and shared (callers must not modify it)."""
+    if _mixed_cache:
+        return _mixed_cache
+    states, family, row = {}, {}, {}
+    for robot in MIXED_ROBOTS:
+        f = families(pkg, robot)
+        if robot == "a1":          # one more stand state: n odd
+            f["stand"] = np.concatenate([f["stand"], pkg.make_batch(1, 10, "a1", seed=SEEDS["a1"]["stand"] + 1)["fb_state"]])
+        states[robot] = np.concatenate([f["stand"], f["wide"], f["edge"]])
+        family[robot] = np.array(sum(([k] * len(f[k]) for k in ("stand", "wide", "edge")), []))
+        row[robot] = np.concatenate([np.arange(len(f[k])) for k in ("stand", "wide", "edge")])
+    st = interleave(states["a1"], states["lite3"])
+    n = len(st)
+    assert n == 239 and n % 2 == 1 and n > 64
+    tid = pkg.shard.interleave_types(n, 2)
+    shapes = dict(H=(n, 18, 18), G=(n, 18), C=(n, 18), Jc=(n, 4, 3, 18), Jcdqd=(n, 4, 3), pGC=(n, 4, 3), vGC=(n, 4, 3))
+    ora = {k: np.zeros(shapes[k]) for k, _ in BARS}
+    for i in range(n):
+        o = oracle.fb_compute(pkg.model_desc(MIXED_ROBOTS[tid[i]]), st[i].astype(np.float64), np.float64)
+        for k, _ in BARS:
+            ora[k][i] = o[k]
+    model = {k: np.zeros(shapes[k]) for k in ("H", "C")}
+    for t, robot in enumerate(MIXED_ROBOTS):
+        r = compute(pkg.model_desc(robot), normalised(st[t::2]))
+        for k in model:
+            model[k][t::2] = r[k]
+    _mixed_cache.update(n=n, state=st, tid=tid, oracle=ora, model=model, family=interleave(family["a1"], family["lite3"]),
+                        row=interleave(row["a1"], row["lite3"]))
+    return _mixed_cache
+
+
+def rel(got, ref):
+    """Per robot: max|got - ref| / max(1, max|ref|)."""
+    n = len(ref)
+    return np.abs(got - ref).reshape(n, -1).max(1) / np.maximum(1.0, np.abs(ref).reshape(n, -1).max(1))
+
+
+def edge_index(mb, t, r):
+    """The robot of type t that holds row r of its edge family."""
+    i = np.nonzero((mb["tid"] == t) & (mb["family"] == "edge") & (mb["row"] == r))[0]
+    assert len(i) == 1
+    return int(i[0])

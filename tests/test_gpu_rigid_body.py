@@ -16,8 +16,10 @@ import rigid_body_ref as M
 
 pytestmark = pytest.mark.gpu
 
-ROBOTS = ("a1", "lite3")
-BARS = (("H", 2e-6), ("G", 2e-5), ("C", 2e-6), ("Jc", 1e-6), ("Jcdqd", 2e-5), ("pGC", 1e-6), ("vGC", 1e-6))
+ROBOTS = M.MIXED_ROBOTS
+BARS = M.BARS
+_interleave = M.interleave
+_rel = M.rel
 
 
 def _setup_both(ctx, pkg):
@@ -25,52 +27,14 @@ def _setup_both(ctx, pkg):
         ctx.mpc_setup_packed(t, pkg.mpc_cfg(robot), 10); ctx.wbc_setup_packed(t, pkg.model_desc(robot))
 
 
-def _interleave(rows_a1, rows_lite3):
-    """A1 rows at even places, Lite3 rows at odd ones (A1 may have one more)."""
-    na, nl = len(rows_a1), len(rows_lite3)
-    assert na in (nl, nl + 1)
-    out = np.empty((na + nl,) + rows_a1.shape[1:], rows_a1.dtype)
-    out[0::2] = rows_a1; out[1::2] = rows_lite3
-    return out
-
-
 @pytest.fixture(scope="module")
 def rb(gpu_ctx, pkg, oracle):
-    """The mixed batch, what the kernel gives on it, the float64 oracle on the same raw float32 rows and the model on the normalised ones
-    (computed once, shared, read-only).  family[i] / row[i]: which family robot i's state is from and its row there."""
+    """The mixed batch with its references (rigid_body_ref.mixed_batch: computed once, shared, read-only) and what the kernel gives on it."""
     _setup_both(gpu_ctx, pkg)
-    states, family, row = {}, {}, {}
-    for robot in ROBOTS:
-        f = M.families(pkg, robot)
-        if robot == "a1":          # one more stand state: n odd
-            f["stand"] = np.concatenate([f["stand"], pkg.make_batch(1, 10, "a1", seed=M.SEEDS["a1"]["stand"] + 1)["fb_state"]])
-        states[robot] = np.concatenate([f["stand"], f["wide"], f["edge"]])
-        family[robot] = np.array(sum(([k] * len(f[k]) for k in ("stand", "wide", "edge")), []))
-        row[robot] = np.concatenate([np.arange(len(f[k])) for k in ("stand", "wide", "edge")])
-    st = _interleave(states["a1"], states["lite3"])
-    n = len(st)
-    assert n == 239 and n % 2 == 1 and n > 64
-    tid = pkg.shard.interleave_types(n, 2)
-    got = G.run_fb_debug(gpu_ctx, pkg, dict(n=n, fb_state=st), type_id=tid)
-    ora = {k: np.zeros(got[k].shape) for k, _ in BARS}
-    for i in range(n):
-        o = oracle.fb_compute(pkg.model_desc(ROBOTS[tid[i]]), st[i].astype(np.float64), np.float64)
-        for k, _ in BARS:
-            ora[k][i] = o[k]
-    model = {k: np.zeros(got[k].shape) for k in ("H", "C")}
-    for t, robot in enumerate(ROBOTS):
-        r = M.compute(pkg.model_desc(robot), M.normalised(st[t::2]))
-        for k in model:
-            model[k][t::2] = r[k]
-    yield dict(n=n, state=st, tid=tid, got=got, oracle=ora, model=model, family=_interleave(family["a1"], family["lite3"]),
-               row=_interleave(row["a1"], row["lite3"]))
+    mb = M.mixed_batch(pkg, oracle)
+    got = G.run_fb_debug(gpu_ctx, pkg, dict(n=mb["n"], fb_state=mb["state"]), type_id=mb["tid"])
+    yield dict(mb, got=got)
     G.setup_a1(gpu_ctx, pkg, 10)
-
-
-def _rel(got, ref):
-    """Per robot: max|got - ref| / max(1, max|ref|)."""
-    n = len(ref)
-    return np.abs(got - ref).reshape(n, -1).max(1) / np.maximum(1.0, np.abs(ref).reshape(n, -1).max(1))
 
 
 def _report(what, rb, k, rel, tol):
@@ -102,10 +66,7 @@ def test_all_seven_against_the_float64_oracle(rb):
     assert not bad, bad
 
 
-def _edge(rb, t, r):
-    i = np.nonzero((rb["tid"] == t) & (rb["family"] == "edge") & (rb["row"] == r))[0]
-    assert len(i) == 1
-    return int(i[0])
+_edge = M.edge_index
 
 
 def test_negated_quaternion_gives_the_same_bits(rb):
