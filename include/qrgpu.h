@@ -713,6 +713,37 @@ int qrgpu_forward_dynamics_batch(qrgpu_ctx *ctx, int n, const int *d_type_id, co
 int qrgpu_plant_step_batch(qrgpu_ctx *ctx, int n, const qrgpu_plant_params *params, const int *d_type_id, float *d_fb_state,
                            const float *d_motor_cmd, float *d_plant_out, float *d_mpc_state, float *d_est_in, int *d_status);
 
+/* qrgpu_plant_step_terrain_batch: qrgpu_plant_step_batch on a ground that is a height field chosen per robot, with a push on the base held
+ * for the tick.  qrgpu_plant_step_batch itself is untouched: the flat call computes what it computed.
+ *   Field: d_height holds terrain->n_fields grids of ny x nx float32 heights, x fastest (d_height[f][j][i]); node (i, j) lies at
+ *     (x0 + i cell, y0 + j cell).  Robot r stands on field d_field_id[r] (NULL: every robot on field 0).
+ *   Sampler: bicubic Catmull-Rom (cubic convolution, a = -1/2), separable, on the heights widened to fp64.  u = (x - x0) / cell clipped to
+ *     [0, nx - 1]; i = min(floor(u), nx - 2), t = u - i; weights w(t) = 1/2 (-t^3 + 2 t^2 - t, 3 t^3 - 5 t^2 + 2, -3 t^3 + 4 t^2 + t, t^3 - t^2)
+ *     on the nodes i - 1 .. i + 2, each index clamped to [0, nx - 1]; the same in y.  The slopes dz/dx, dz/dy come from the derivative weights
+ *     w'(t) / cell at the same clipped (u, v).  The surface is C1 (the cell on either side of a grid line gives the same height and normal);
+ *     outside the grid it has the height and the normal of the nearest border point.
+ *   Contact law, for a foot at world p with velocity v:  z_g = sampled height + params->ground_z;  n = (-z_x, -z_y, 1) / |.|;
+ *     delta = (z_g - p_z) n_z;  v_n = v . n,  v_t = v - v_n n;  f_n = max(0, contact_k delta (1 - contact_a v_n)) for delta > 0, else 0;
+ *     f = f_n n - mu f_n v_t / sqrt(|v_t|^2 + v_eps^2).  On a constant field this is qrgpu_plant_step_batch's law.
+ *   Push: d_base_push [6][n] = a world-frame force acting at the base origin (rows 0-2) and a world-frame moment (rows 3-5), held over the
+ *     tick; every sub-step rotates them into the base frame and adds [R^T moment; R^T force] to the right-hand side of the base's rows:
+ *     H nu_dot + C + G = [0; tau] + sum_leg Jc^T f + [R^T moment; R^T force; 0].  NULL = none.
+ *   d_terrain_out [QRGPU_TERRAIN_OUT_ROWS][n] (may be NULL): of the state written, per foot, the ground height z_g under the foot [4] at row 0
+ *     and the unit normal there [12] (3 * leg + axis) at row 4.
+ *   d_status: the QRGPU_PL_* bits of qrgpu_plant_step_batch and the two below.
+ * The other arguments, outputs and rules are qrgpu_plant_step_batch's.  QRGPU_ERR_BAD_ARG (nothing launched) also for a NULL terrain or
+ * d_height, nx or ny < 2, n_fields < 1, cell <= 0 or not finite, x0 or y0 not finite.  One launch on the context's stream. */
+struct qrgpu_terrain_desc { int nx, ny, n_fields; float x0, y0, cell; };
+typedef struct qrgpu_terrain_desc qrgpu_terrain_desc;
+#define QRGPU_TERRAIN_OUT_ROWS 16       /* per foot: ground height under the foot [4] at row 0, unit normal [12] at row 4, of the state written */
+#define QRGPU_PL_BAD_FIELD 0x4          /* d_field_id outside 0..n_fields-1: field 0 was used */
+#define QRGPU_PL_OFF_FIELD 0x8          /* a foot with f_n > 0 outside the grid in the last sub-step: the border was extended */
+int qrgpu_plant_step_terrain_batch(qrgpu_ctx *ctx, int n, const qrgpu_plant_params *params, const qrgpu_terrain_desc *terrain,
+                                   const float *d_height, const int *d_field_id /* [n], NULL = field 0 */,
+                                   const float *d_base_push /* [6][n] force, moment; NULL = none */, const int *d_type_id, float *d_fb_state,
+                                   const float *d_motor_cmd, float *d_plant_out, float *d_terrain_out, float *d_mpc_state, float *d_est_in,
+                                   int *d_status);
+
 /* ---- multi-GPU: all-gather of the per-robot torques over RCCL / xGMI ----------------------------------------
  * One process per GPU, one context per process; rank r of N owns a contiguous shard of the robot population and there is no exchange
  * inside a tick.  The only collective of the path collects every rank's tau[12][n_local] on every rank:

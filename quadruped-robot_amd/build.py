@@ -49,7 +49,7 @@ def build(force=False, verbose=False):
 
 
 # what each translation unit includes beyond itself: an object is rebuilt only when one of these (or the flags) is newer than it
-KERNEL_DEPS = ["qr_device_types.h", "qr_wave_helpers.h", "qr_kernels.h", "qr_rigid_body.h", "qr_wbc_rigid_body.h", "qr_plant_math.h", os.path.join("..", "..", "include", "qrgpu.h")]
+KERNEL_DEPS = ["qr_device_types.h", "qr_wave_helpers.h", "qr_kernels.h", "qr_rigid_body.h", "qr_wbc_rigid_body.h", "qr_plant_math.h", "qr_terrain.h", os.path.join("..", "..", "include", "qrgpu.h")]
 HOST_DEPS = KERNEL_DEPS + ["qrgpu_ctx.h", "qr_wbc_model.h"]
 EXTRA_DEPS = {"qr_mpc_kernel_fl.hip": ["qr_mpc_kernel.hip"], "qr_wbc_kernel_dbg.hip": ["qr_wbc_kernel.hip"]}
 

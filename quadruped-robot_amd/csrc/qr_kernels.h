@@ -79,5 +79,8 @@ __global__ void qr_fwd_dyn_kernel(int n, const WbcConst *types, const int *type_
                                   float *g_nudot, int *g_status);
 __global__ void qr_plant_step_kernel(int n, qrgpu_plant_params P, const WbcConst *types, const int *type_id, int type_ready, float *g_state, const float *g_cmd,
                                      float *g_out, float *g_mpc, float *g_est, int *g_status);
+__global__ void qr_plant_step_terrain_kernel(int n, qrgpu_plant_params P, qrgpu_terrain_desc T, const WbcConst *types, const int *type_id, int type_ready,
+                                             const float *g_height, const int *g_field, const float *g_push, float *g_state, const float *g_cmd, float *g_out,
+                                             float *g_tout, float *g_mpc, float *g_est, int *g_status);
 
 }  // namespace qrgpu

@@ -366,4 +366,18 @@ int qrgpu_plant_step_batch(qrgpu_ctx *c, int n, const qrgpu_plant_params *params
                         d_motor_cmd, d_plant_out, d_mpc_state, d_est_in, d_status);
 }
 
+int qrgpu_plant_step_terrain_batch(qrgpu_ctx *c, int n, const qrgpu_plant_params *params, const qrgpu_terrain_desc *terrain, const float *d_height,
+                                   const int *d_field_id, const float *d_base_push, const int *d_type_id, float *d_fb_state, const float *d_motor_cmd,
+                                   float *d_plant_out, float *d_terrain_out, float *d_mpc_state, float *d_est_in, int *d_status)
+{
+    if (!batch_ok(c, n) || !params || !d_fb_state || !d_motor_cmd || !terrain || !d_height) return QRGPU_ERR_BAD_ARG;
+    if (params->substeps < 1 || params->substeps > 64 || !(params->dt > 0.f)) return QRGPU_ERR_BAD_ARG;
+    if (terrain->nx < 2 || terrain->ny < 2 || terrain->n_fields < 1 || !(terrain->cell > 0.f) || !std::isfinite(terrain->cell)) return QRGPU_ERR_BAD_ARG;
+    if (!std::isfinite(terrain->x0) || !std::isfinite(terrain->y0)) return QRGPU_ERR_BAD_ARG;
+    const int e = plant_model(c, d_type_id);
+    if (e != QRGPU_OK) return e;
+    return launch_stage(c, qr_plant_step_terrain_kernel, per_quad(n), dim3(64), n, *params, *terrain, (const WbcConst *)c->d_wbc, d_type_id, ready_mask(c->wbc_ready),
+                        d_height, d_field_id, d_base_push, d_fb_state, d_motor_cmd, d_plant_out, d_terrain_out, d_mpc_state, d_est_in, d_status);
+}
+
 }  // extern "C"

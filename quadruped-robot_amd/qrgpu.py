@@ -191,6 +191,19 @@ def plant_params(**fields):
     return _set_fields(d, fields)
 
 
+TERRAIN_OUT_ROWS = 16
+PL_BAD_FIELD, PL_OFF_FIELD = 0x4, 0x8
+
+
+class terrain_desc_struct(C.Structure):
+    _fields_ = [("nx", C.c_int), ("ny", C.c_int), ("n_fields", C.c_int), ("x0", C.c_float), ("y0", C.c_float), ("cell", C.c_float)]
+
+
+def terrain_desc(nx, ny, n_fields=1, x0=0.0, y0=0.0, cell=0.1):
+    """qrgpu_terrain_desc: n_fields grids of ny x nx heights, x fastest; node (i, j) lies at (x0 + i cell, y0 + j cell)."""
+    return terrain_desc_struct(int(nx), int(ny), int(n_fields), float(x0), float(y0), float(cell))
+
+
 EPILOGUE_HIP_COMP, EPILOGUE_CLIP = 1, 2
 COMM_ID_BYTES = 128
 
@@ -222,7 +235,8 @@ EXPORTS = ["qrgpu_model_desc_default", "qrgpu_create", "qrgpu_destroy", "qrgpu_s
            "qrgpu_memcpy_async", "qrgpu_memset_async", "qrgpu_mark", "qrgpu_mark_elapsed_ms", "qrgpu_set_tick_pipeline", "qrgpu_set_tick_overlap",
            "qrgpu_tick_fence", "qrgpu_tick_overlap_stats", "qrgpu_swing_mode_desc_default", "qrgpu_swing_update_batch", "qrgpu_swing_action_batch",
            "qrgpu_stance_desc_default", "qrgpu_stance_update_batch", "qrgpu_stance_command_batch", "qrgpu_stance_tick_batch",
-           "qrgpu_pose_plan_desc_default", "qrgpu_pose_plan_batch", "qrgpu_plant_params_default", "qrgpu_forward_dynamics_batch", "qrgpu_plant_step_batch"]
+           "qrgpu_pose_plan_desc_default", "qrgpu_pose_plan_batch", "qrgpu_plant_params_default", "qrgpu_forward_dynamics_batch", "qrgpu_plant_step_batch",
+           "qrgpu_plant_step_terrain_batch"]
 
 
 def load_library():
@@ -302,6 +316,7 @@ def load_library():
     lib.qrgpu_plant_params_default.argtypes = [C.POINTER(plant_params_struct)]; lib.qrgpu_plant_params_default.restype = None
     lib.qrgpu_forward_dynamics_batch.argtypes = [vp, ip] + [vp] * 6
     lib.qrgpu_plant_step_batch.argtypes = [vp, ip, C.POINTER(plant_params_struct)] + [vp] * 7
+    lib.qrgpu_plant_step_terrain_batch.argtypes = [vp, ip, C.POINTER(plant_params_struct), C.POINTER(terrain_desc_struct)] + [vp] * 11
     lib.qrgpu_vmc_force1.argtypes = [vp, ip, fp, fp, fp, fp, C.POINTER(ip)]
     lib.qrgpu_vmc_force_world1.argtypes = [vp, ip, fp, fp, fp, fp, fp, C.POINTER(ip)]
     lib.qrgpu_mpc_frontend_batch.argtypes = [vp, ip, ip, C.c_float, C.c_float] + [vp] * 6
@@ -694,6 +709,15 @@ class Context:
         and rows 0-40 of est_in [54][n] are written when given."""
         self._chk(self._lib.qrgpu_plant_step_batch(self._h, n, C.byref(params), _dp(type_id), _dp(fb_state), _dp(motor_cmd), _dp(plant_out),
                                                    _dp(mpc_state), _dp(est_in), _dp(status)))
+
+    def plant_step_terrain_batch(self, n, params, terrain, height, fb_state, motor_cmd, field_id=None, base_push=None, plant_out=None, terrain_out=None,
+                                 mpc_state=None, est_in=None, status=None, type_id=None):
+        """plant_step_batch on a height field: terrain = terrain_desc(), height [n_fields][ny][nx] float32 on the device, field_id [n] int32
+        (None: field 0), base_push [6][n] = world-frame force at the base origin and moment, held over the tick (None: none).  terrain_out
+        [TERRAIN_OUT_ROWS][n]: ground height under each foot and the unit normal there, of the state written."""
+        self._chk(self._lib.qrgpu_plant_step_terrain_batch(self._h, n, C.byref(params), C.byref(terrain), _dp(height), _dp(field_id), _dp(base_push),
+                                                           _dp(type_id), _dp(fb_state), _dp(motor_cmd), _dp(plant_out), _dp(terrain_out), _dp(mpc_state),
+                                                           _dp(est_in), _dp(status)))
 
     def mpc_frontend_batch(self, n, fe_in, fe_state, traj, gait, wbc_cmd=None, mpc_updated=None, num_horizon_l=2, dt_ctrl=0.002, dt_mpc=0.06):
         """SetupCommand + Run + UpdateMPC (without the solve) of n robots: qr_mpc_stance_leg_controller.cpp:158-382."""
