@@ -737,12 +737,63 @@ struct qrgpu_terrain_desc { int nx, ny, n_fields; float x0, y0, cell; };
 typedef struct qrgpu_terrain_desc qrgpu_terrain_desc;
 #define QRGPU_TERRAIN_OUT_ROWS 16       /* per foot: ground height under the foot [4] at row 0, unit normal [12] at row 4, of the state written */
 #define QRGPU_PL_BAD_FIELD 0x4          /* d_field_id outside 0..n_fields-1: field 0 was used */
-#define QRGPU_PL_OFF_FIELD 0x8          /* a foot with f_n > 0 outside the grid in the last sub-step: the border was extended */
+#define QRGPU_PL_OFF_FIELD 0x8          /* a foot (the body call: any point) with f_n > 0 outside the grid in the last sub-step: the border was extended */
 int qrgpu_plant_step_terrain_batch(qrgpu_ctx *ctx, int n, const qrgpu_plant_params *params, const qrgpu_terrain_desc *terrain,
                                    const float *d_height, const int *d_field_id /* [n], NULL = field 0 */,
                                    const float *d_base_push /* [6][n] force, moment; NULL = none */, const int *d_type_id, float *d_fb_state,
                                    const float *d_motor_cmd, float *d_plant_out, float *d_terrain_out, float *d_mpc_state, float *d_est_in,
                                    int *d_status);
+
+/* qrgpu_plant_step_body_batch: qrgpu_plant_step_terrain_batch for a robot that has a body -- it touches the ground with its knees and its trunk
+ * as well as its feet, and its joints have stops.  A robot that loses its footing comes to rest on the ground, finite, and says so in d_status.
+ * The flat and the terrain call are untouched: they compute what they computed.
+ *   Points: a robot has 16 contact points.  Per leg l (FR FL RR RL, signs sx, sy as for the abad location): the foot, as in the other calls; the
+ *     knee, the origin of the knee link's frame, with that origin's velocity; and the two trunk corners on the leg's side,
+ *     trunk_center + (sx hx, sy hy, -+hz) in the base frame, moving with the base (the four top corners carry a robot on its back).
+ *   Every point takes the terrain call's law unchanged: the surface sampled at the point's world x, y, z_g = sampled height + ground_z, and
+ *     f = f_n n - mu f_n v_t / sqrt(|v_t|^2 + v_eps^2) with the call's contact_k, contact_a, mu, v_eps.  Points, no radii; no new contact parameter.
+ *   Joint limits, per joint with lo = q_lo, hi = q_hi of its kind (abad, hip, knee), k_l = limit_k, a_l = limit_a:
+ *     tau_lim = -max(0, k_l (q - hi) (1 + a_l qd)) for q > hi,  +max(0, k_l (lo - q) (1 - a_l qd)) for q < lo,  0 otherwise:
+ *     one-sided and continuous in the state, like the contact law.  It is added to the joint torque AFTER the motor law's clip: a stop is not
+ *     the motor.
+ *   Each sub-step:  H nu_dot + C + G = [0; tau_motor + tau_lim] + sum_feet Jc^T f + sum_knees Jk^T f_k + sum_corners Jc^T f_c
+ *     + [R^T moment; R^T force; 0], with the field, the per-robot field id, the push, the integrator and the fp64 state of the terrain call.
+ *   Per type: qrgpu_plant_body_setup keeps one qrgpu_plant_body_desc per type_id beside the model constants of qrgpu_wbc_setup.
+ *     QRGPU_ERR_BAD_ARG for a non-finite or non-positive trunk_half, a non-finite trunk_center or limit, q_lo >= q_hi, a negative or non-finite
+ *     limit_k or limit_a.
+ *   d_plant_out, d_terrain_out, d_mpc_state, d_est_in: the terrain call's (the torque rows of d_plant_out hold the motor's torque).
+ *   d_body_out [QRGPU_BODY_OUT_ROWS][n] (may be NULL), of the last sub-step: knee force, world frame [12] (3 * leg + axis) at row 0; knee
+ *     contact flag [4] (f_n > contact_threshold) at row 12; the corners' f_n [8] (2 * leg + top) at row 16; tau_lim [12] at row 24.
+ *   d_status: the terrain call's bits and the three below; QRGPU_PL_OFF_FIELD here means ANY point with f_n > 0 outside the grid.
+ * QRGPU_ERR_BAD_ARG as the terrain call; QRGPU_ERR_NOT_SETUP also unless every type set up with qrgpu_wbc_setup has a body desc.  One launch on
+ * the context's stream.
+ *
+ * Defaults of the stops.  The integrator is semi-implicit Euler, stable on an oscillator for omega h < 2; omega h <= 0.2 keeps a stop's
+ * frequency error under one percent.  The stiffest oscillator a stop can meet is the joint with the smallest reflected inertia, the knee: the knee
+ * link about its axis, I_yy + m (c_x^2 + c_z^2) = 3014e-6 + 0.166 (0.006435^2 + 0.107^2) = 4.92e-3 kg m^2, plus k_rot^2 times the rotor's 1e-8
+ * (gear ratio 1: nothing).  At the default sub-step h = 1 ms, omega <= 200 rad/s gives k_l <= 4.92e-3 * 200^2 = 197 N m/rad; the default is
+ * limit_k = 150 (omega h = 0.175; the motor's 33.5 N m hold a joint 0.22 rad beyond its stop).  The damping rate a stop adds is
+ * k_l a_l x / I at excursion x; with limit_a = 0.02 s/rad it is 0.3 / h at x = 0.5 rad, well inside the integrator's bound of 2 / h. */
+struct qrgpu_plant_body_desc {
+    float trunk_half[3];        /* hx, hy, hz of the trunk box, m */
+    float trunk_center[3];      /* its centre in the base frame */
+    float q_lo[3], q_hi[3];     /* joint limits of abad, hip, knee, rad, in this library's sign convention (stand pose 0, 0.8, -1.6) */
+    float limit_k;              /* N m / rad */
+    float limit_a;              /* s / rad */
+};
+typedef struct qrgpu_plant_body_desc qrgpu_plant_body_desc;
+#define QRGPU_BODY_OUT_ROWS 36
+#define QRGPU_PL_TRUNK_CONTACT 0x10     /* a trunk corner with f_n > contact_threshold in the last sub-step */
+#define QRGPU_PL_KNEE_CONTACT  0x20     /* a knee with f_n > contact_threshold in the last sub-step */
+#define QRGPU_PL_JOINT_LIMIT   0x40     /* a joint beyond a stop (tau_lim != 0) in the last sub-step */
+/* A1: a1_description's trunk box 0.267 x 0.194 x 0.114 at the base origin; limits +-46 deg, -60..240 deg, -154.5..-52.5 deg; 150, 0.02 */
+void qrgpu_plant_body_desc_default(qrgpu_plant_body_desc *desc);
+int qrgpu_plant_body_setup(qrgpu_ctx *ctx, int type_id, const qrgpu_plant_body_desc *desc);
+int qrgpu_plant_step_body_batch(qrgpu_ctx *ctx, int n, const qrgpu_plant_params *params, const qrgpu_terrain_desc *terrain,
+                                const float *d_height, const int *d_field_id /* [n], NULL = field 0 */,
+                                const float *d_base_push /* [6][n] force, moment; NULL = none */, const int *d_type_id, float *d_fb_state,
+                                const float *d_motor_cmd, float *d_plant_out, float *d_terrain_out, float *d_body_out, float *d_mpc_state,
+                                float *d_est_in, int *d_status);
 
 /* ---- multi-GPU: all-gather of the per-robot torques over RCCL / xGMI ----------------------------------------
  * One process per GPU, one context per process; rank r of N owns a contiguous shard of the robot population and there is no exchange

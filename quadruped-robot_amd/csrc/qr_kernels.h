@@ -83,4 +83,10 @@ __global__ void qr_plant_step_terrain_kernel(int n, qrgpu_plant_params P, qrgpu_
                                              const float *g_height, const int *g_field, const float *g_push, float *g_state, const float *g_cmd, float *g_out,
                                              float *g_tout, float *g_mpc, float *g_est, int *g_status);
 
+
+// qr_plant_body_kernel.hip: the terrain step with knee and trunk contact and joint limits; bodies [QRGPU_MAX_TYPES] beside types
+__global__ void qr_plant_step_body_kernel(int n, qrgpu_plant_params P, qrgpu_terrain_desc T, const WbcConst *types, const qrgpu_plant_body_desc *bodies,
+                                          const int *type_id, int type_ready, const float *g_height, const int *g_field, const float *g_push, float *g_state,
+                                          const float *g_cmd, float *g_out, float *g_tout, float *g_bout, float *g_mpc, float *g_est, int *g_status);
+
 }  // namespace qrgpu

@@ -187,6 +187,7 @@ int qrgpu_create(int device_id, int max_batch, int horizon_max, qrgpu_ctx **out)
     auto zalloc = [](auto **p, size_t bytes) { return hipMalloc((void **)p, bytes) == hipSuccess && hipMemset(*p, 0, bytes) == hipSuccess; };
     bool ok = stage_ok && hipMalloc(&c->d_wbc, sizeof(WbcConst) * QRGPU_MAX_TYPES) == hipSuccess;
     const size_t nb = (size_t)max_batch;
+    ok = ok && zalloc(&c->d_body, sizeof(qrgpu_plant_body_desc) * QRGPU_MAX_TYPES);
     ok = ok && zalloc(&c->d_cost[0], sizeof(int) * nb) && zalloc(&c->d_cost[1], sizeof(int) * nb) && hipMalloc(&c->d_warm, (size_t)QR_WARM_STRIDE * nb) == hipSuccess &&
          hipStreamCreateWithFlags(&c->wbc_stream, hipStreamNonBlocking) == hipSuccess &&
          zalloc(&c->d_main_started, sizeof(int)) && zalloc(&c->d_tick_done, sizeof(int)) && zalloc(&c->d_gate_abort, QR_ABORT_RING * sizeof(int)) &&
@@ -225,7 +226,7 @@ void qrgpu_destroy(qrgpu_ctx *c)
     for (int k = 0; k < 2; ++k) if (c->ev_call[k]) hipEventDestroy(c->ev_call[k]);
     if (c->h_stage) (void)hipHostFree(c->h_stage);              // (zero copy: d_in1, d_out1 and d_st1 point into this block)
     else for (void *p : {(void *)c->d_in1, (void *)c->d_out1, (void *)c->d_st1}) (void)hipFree(p);
-    for (void *p : {(void *)c->d_wbc, (void *)c->d_cost[0], (void *)c->d_cost[1], (void *)c->d_warm, (void *)c->d_flops, (void *)c->d_main_started, (void *)c->d_ftime,
+    for (void *p : {(void *)c->d_wbc, (void *)c->d_body, (void *)c->d_cost[0], (void *)c->d_cost[1], (void *)c->d_warm, (void *)c->d_flops, (void *)c->d_main_started, (void *)c->d_ftime,
                     (void *)c->d_wbc_finished, (void *)c->d_gate_abort, (void *)c->d_solved, (void *)c->d_wbc_done, (void *)c->d_gather_done, (void *)c->d_tick_done,
                     (void *)c->d_timeline, (void *)c->d_tlr, (void *)c->d_sinv_spill, c->d_dbg_cycles, c->d_dbg_cycles_wbc, (void *)c->d_join_dbg})
         (void)hipFree(p);                                      // (null: a no-op)

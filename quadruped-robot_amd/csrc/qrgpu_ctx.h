@@ -93,6 +93,11 @@ struct qrgpu_ctx {
     WbcConst wbc_host[QRGPU_MAX_TYPES];
     WbcConst *d_wbc = nullptr;
     bool wbc_dirty = true;
+    // the plant's body per type (qrgpu_plant_body_setup): a device array of its own beside d_wbc, uploaded like it
+    qrgpu_plant_body_desc body_host[QRGPU_MAX_TYPES] = {};
+    qrgpu_plant_body_desc *d_body = nullptr;
+    bool body_ready[QRGPU_MAX_TYPES] = {false, false, false, false};
+    bool body_dirty = true;
     // scratch for the single-robot calls and the fused tick
     // Staging of the single-robot calls.  Default: ONE block of pinned, mapped host memory that the kernels read and write in place (zero
     // copy: d_* are the device-side addresses of h_*), so a call is "fill h_in1, one launch, wait, read h_out1" with no copy command on the

@@ -380,4 +380,50 @@ int qrgpu_plant_step_terrain_batch(qrgpu_ctx *c, int n, const qrgpu_plant_params
                         d_height, d_field_id, d_base_push, d_fb_state, d_motor_cmd, d_plant_out, d_terrain_out, d_mpc_state, d_est_in, d_status);
 }
 
+void qrgpu_plant_body_desc_default(qrgpu_plant_body_desc *d)
+{   // a1_description: the trunk's collision box 0.267 x 0.194 x 0.114 at the base origin; hip +-46 deg, thigh -60..240 deg, calf -154.5..-52.5 deg
+    if (!d) return;
+    memset(d, 0, sizeof(*d));
+    d->trunk_half[0] = 0.1335f; d->trunk_half[1] = 0.097f; d->trunk_half[2] = 0.057f;
+    d->q_lo[0] = -0.802851455917f; d->q_hi[0] = 0.802851455917f;
+    d->q_lo[1] = -1.0471975512f; d->q_hi[1] = 4.18879020479f;
+    d->q_lo[2] = -2.69653369433f; d->q_hi[2] = -0.916297857297f;
+    d->limit_k = 150.f; d->limit_a = 0.02f;                       // include/qrgpu.h derives them
+}
+
+int qrgpu_plant_body_setup(qrgpu_ctx *c, int type_id, const qrgpu_plant_body_desc *desc)
+{
+    if (!c || type_id < 0 || type_id >= QRGPU_MAX_TYPES || !desc) return QRGPU_ERR_BAD_ARG;
+    for (int k = 0; k < 3; ++k) {
+        if (!std::isfinite(desc->trunk_half[k]) || !(desc->trunk_half[k] > 0.f) || !std::isfinite(desc->trunk_center[k])) return QRGPU_ERR_BAD_ARG;
+        if (!std::isfinite(desc->q_lo[k]) || !std::isfinite(desc->q_hi[k]) || !(desc->q_lo[k] < desc->q_hi[k])) return QRGPU_ERR_BAD_ARG;
+    }
+    if (!std::isfinite(desc->limit_k) || !(desc->limit_k >= 0.f) || !std::isfinite(desc->limit_a) || !(desc->limit_a >= 0.f)) return QRGPU_ERR_BAD_ARG;
+    c->body_host[type_id] = *desc;
+    c->body_ready[type_id] = true;
+    c->body_dirty = true;
+    return QRGPU_OK;
+}
+
+int qrgpu_plant_step_body_batch(qrgpu_ctx *c, int n, const qrgpu_plant_params *params, const qrgpu_terrain_desc *terrain, const float *d_height,
+                                const int *d_field_id, const float *d_base_push, const int *d_type_id, float *d_fb_state, const float *d_motor_cmd,
+                                float *d_plant_out, float *d_terrain_out, float *d_body_out, float *d_mpc_state, float *d_est_in, int *d_status)
+{
+    if (!batch_ok(c, n) || !params || !d_fb_state || !d_motor_cmd || !terrain || !d_height) return QRGPU_ERR_BAD_ARG;
+    if (params->substeps < 1 || params->substeps > 64 || !(params->dt > 0.f)) return QRGPU_ERR_BAD_ARG;
+    if (terrain->nx < 2 || terrain->ny < 2 || terrain->n_fields < 1 || !(terrain->cell > 0.f) || !std::isfinite(terrain->cell)) return QRGPU_ERR_BAD_ARG;
+    if (!std::isfinite(terrain->x0) || !std::isfinite(terrain->y0)) return QRGPU_ERR_BAD_ARG;
+    for (int t = 0; t < QRGPU_MAX_TYPES; ++t) if (c->wbc_ready[t] && !c->body_ready[t]) return QRGPU_ERR_NOT_SETUP;      // a type with a model and no body
+    const int e = plant_model(c, d_type_id);
+    if (e != QRGPU_OK) return e;
+    if (c->body_dirty) {
+        HIPCHK(c, hipMemcpyAsync(c->d_body, c->body_host, sizeof(c->body_host), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->body_dirty = false;
+    }
+    return launch_stage(c, qr_plant_step_body_kernel, per_quad(n), dim3(64), n, *params, *terrain, (const WbcConst *)c->d_wbc, (const qrgpu_plant_body_desc *)c->d_body,
+                        d_type_id, ready_mask(c->wbc_ready), d_height, d_field_id, d_base_push, d_fb_state, d_motor_cmd, d_plant_out, d_terrain_out, d_body_out,
+                        d_mpc_state, d_est_in, d_status);
+}
+
 }  // extern "C"

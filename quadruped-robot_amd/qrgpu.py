@@ -204,6 +204,29 @@ def terrain_desc(nx, ny, n_fields=1, x0=0.0, y0=0.0, cell=0.1):
     return terrain_desc_struct(int(nx), int(ny), int(n_fields), float(x0), float(y0), float(cell))
 
 
+BODY_OUT_ROWS = 36
+PL_TRUNK_CONTACT, PL_KNEE_CONTACT, PL_JOINT_LIMIT = 0x10, 0x20, 0x40
+
+
+class plant_body_desc_struct(C.Structure):
+    _fields_ = [("trunk_half", C.c_float * 3), ("trunk_center", C.c_float * 3), ("q_lo", C.c_float * 3), ("q_hi", C.c_float * 3), ("limit_k", C.c_float),
+                ("limit_a", C.c_float)]
+
+
+# What differs from the library's default (A1) per robot.  Lite3: the trunk's collision box 0.234 x 0.184 x 0.08 and the joint limits of
+# lite3_description (HipX +-0.523, HipY -2.67..0.314, Knee 0.524..2.792) mapped into this library's sign convention, in which hip and knee turn the
+# other way (the stand pose is 0, 0.8, -1.6; that description's knee is positive): lo = -upper, hi = -lower.
+PLANT_BODY = {"a1": {}, "lite3": dict(trunk_half=(0.117, 0.092, 0.04), q_lo=(-0.523, -0.314, -2.792), q_hi=(0.523, 2.67, -0.524))}
+
+
+def plant_body_desc(robot="a1", **fields):
+    """qrgpu_plant_body_desc of "a1" (the library's default) or "lite3": trunk box, joint limits, the stops' stiffness and damping, with any field
+    overridden (scalars or sequences by name)."""
+    d = plant_body_desc_struct()
+    load_library().qrgpu_plant_body_desc_default(C.byref(d))
+    return _set_fields(_set_fields(d, PLANT_BODY[robot]), fields)
+
+
 EPILOGUE_HIP_COMP, EPILOGUE_CLIP = 1, 2
 COMM_ID_BYTES = 128
 
@@ -236,7 +259,7 @@ EXPORTS = ["qrgpu_model_desc_default", "qrgpu_create", "qrgpu_destroy", "qrgpu_s
            "qrgpu_tick_fence", "qrgpu_tick_overlap_stats", "qrgpu_swing_mode_desc_default", "qrgpu_swing_update_batch", "qrgpu_swing_action_batch",
            "qrgpu_stance_desc_default", "qrgpu_stance_update_batch", "qrgpu_stance_command_batch", "qrgpu_stance_tick_batch",
            "qrgpu_pose_plan_desc_default", "qrgpu_pose_plan_batch", "qrgpu_plant_params_default", "qrgpu_forward_dynamics_batch", "qrgpu_plant_step_batch",
-           "qrgpu_plant_step_terrain_batch"]
+           "qrgpu_plant_step_terrain_batch", "qrgpu_plant_body_desc_default", "qrgpu_plant_body_setup", "qrgpu_plant_step_body_batch"]
 
 
 def load_library():
@@ -317,6 +340,9 @@ def load_library():
     lib.qrgpu_forward_dynamics_batch.argtypes = [vp, ip] + [vp] * 6
     lib.qrgpu_plant_step_batch.argtypes = [vp, ip, C.POINTER(plant_params_struct)] + [vp] * 7
     lib.qrgpu_plant_step_terrain_batch.argtypes = [vp, ip, C.POINTER(plant_params_struct), C.POINTER(terrain_desc_struct)] + [vp] * 11
+    lib.qrgpu_plant_body_desc_default.argtypes = [C.POINTER(plant_body_desc_struct)]; lib.qrgpu_plant_body_desc_default.restype = None
+    lib.qrgpu_plant_body_setup.argtypes = [vp, ip, C.POINTER(plant_body_desc_struct)]
+    lib.qrgpu_plant_step_body_batch.argtypes = [vp, ip, C.POINTER(plant_params_struct), C.POINTER(terrain_desc_struct)] + [vp] * 12
     lib.qrgpu_vmc_force1.argtypes = [vp, ip, fp, fp, fp, fp, C.POINTER(ip)]
     lib.qrgpu_vmc_force_world1.argtypes = [vp, ip, fp, fp, fp, fp, fp, C.POINTER(ip)]
     lib.qrgpu_mpc_frontend_batch.argtypes = [vp, ip, ip, C.c_float, C.c_float] + [vp] * 6
@@ -718,6 +744,19 @@ class Context:
         self._chk(self._lib.qrgpu_plant_step_terrain_batch(self._h, n, C.byref(params), C.byref(terrain), _dp(height), _dp(field_id), _dp(base_push),
                                                            _dp(type_id), _dp(fb_state), _dp(motor_cmd), _dp(plant_out), _dp(terrain_out), _dp(mpc_state),
                                                            _dp(est_in), _dp(status)))
+
+    def plant_body_setup(self, type_id, desc):
+        """The body of robot type type_id (plant_body_desc()): what plant_step_body_batch needs for every type set up with wbc_setup."""
+        self._chk(self._lib.qrgpu_plant_body_setup(self._h, type_id, C.byref(desc)))
+
+    def plant_step_body_batch(self, n, params, terrain, height, fb_state, motor_cmd, field_id=None, base_push=None, plant_out=None, terrain_out=None,
+                              body_out=None, mpc_state=None, est_in=None, status=None, type_id=None):
+        """plant_step_terrain_batch for robots with a body: the knees and the eight trunk corners touch the ground by the feet's law, the joints
+        have stops.  body_out [BODY_OUT_ROWS][n]: knee force, knee contact, the corners' f_n, the stops' torques, of the last sub-step; status
+        names a fall (PL_TRUNK_CONTACT, PL_KNEE_CONTACT) and a joint at a stop (PL_JOINT_LIMIT)."""
+        self._chk(self._lib.qrgpu_plant_step_body_batch(self._h, n, C.byref(params), C.byref(terrain), _dp(height), _dp(field_id), _dp(base_push),
+                                                        _dp(type_id), _dp(fb_state), _dp(motor_cmd), _dp(plant_out), _dp(terrain_out), _dp(body_out),
+                                                        _dp(mpc_state), _dp(est_in), _dp(status)))
 
     def mpc_frontend_batch(self, n, fe_in, fe_state, traj, gait, wbc_cmd=None, mpc_updated=None, num_horizon_l=2, dt_ctrl=0.002, dt_mpc=0.06):
         """SetupCommand + Run + UpdateMPC (without the solve) of n robots: qr_mpc_stance_leg_controller.cpp:158-382."""

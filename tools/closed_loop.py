@@ -5,6 +5,7 @@ inside the loop.
   python tools/closed_loop.py [--robots 1024] [--ticks 500] [--substeps 2]            prints ONE JSON line
   rocprofv3 --kernel-trace --stats -d DIR -- python tools/closed_loop.py --profile    the same loop as the workload of a kernel trace
   python tools/closed_loop.py --terrain plane:0.2 [--push 30]                         the same loop on a height field, with a push on the base
+  python tools/closed_loop.py --body [--terrain stairs:0.04] [--push 30]              the same loop with knee and trunk contact and joint limits
 
 The robots are dropped from z = 0.30 onto joint PD at the stand pose (400 ticks of 1 ms), shoved by up to 0.3 m/s in x and y, and handed to
 MPC + WBC: qrgpu_plant_step_batch (include/qrgpu.h) writes the ground-truth mpc_state and fb_state the tick reads, and the tick -- the plain
@@ -15,10 +16,13 @@ gait, a trajectory and a WBC command that hold the origin at height 0.27, warm s
 the loop through qrgpu_plant_step_terrain_batch on that field; on a plane the robots start aligned with the slope (a level robot dropped onto
 a slope of 0.2 tips over backwards).  --push N holds a world-frame force of N newtons along +x on every base during the timed loop.  The
 controller's trajectory and command stay the level ones: what it makes of a pitched ground is reported, not judged.  Without either option
-the run is the flat one.
+the run is the flat one.  --body runs the settle phase and the loop through qrgpu_plant_step_body_batch (on the flat field unless --terrain names
+another): a robot that loses its footing comes to rest on knees and trunk instead of sinking through the ground, and is counted.
 
   ticks_per_s   closed-loop control ticks per second: every robot advances one tick per (plant step + controller tick)
   in_band       share of the robots that end inside the stand band: |z - 0.27| <= 0.01, |x|, |y| <= 0.03, |roll|, |pitch| <= 0.03
+  fallen        (--body) robots that raised PL_TRUNK_CONTACT or PL_KNEE_CONTACT at any tick of the loop, warm-up included
+  nonfinite     robots whose state left the finite numbers
 """
 import argparse
 import importlib.util
@@ -56,6 +60,7 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--terrain", default=None, metavar="KIND[:ARG]", help="run on a height field: flat, plane:0.2, stairs:0.04, gap:0.1, rough:0.01")
     ap.add_argument("--push", type=float, default=0.0, metavar="N", help="world-frame force along +x on every base during the timed loop, newtons")
+    ap.add_argument("--body", action="store_true", help="knee and trunk contact and joint limits: qrgpu_plant_step_body_batch")
     ap.add_argument("--profile", action="store_true", help="the run a profiler traces: fewer ticks, nothing else changed")
     a = ap.parse_args()
     pkg = _load_pkg()
@@ -73,7 +78,7 @@ def main():
              traj=ctx.alloc((12 * h, n)).upload(traj.reshape(12 * h, n)), gait=ctx.alloc((4 * h, n)).upload(np.ones((4 * h, n), np.float32)),
              wcmd=ctx.alloc((67, n)).upload(wcmd), prev=ctx.alloc((3, n)).zero(), force=ctx.alloc((12, n)),
              tick_status=ctx.alloc((n,), np.int32), plant_status=ctx.alloc((n,), np.int32), flags=ctx.alloc((2, n), np.int32))
-    on_field = a.terrain is not None or a.push != 0.0
+    on_field = a.terrain is not None or a.push != 0.0 or a.body
     if on_field:
         kind, _, arg = (a.terrain or "flat").partition(":")
         grid, field = pkg.terrain.make(kind, arg or None)
@@ -85,9 +90,15 @@ def main():
         d["height"] = ctx.alloc((1, grid.ny, grid.nx)).upload(pkg.terrain.stack([field]))
         d["push"] = ctx.alloc((6, n)).zero()
         d["tout"] = ctx.alloc((pkg.qrgpu.TERRAIN_OUT_ROWS, n))
+    if a.body:
+        ctx.plant_body_setup(0, pkg.plant_body_desc("a1"))
+        d["bout"] = ctx.alloc((pkg.qrgpu.BODY_OUT_ROWS, n))
+        d["status_log"] = ctx.alloc((ticks + 20, n), np.int32).zero()        # every tick's plant status: read once, after the loop
 
     def plant(par, **out):
-        if on_field:
+        if a.body:
+            ctx.plant_step_body_batch(n, par, tdesc, d["height"], d["fb"], d["cmd"], base_push=d["push"], terrain_out=d["tout"], body_out=d["bout"], **out)
+        elif on_field:
             ctx.plant_step_terrain_batch(n, par, tdesc, d["height"], d["fb"], d["cmd"], base_push=d["push"], terrain_out=d["tout"], **out)
         else:
             ctx.plant_step_batch(n, par, d["fb"], d["cmd"], **out)
@@ -107,9 +118,12 @@ def main():
     params = pkg.plant_params(dt=0.002, substeps=a.substeps)
     tau = d["cmd"].row(48)
 
+    done = [0]
+
     def loop(k):
         for _ in range(k):
-            plant(params, plant_out=d["out"], mpc_state=d["mpc"], status=d["plant_status"])
+            plant(params, plant_out=d["out"], mpc_state=d["mpc"], status=d["status_log"].row(done[0]) if a.body else d["plant_status"])
+            done[0] += 1
             ctx.tick_batch(n, d["mpc"], d["traj"], d["gait"], d["fb"], d["wcmd"], d["prev"], d["force"], tau, d["tick_status"])
 
     loop(20)                                                          # warm-up: the first launches, the scheduler's history
@@ -121,7 +135,9 @@ def main():
     fb = d["fb"].download()
     rp = _rpy(fb[0:4].T)
     ok = (np.abs(fb[6] - HEIGHT) <= 0.01) & (np.abs(fb[4:6]).max(0) <= 0.03) & (np.abs(rp).max(1) <= 0.03)
-    tick_flags = pkg.status_flags(d["tick_status"].download()); plant_flags = d["plant_status"].download()
+    tick_flags = pkg.status_flags(d["tick_status"].download())
+    log = d["status_log"].download() if a.body else None
+    plant_flags = log[-1] if a.body else d["plant_status"].download()
     res = dict(metric="closed_loop_ticks_per_s", value=ticks / sec, robot_ticks_per_s=n * ticks / sec, ms_per_tick=1e3 * sec / ticks, robots=n, ticks=ticks,
                substeps=a.substeps, in_band=float(ok.mean()), last_tick_flagged=int(((tick_flags != 0) | (plant_flags != 0)).sum()), profile=bool(a.profile))
     if on_field:      # what the controllers made of it: reported, not judged
@@ -131,6 +147,11 @@ def main():
         res.update(terrain=a.terrain or "flat", push=a.push, nonfinite=int((~fin).sum()), pitch_mean=m(rp[:, 1]), z_mean=m(fb[6]), x_mean=m(fb[4]),
                    feet_in_contact=m(out[24:28].mean(0)), upright=float((fin & (np.nan_to_num(np.abs(rp).max(1), nan=9.0) < 0.5)).mean()),
                    plant_flags=int(np.bitwise_or.reduce(plant_flags)))
+    if a.body:
+        q = pkg.qrgpu
+        seen = np.bitwise_or.reduce(log, axis=0)
+        res.update(body=True, fallen=int(((seen & (q.PL_TRUNK_CONTACT | q.PL_KNEE_CONTACT)) != 0).sum()), at_a_stop=int(((seen & q.PL_JOINT_LIMIT) != 0).sum()),
+                   fallen_at_end=int(((plant_flags & (q.PL_TRUNK_CONTACT | q.PL_KNEE_CONTACT)) != 0).sum()))
     print(json.dumps(res))
     ctx.close()
 
