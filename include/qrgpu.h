@@ -377,11 +377,19 @@ int qrgpu_ground_update_batch(qrgpu_ctx *ctx, int n, int reset, const float *d_g
 
 /* Open-loop gait generator (qrOpenLoopGaitGenerator::Update + Schedule, QS/gait/qr_openloop_gait_generator.cpp:126-249) of n robots for
  * one control tick.  d_contact [4][n]: robot->GetFootContact().  d_gait_state [QRGPU_GAIT_STATE_FLOATS][n] is the generators' memory;
- * reset != 0 applies Reset(0) before the update.  d_gait_out [24][n] (may be NULL): phaseInFullCycle[4], normalizedPhase[4],
+ * reset: 0 = carry on; QRGPU_GAIT_RESET_CONSTRUCT (1) = a generator as constructed followed by Reset(0): the state array's earlier content is not
+ * read (the first call on a state array); QRGPU_GAIT_RESET_LIVE (2) = Reset(0) on the RUNNING generator before the update, which in the reference
+ * (QI/gait/qr_gait.h:76-87) rewrites resetTime, lastTime, normalizedPhase, the four leg-state vectors and contactStartPhase and leaves gaitCycle,
+ * cumDt, firstSwing, firstStance, swingTimeRemaining and phaseInFullCycle as they were -- it READS the state array, so it must never be the
+ * first call on one.  NOTE: the numbers are the other way round from qrgpu_walk_gait_update_batch and qrgpu_swing_update_batch (2 = as
+ * constructed, 1 = Reset()): 1 keeps the meaning this entry point's "reset != 0" always had; use the names.  Any other value: QRGPU_ERR_BAD_ARG.
+ * d_gait_out [24][n] (may be NULL): phaseInFullCycle[4], normalizedPhase[4],
  * desiredLegState[4], legState[4], curLegState[4], swingTimeRemaining[4].  d_fe_in (may be NULL): the front-end's input array, whose rows
  * 42-61 (phaseInFullCycle, dutyFactor, normalizedPhase, desiredLegState, legState) are written.  Legs with duty factor 0
  * (USERDEFINED_SWING) are not supported. */
 #define QRGPU_GAIT_STATE_FLOATS 52
+#define QRGPU_GAIT_RESET_CONSTRUCT 1
+#define QRGPU_GAIT_RESET_LIVE 2
 typedef struct {
     float stance_duration[4], duty_factor[4], initial_leg_phase[4];   /* openloop_gait_generator.yaml: 0.5, 0.6, (0.5, 0, 0, 0.5) for advanced_trot */
     int initial_leg_state[4];                                          /* LegState: SWING 0, STANCE 1 */

@@ -374,11 +374,15 @@ def swing_velocity(geom3, hip_offset12, desc20, in53, out48_prev=None):
     return out
 
 
-def gait_run(cfg19, time, contact, stop=None):
-    """Open-loop gait generator of one robot from Reset(0): time [T], contact [T][4] -> out [T][24]
-    (phaseInFullCycle, normalizedPhase, desiredLegState, legState, curLegState, swingTimeRemaining)."""
+def gait_run(cfg19, time, contact, stop=None, reset=None, want_state=False):
+    """Open-loop gait generator of one robot as constructed + Reset(0): time [T], contact [T][4] -> out [T][24]
+    (phaseInFullCycle, normalizedPhase, desiredLegState, legState, curLegState, swingTimeRemaining).  reset [T]: a non-zero entry applies
+    Reset(0) to the running generator before that tick.  want_state: also rows 0-47 of the kernel's gait_state after each tick, [T][48]."""
     t = np.ascontiguousarray(time, _f); c = np.ascontiguousarray(contact, _f)
     out = np.zeros((t.shape[0], 24), _f)
     st = np.ascontiguousarray(stop, np.int32) if stop is not None else None
-    lib().qro_gait_run(_fp(np.ascontiguousarray(cfg19, _f)), t.shape[0], _fp(t), _fp(c), _ip(st) if st is not None else None, _fp(out))
-    return out
+    rs = np.ascontiguousarray(reset, np.int32) if reset is not None else None
+    state = np.zeros((t.shape[0], 48), _f) if want_state else None
+    lib().qro_gait_run_reset(_fp(np.ascontiguousarray(cfg19, _f)), t.shape[0], _fp(t), _fp(c), _ip(st) if st is not None else None,
+                             _ip(rs) if rs is not None else None, _fp(out), _fp(state) if want_state else None)
+    return (out, state) if want_state else out

@@ -275,7 +275,7 @@ struct GaitState {
     int first_swing[4] = {0, 0, 0, 0}, first_stance[4] = {0, 0, 0, 0};
     float phase[4] = {0, 0, 0, 0}, nphase[4] = {0, 0, 0, 0}, contact_start_phase[4] = {0, 0, 0, 0}, swing_remaining[4] = {0, 0, 0, 0};
 };
-void gait_reset(const GaitConfig &c, GaitState &s);
+void gait_reset(const GaitConfig &c, GaitState &s, bool live = false);
 void gait_update(const GaitConfig &c, float currentTime, const float contact[4], bool stop, GaitState &s, float out[24]);
 
 // Swing-leg targets, ADVANCED_TROT on horizontal terrain (second part).  qr_oracle_swing.cpp

@@ -9,10 +9,14 @@
 
 namespace qro {
 
-void gait_reset(const GaitConfig &c, GaitState &s)
+// live = false: a generator as constructed (the members' initialisers, QI/gait/qr_gait.h:263-294) followed by Reset(0).  live = true: Reset(0)
+// on a running generator, which writes resetTime, lastTime, normalizedPhase, the four leg-state vectors and contactStartPhase and nothing
+// else: gaitCycle, cumDt, firstSwing, firstStance, swingTimeRemaining and phaseInFullCycle survive it.
+void gait_reset(const GaitConfig &c, GaitState &s, bool live)
 {
-    s = GaitState();
-    for (int l = 0; l < 4; ++l) { s.cur[l] = s.last[l] = s.leg[l] = s.desired[l] = c.initial_leg_state[l]; }
+    if (!live) s = GaitState();
+    s.reset_time = 0; s.last_time = 0;
+    for (int l = 0; l < 4; ++l) { s.cur[l] = s.last[l] = s.leg[l] = s.desired[l] = c.initial_leg_state[l]; s.nphase[l] = 0; s.contact_start_phase[l] = 0; }
 }
 
 // contact[4]: robot->GetFootContact(); stop: robot->stop.  out[24]: phaseInFullCycle, normalizedPhase, desiredLegState, legState,
@@ -66,12 +70,36 @@ void gait_update(const GaitConfig &c, float currentTime, const float contact[4],
 
 }  // namespace qro
 
-extern "C" void qro_gait_run(const float *cfg19, int nticks, const float *time, const float *contact /*[nticks][4]*/, const int *stop, float *out /*[nticks][24]*/)
+// reset (may be null): a non-zero entry applies Reset(0) to the running generator before that tick's update.  state (may be null) [nticks][48]:
+// rows 0-47 of the kernel's gait_state after each tick.
+static void gait_run(const float *cfg19, int nticks, const float *time, const float *contact, const int *stop, const int *reset, float *out, float *state)
 {
     qro::GaitConfig c;
     for (int l = 0; l < 4; ++l) { c.stance_duration[l] = cfg19[l]; c.duty_factor[l] = cfg19[4 + l]; c.initial_leg_phase[l] = cfg19[8 + l]; c.initial_leg_state[l] = (int)cfg19[12 + l]; }
     c.contact_detection_phase_threshold = cfg19[16]; c.wait_time = cfg19[17]; c.advanced_trot = cfg19[18] != 0.f;
     qro::GaitState s;
-    qro::gait_reset(c, s);
-    for (int k = 0; k < nticks; ++k) qro::gait_update(c, time[k], contact + 4 * k, stop ? stop[k] != 0 : false, s, out + 24 * k);
+    qro::gait_reset(c, s, false);
+    for (int k = 0; k < nticks; ++k) {
+        if (reset && reset[k]) qro::gait_reset(c, s, true);
+        qro::gait_update(c, time[k], contact + 4 * k, stop ? stop[k] != 0 : false, s, out + 24 * k);
+        if (state) {
+            float *o = state + 48 * k;
+            o[0] = s.reset_time; o[1] = s.last_time; o[2] = s.cum_dt; o[3] = s.gait_cycle;
+            for (int l = 0; l < 4; ++l) {
+                o[4 + l] = (float)s.cur[l]; o[8 + l] = (float)s.last[l]; o[12 + l] = (float)s.desired[l]; o[16 + l] = (float)s.leg[l]; o[20 + l] = (float)s.allow[l];
+                o[24 + l] = (float)s.first_swing[l]; o[28 + l] = (float)s.first_stance[l]; o[32 + l] = s.phase[l]; o[36 + l] = s.nphase[l];
+                o[40 + l] = s.contact_start_phase[l]; o[44 + l] = s.swing_remaining[l];
+            }
+        }
+    }
+}
+
+extern "C" void qro_gait_run(const float *cfg19, int nticks, const float *time, const float *contact /*[nticks][4]*/, const int *stop, float *out /*[nticks][24]*/)
+{
+    gait_run(cfg19, nticks, time, contact, stop, nullptr, out, nullptr);
+}
+
+extern "C" void qro_gait_run_reset(const float *cfg19, int nticks, const float *time, const float *contact, const int *stop, const int *reset, float *out, float *state)
+{
+    gait_run(cfg19, nticks, time, contact, stop, reset, out, state);
 }

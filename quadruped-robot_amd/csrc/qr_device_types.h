@@ -236,7 +236,7 @@ struct WbcPipe {
     // ... and there is NO second pass: a thousand (empty) workgroups dispatched one freed slot at a time on a machine that is never empty held the
     // tick's join back by 100 us.  The trailing MPC list launch -- half-CU workgroups in this mode, so a waiting WBC workgroup can never keep it
     // from starting -- raises the flag of a robot it has re-solved with bit 0 clear, and the robot's workgroup here waits on through the
-    // "on the list pass" value for that (bounded by wait_ticks, flagged).
+    // "on the list pass" value for that (bounded by the longer of wait_ticks and flag_ticks -- it is a wait for this tick's forces -- and flagged).
     int wait_list;
     long long flag_ticks;       // bound of the wait for the robot's forces (100 MHz clock; 4 ms, QRGPU_PIPE_WAIT_US for the tests)
     // Large batches, LABORATORY (QRGPU_WBC_CHUNKS; measured slower, LAB_NOTES A.7): the WBC launch is cut into launches of 1024 workgroups, each behind a gate of its own that

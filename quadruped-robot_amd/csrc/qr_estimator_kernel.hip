@@ -410,8 +410,9 @@ __global__ void __launch_bounds__(64) qr_swing_kernel(int n, qrgpu_estimator_des
 // Open-loop gait generator, one thread per robot: qrOpenLoopGaitGenerator::Update + Schedule
 // (quadruped/src/gait/qr_openloop_gait_generator.cpp:126-207, 210-249; legs with a non-zero duty factor).  State [52][n] floats:
 // resetTime, lastTime, cumDt, gaitCycle, then per leg cur, last, desired, legState, allow, firstSwing, firstStance, phaseInFullCycle,
-// normalizedPhase, contactStartPhase, swingTimeRemaining, (spare); `fresh` != 0 applies Reset(0) first.  Plain float arithmetic and
-// fmodf (exact): bit-identical to the CPU restatement.
+// normalizedPhase, contactStartPhase, swingTimeRemaining, (spare); `fresh` = 2 applies Reset(0) to the running generator first, any other
+// non-zero value starts from a generator as constructed (the state's content is not read).  Plain float arithmetic and fmodf (exact):
+// bit-identical to the CPU restatement.
 __global__ void __launch_bounds__(64) qr_gait_kernel(int n, qrgpu_gait_desc D, float currentTime, int stop, int fresh, const float *__restrict__ g_contact,
                                                      float *__restrict__ st, float *__restrict__ g_out, float *__restrict__ g_fe)
 {
@@ -423,7 +424,14 @@ __global__ void __launch_bounds__(64) qr_gait_kernel(int n, qrgpu_gait_desc D, f
     float reset_time, last_time, cum_dt, gait_cycle;
     int cur[4], last[4], desired[4], leg[4], allow[4], fsw[4], fst[4];
     float phase[4], nphase[4], csp[4], srem[4];
-    if (fresh) {
+    if (fresh == 2) {                // Reset(0) on a running generator (qr_gait.h:76-87): the members it does not write survive
+        reset_time = last_time = 0.f; cum_dt = ST(2); gait_cycle = ST(3);
+#pragma unroll
+        for (int l = 0; l < 4; ++l) {
+            cur[l] = last[l] = desired[l] = leg[l] = D.initial_leg_state[l]; allow[l] = (int)ST(20 + l); nphase[l] = csp[l] = 0.f;
+            fsw[l] = (int)ST(24 + l); fst[l] = (int)ST(28 + l); phase[l] = ST(32 + l); srem[l] = ST(44 + l);
+        }
+    } else if (fresh) {              // as constructed (the members' initialisers, qr_gait.h:263-294), then Reset(0)
         reset_time = last_time = cum_dt = gait_cycle = 0.f;
 #pragma unroll
         for (int l = 0; l < 4; ++l) { cur[l] = last[l] = desired[l] = leg[l] = D.initial_leg_state[l]; allow[l] = 1; fsw[l] = fst[l] = 0; phase[l] = nphase[l] = csp[l] = srem[l] = 0.f; }

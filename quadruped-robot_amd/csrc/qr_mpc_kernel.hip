@@ -1865,7 +1865,11 @@ void qr_mpc_kernel(MpcLaunch P, MpcIO io)
                                     if (taken < avail && taken < P.n) continue;
                                     break;                                     // the main pass is through and the list is empty
                                 }
-                                if (wall_clock64() - t0 > 5 * P.xtick_wait) break;          // (100 ms: a main pass that never ends)
+                                // (a main pass that never ends: five times the bound of the predecessor waits, as the main pass may spend that bound on
+                                //  them, and never less than 100 ms of the 100 MHz clock, its value at the default 20 ms.  This is a wait for THIS tick's main
+                                //  pass: under the give-up tests' 50 us bound the lingering workgroups left 250 us after they started -- before the hand-overs
+                                //  of an unchained tick on a machine that runs the main pass slower)
+                                { const long long lim = 5 * P.xtick_wait; if (wall_clock64() - t0 > (lim > 10000000ll ? lim : 10000000ll)) break; }
                                 __builtin_amdgcn_s_sleep(32);
                             }
                             *sNext = got;

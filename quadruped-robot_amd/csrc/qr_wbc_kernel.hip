@@ -1020,10 +1020,13 @@ void qr_wbc_kernel(int n, const WbcConst *__restrict__ types, const int *__restr
         // forces with loads of the same kind (they bypass this CU's L1, which may hold last tick's line).
         unsigned v = 0;
         const long long t0 = wall_clock64();
+        // (the wait through the list pass is a wait for THIS tick's forces, not for the predecessor: never shorter than flag_ticks, so that a bound
+        //  on the predecessor waits cut down for the give-up tests does not make the list robots of an unchained tick give up on a slow machine)
+        const long long list_ticks = pipe.wait_ticks > pipe.flag_ticks ? pipe.wait_ticks : pipe.flag_ticks;
         for (;;) {
             v = __hip_atomic_load(pipe.flag + rid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if ((v >> 1) == pipe.epoch && !(pipe.wait_list && (v & 1u))) break;
-            if (wall_clock64() - t0 > (((v >> 1) == pipe.epoch && pipe.wait_list) ? pipe.wait_ticks : pipe.flag_ticks)) {
+            if (wall_clock64() - t0 > (((v >> 1) == pipe.epoch && pipe.wait_list) ? list_ticks : pipe.flag_ticks)) {
                 // Never silent, also when the solve is still running and will store its status word OVER the one this workgroup writes: leave
                 // "gave up in this epoch" in the flag word itself (bit 31; epochs stay below 2^30) -- the solve raises the flag with an exchange
                 // and, finding that value, adds QRGPU_ST_PIPE_TIMEOUT to the status word it has just stored (qr_mpc_kernel.hip).

@@ -56,6 +56,7 @@ int qrgpu_gait_update_batch(qrgpu_ctx *c, int n, const qrgpu_gait_desc *desc, fl
                             float *d_gait_state, float *d_gait_out, float *d_fe_in)
 {
     if (!batch_ok(c, n) || !desc || !d_contact || !d_gait_state) return QRGPU_ERR_BAD_ARG;
+    if (reset != 0 && reset != QRGPU_GAIT_RESET_CONSTRUCT && reset != QRGPU_GAIT_RESET_LIVE) return QRGPU_ERR_BAD_ARG;
     for (int l = 0; l < 4; ++l) if (!(desc->duty_factor[l] > 0.001f) || !(desc->stance_duration[l] > 0.f)) return QRGPU_ERR_BAD_ARG;   // USERDEFINED_SWING legs are not built
     return launch_stage(c, qr_gait_kernel, per_robot(n), dim3(64), n, *desc, current_time, robot_stop, reset, d_contact, d_gait_state, d_gait_out, d_fe_in);
 }

@@ -25,6 +25,7 @@ ST_FLAG_MASK, ST_BAD_TYPE = 0xff0000ff, 0x01000000
 
 ST_MPC_MAXITER, ST_MPC_INFEAS, ST_MPC_OVERFLOW, ST_MPC_NOTSPD = 0x1, 0x2, 0x4, 0x8
 ST_WBC_MAXITER, ST_WBC_INFEAS = 0x10, 0x20
+GAIT_RESET_CONSTRUCT, GAIT_RESET_LIVE = 1, 2          # qrgpu_gait_update_batch's reset (include/qrgpu.h)
 FB_DEBUG_FLOATS = 324 + 18 + 18 + 216 + 12 + 12 + 12
 
 
@@ -617,14 +618,16 @@ class Context:
         self._chk(self._lib.qrgpu_estimator_update_batch(self._h, n, C.byref(d), _dp(est_in), _dp(tick), _dp(est_state), _dp(est_out)))
 
     def gait_update_batch(self, n, cfg19, current_time, contact, gait_state, gait_out=None, fe_in=None, stop=False, reset=False):
-        """qrOpenLoopGaitGenerator::Update of n robots (qr_openloop_gait_generator.cpp:126-249).  cfg19 = workload.gait_cfg()."""
+        """qrOpenLoopGaitGenerator::Update of n robots (qr_openloop_gait_generator.cpp:126-249).  cfg19 = workload.gait_cfg().
+        reset: True / GAIT_RESET_CONSTRUCT (1) = start from a generator as constructed, GAIT_RESET_LIVE (2) = Reset(0) on the running generator --
+        the other way round from walk_gait_update_batch / swing_update_batch (include/qrgpu.h); any other value is refused."""
         d = gait_desc_struct()
         cfg19 = np.asarray(cfg19, np.float32)
         for l in range(4):
             d.stance_duration[l] = float(cfg19[l]); d.duty_factor[l] = float(cfg19[4 + l]); d.initial_leg_phase[l] = float(cfg19[8 + l])
             d.initial_leg_state[l] = int(cfg19[12 + l])
         d.contact_detection_phase_threshold = float(cfg19[16]); d.wait_time = float(cfg19[17]); d.advanced_trot = int(cfg19[18])
-        self._chk(self._lib.qrgpu_gait_update_batch(self._h, n, C.byref(d), float(current_time), int(bool(stop)), int(bool(reset)), _dp(contact),
+        self._chk(self._lib.qrgpu_gait_update_batch(self._h, n, C.byref(d), float(current_time), int(bool(stop)), int(reset), _dp(contact),
                                                     _dp(gait_state), _dp(gait_out), _dp(fe_in)))
 
     def walk_gait_update_batch(self, n, cfg26, current_time, contact, walk_state, walk_out=None, ratio=None, vmc_in=None, stop=False, reset=0):

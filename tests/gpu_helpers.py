@@ -153,3 +153,28 @@ def setup_a1(ctx, pkg, horizon=10):
 def tau_tol(tau_ref, rel=1e-4):
     """north_star tolerance: 1e-4 * max(1, |tau_cpu|) per motor."""
     return rel * np.maximum(1.0, np.abs(tau_ref))
+
+
+def ground_sequences(n, T, seed):
+    """Inputs of qrgpu_ground_update_batch over T ticks, [T][n][23] (the generator of tests/test_gpu_ground.py): trot-like contact toggling, feet on
+    a random plane, a slowly turning base."""
+    rng = np.random.default_rng(seed)
+    hips = np.array([(0.18, -0.13), (0.18, 0.13), (-0.18, -0.13), (-0.18, 0.13)])
+    x = np.zeros((T, n, 23), np.float32)
+    # contacts: trot-like toggling with random phase, so that "all four down, one newly" happens at irregular times
+    ph = rng.uniform(0, 1, (n, 4)); per = rng.integers(6, 14, (n, 1))
+    for t in range(T):
+        x[t, :, 0:4] = (np.fmod(ph + t / per, 1.0) < 0.8)
+    plane = np.stack([rng.uniform(-0.35, -0.2, n), rng.uniform(-0.3, 0.3, n), rng.uniform(-0.3, 0.3, n)], 1)
+    for l in range(4):
+        fx = hips[l, 0] + rng.uniform(-0.06, 0.06, (T, n)); fy = hips[l, 1] + rng.uniform(-0.04, 0.04, (T, n))
+        x[:, :, 4 + 3 * l] = fx; x[:, :, 5 + 3 * l] = fy
+        x[:, :, 6 + 3 * l] = plane[:, 0] + plane[:, 1] * fx + plane[:, 2] * fy + rng.uniform(-0.01, 0.01, (T, n))
+    x[:, :, 16:19] = rng.uniform(-1, 1, (T, n, 3))
+    # orientation: a slowly turning base with some roll and pitch (yaw crosses +-pi for some robots: the reference filters the angles as they are)
+    yaw = rng.uniform(-3.1, 3.1, (1, n)) + np.cumsum(rng.uniform(-0.05, 0.08, (T, n)), 0)
+    roll = rng.uniform(-0.3, 0.3, (T, n)); pitch = rng.uniform(-0.3, 0.3, (T, n))
+    cr, sr, cp, sp, cy, sy = np.cos(roll / 2), np.sin(roll / 2), np.cos(pitch / 2), np.sin(pitch / 2), np.cos(yaw / 2), np.sin(yaw / 2)
+    x[:, :, 19] = cr * cp * cy + sr * sp * sy; x[:, :, 20] = sr * cp * cy - cr * sp * sy
+    x[:, :, 21] = cr * sp * cy + sr * cp * sy; x[:, :, 22] = cr * cp * sy - sr * sp * cy
+    return x

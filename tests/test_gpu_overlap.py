@@ -215,6 +215,18 @@ def test_per_robot_waits_that_give_up_at_h16():
     assert "TIMED_OUT" in r.stdout
 
 
+def test_give_up_bound_does_not_reach_the_ticks_own_waits_at_h16():
+    """The same sequence with the bound of the waits for the PREDECESSOR at 2 us instead of 50: chained ticks give up on every robot as before,
+    and the unchained first tick carries no flag and finite torques.  The waits for a tick's own work -- the lingering list workgroups' wait
+    for the main pass's hand-overs, the WBC workgroups' wait through the list pass -- are not derived from that bound alone (when they were,
+    2 us x 5 ended the lingering long before the first hand-over on any machine: the tenth of the batch that the main pass hands on was solved
+    by nobody in the first tick; at 50 us that happened on machines that run the main pass slower)."""
+    env = dict(os.environ, QRGPU_OV_WAIT_US="2", QRGPU_OV_FAULT="1", GPU_MAX_HW_QUEUES="8", QR_TEST_H="16")
+    r = subprocess.run([sys.executable, "-c", _GIVE_UP % dict(root=ROOT)], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert "TIMED_OUT" in r.stdout
+
+
 _SHARED_QUEUE = r"""
 import os, sys
 sys.path.insert(0, os.path.join(%(root)r, "tests"))

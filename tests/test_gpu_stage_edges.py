@@ -1,0 +1,281 @@
+"""Batch edges, guard rows and error returns of the per-robot stage entry points: qrgpu_estimator_update_batch, qrgpu_pack_state_batch,
+qrgpu_ground_update_batch, qrgpu_gait_update_batch, qrgpu_footholds_batch, qrgpu_swing_targets_batch (one thread per robot, workgroups of 64).
+
+  * batch edges: n = 1, 63, 64, 65.  A robot's outputs and memory are the same bits whether it runs in a batch of 65, in the first 63 or 64
+    of it, alone (n = 1), or in the reversed batch.
+  * guard rows: every output and state array is allocated one row longer than the call needs; that row is poisoned and comes back untouched.
+  * error returns: QRGPU_ERR_BAD_ARG, nothing launched, outputs untouched."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import gait_ref as GR
+import gpu_helpers as G
+import stage_ref as SR
+
+pytestmark = pytest.mark.gpu
+
+N = 65
+P32 = np.float32(-12345.5)
+P64 = np.float64(-98765.25)
+BAD_ARG = 2
+
+
+class Guarded:
+    """A device array [rows + 1][n] whose last row is a poisoned guard; `fill` initialises the rows the call owns (None: poison as well)."""
+
+    def __init__(self, ctx, rows, n, dtype=np.float32, fill=None):
+        self.rows, self.n, self.poison = rows, n, (P64 if np.dtype(dtype) == np.float64 else P32)
+        host = np.full((rows + 1, n), self.poison if fill is None else fill, dtype)
+        host[rows] = self.poison
+        self.d = ctx.alloc((rows + 1, n), dtype).upload(host)
+
+    def data_ptr(self):
+        return self.d.data_ptr()
+
+    def take(self):
+        """-> [n][rows] (AoS) after checking the guard row; frees the array."""
+        h = self.d.download()
+        self.d.free()
+        assert np.all(h[self.rows] == self.poison), "guard row overwritten"
+        return np.ascontiguousarray(h[:self.rows].T)
+
+    def untouched(self):
+        h = self.d.download()
+        self.d.free()
+        return bool(np.all(h == self.poison))
+
+
+def same_bits(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
+
+
+# ----------------------------------------------------------------------------- the six stages: inputs [T][N][k], a runner over a subset of robots
+def _est_cfg(pkg):
+    return pkg.workload.estimator_cfg("a1", window=8)
+
+
+def _inputs(pkg):
+    W = pkg.workload
+    x, stamp = SR.wide_sensor_streams(N, 12, 91)
+    gt = (np.arange(40) * 0.02).astype(np.float32)                      # 20 ms ticks: touch-downs, holds and early contacts within 40 ticks
+    gcfg = W.gait_cfg(stance_duration=0.3, duty_factor=0.5, initial_leg_state=(0, 1, 1, 0), wait_time=0.06)
+    rng = np.random.default_rng(92)
+    return dict(
+        estimator=dict(x=x, stamp=stamp),
+        pack=dict(x=x[:1], est=rng.uniform(-2, 2, (1, N, 42)).astype(np.float32), rpy=rng.uniform(-3, 3, (1, N, 3)).astype(np.float32)),
+        ground=dict(x=G.ground_sequences(N, 16, seed=93)),
+        gait=dict(c=GR.contacts(N, 40, gcfg, gt, 94), t=gt, cfg=gcfg),
+        foothold=dict(x=W.make_foothold_batch(N, seed=95)[None]),
+        swing=dict(x=W.make_swing_batch(N, seed=96)[None]))
+
+
+def run_estimator(ctx, pkg, inp, idx):
+    n = len(idx)
+    cfg = _est_cfg(pkg)
+    S = ctx.estimator_state_doubles(8)
+    st = Guarded(ctx, S, n, np.float64, fill=0.0); out = Guarded(ctx, 42, n)
+    d_in = ctx.alloc((54, n)); d_tick = ctx.alloc((n,), np.uint32)
+    for k in range(inp["x"].shape[0]):
+        d_in.upload(pkg.to_soa(inp["x"][k][idx])); d_tick.upload(inp["stamp"][k][idx])
+        ctx.estimator_update_batch(n, cfg, d_in, d_tick, st, out)
+    ctx.sync()
+    d_in.free(); d_tick.free()
+    return dict(out=out.take(), state=st.take())
+
+
+def run_pack(ctx, pkg, inp, idx):
+    n = len(idx)
+    d_in = ctx.alloc((54, n)).upload(pkg.to_soa(inp["x"][0][idx])); d_est = ctx.alloc((42, n)).upload(pkg.to_soa(inp["est"][0][idx]))
+    d_rpy = ctx.alloc((3, n)).upload(pkg.to_soa(inp["rpy"][0][idx]))
+    mpc = Guarded(ctx, 28, n); fb = Guarded(ctx, 37, n)
+    ctx.pack_state_batch(n, np.array([-0.008, 0.005, 0.0], np.float32), d_in, d_est, d_rpy, mpc, fb)
+    ctx.sync()
+    for v in (d_in, d_est, d_rpy):
+        v.free()
+    return dict(mpc=mpc.take(), fb=fb.take())
+
+
+def run_ground(ctx, pkg, inp, idx):
+    n = len(idx)
+    st = Guarded(ctx, 13, n, np.float64); out = Guarded(ctx, 32, n); est = Guarded(ctx, 54, n)
+    d_in = ctx.alloc((23, n))
+    for k in range(inp["x"].shape[0]):
+        d_in.upload(pkg.to_soa(inp["x"][k][idx]))
+        ctx.ground_update_batch(n, d_in, st, out, est, reset=(k == 0))
+    ctx.sync()
+    d_in.free()
+    r = dict(out=out.take(), state=st.take(), est=est.take())
+    assert np.all(r["est"][:, :45] == P32)
+    return r
+
+
+def run_gait(ctx, pkg, inp, idx):
+    n = len(idx)
+    st = Guarded(ctx, 52, n); out = Guarded(ctx, 24, n); fe = Guarded(ctx, 64, n)
+    d_c = ctx.alloc((4, n))
+    for k in range(inp["t"].size):
+        d_c.upload(pkg.to_soa(inp["c"][k][idx]))
+        ctx.gait_update_batch(n, inp["cfg"], float(inp["t"][k]), d_c, st, out, fe, reset=(k == 0))
+    ctx.sync()
+    d_c.free()
+    r = dict(out=out.take(), state=st.take(), fe=fe.take())
+    assert np.all(r["fe"][:, :42] == P32) and np.all(r["fe"][:, 62:] == P32) and np.all(r["state"][:, 48:] == P32)
+    return r
+
+
+def run_foothold(ctx, pkg, inp, idx):
+    n = len(idx)
+    d_in = ctx.alloc((46, n)).upload(pkg.to_soa(inp["x"][0][idx]))
+    sw = Guarded(ctx, 58, n)
+    ctx.footholds_batch(n, pkg.workload.foothold_cfg("a1"), d_in, sw)
+    ctx.sync()
+    d_in.free()
+    r = dict(swing_in=sw.take())
+    assert np.all(r["swing_in"][:, 8:24] == P32) and np.all(r["swing_in"][:, 36:] == P32)
+    return r
+
+
+def run_swing(ctx, pkg, inp, idx):
+    n = len(idx)
+    d_in = ctx.alloc((58, n)).upload(pkg.to_soa(inp["x"][0][idx]))
+    cmd = Guarded(ctx, 67, n); tgt = Guarded(ctx, 12, n); qd = Guarded(ctx, 24, n)
+    ctx.swing_targets_batch(n, _est_cfg(pkg), d_in, cmd, tgt, qd)
+    ctx.sync()
+    d_in.free()
+    r = dict(cmd=cmd.take(), tgt=tgt.take(), qdes=qd.take())
+    assert np.all(r["cmd"][:, :15] == P32) and np.all(r["cmd"][:, 51:] == P32)
+    return r
+
+
+RUNNERS = dict(estimator=run_estimator, pack=run_pack, ground=run_ground, gait=run_gait, foothold=run_foothold, swing=run_swing)
+
+
+@pytest.fixture(scope="module")
+def inputs(pkg):
+    return _inputs(pkg)
+
+
+@pytest.mark.parametrize("stage", sorted(RUNNERS))
+def test_batch_edges_and_guard_rows(gpu_ctx, pkg, inputs, stage):
+    run, inp = RUNNERS[stage], inputs[stage]
+    full = run(gpu_ctx, pkg, inp, np.arange(N))
+    for k, v in full.items():
+        assert (v != (P64 if v.dtype == np.float64 else P32)).any(), (stage, k)                   # the stage wrote something
+    for m in (63, 64):
+        part = run(gpu_ctx, pkg, inp, np.arange(m))
+        for k in full:
+            assert same_bits(part[k], full[k][:m]), (stage, k, m)
+    rev = run(gpu_ctx, pkg, inp, np.arange(N)[::-1])
+    for k in full:
+        assert same_bits(rev[k][::-1], full[k]), (stage, k, "reversed")
+    for j in (0, 31, 63, 64):
+        one = run(gpu_ctx, pkg, inp, np.array([j]))
+        for k in full:
+            assert same_bits(one[k], full[k][j:j + 1]), (stage, k, j)
+    if stage == "gait":
+        assert np.unique(full["state"][:, 0]).size > 3                                            # holds moved the robots' clocks apart
+    if stage == "ground":
+        assert (full["state"][:, 4:7] != 0).any()                                                 # the plane fit fired
+
+
+# ----------------------------------------------------------------------------- error returns
+def _ptr(x):
+    return None if x is None else C.c_void_p(x.data_ptr())
+
+
+def test_error_returns_leave_the_outputs_untouched(gpu_ctx, pkg):
+    from quadruped_robot_amd import qrgpu as Q
+    lib, h, W = gpu_ctx._lib, gpu_ctx._h, pkg.workload
+    n = 8
+    too_many = gpu_ctx.max_batch + 1
+    some = gpu_ctx.alloc((64, n)).upload(np.zeros((64, n), np.float32))                  # stands in for every input array
+    tick = gpu_ctx.alloc((n,), np.uint32).upload(np.ones(n, np.uint32))
+    I, T = _ptr(some), _ptr(tick)
+
+    def bad(rc):
+        assert rc == BAD_ARG, (rc, gpu_ctx.last_error())
+
+    # ---- estimator
+    st = Guarded(gpu_ctx, 96 + 3 * 8, n, np.float64); out = Guarded(gpu_ctx, 42, n)
+    ed = Q._estimator_desc(W.estimator_cfg("a1", window=8))
+    f = lib.qrgpu_estimator_update_batch
+    for nn in (0, too_many, -1):
+        bad(f(h, nn, C.byref(ed), I, T, _ptr(st), _ptr(out)))
+    bad(f(h, n, None, I, T, _ptr(st), _ptr(out)))
+    bad(f(h, n, C.byref(ed), None, T, _ptr(st), _ptr(out)))
+    bad(f(h, n, C.byref(ed), I, None, _ptr(st), _ptr(out)))
+    bad(f(h, n, C.byref(ed), I, T, None, _ptr(out)))
+    bad(f(h, n, C.byref(ed), I, T, _ptr(st), None))
+    for w in (0, 4097, -3):
+        e2 = Q._estimator_desc(W.estimator_cfg("a1", window=8)); e2.window = w
+        bad(f(h, n, C.byref(e2), I, T, _ptr(st), _ptr(out)))
+    assert lib.qrgpu_estimator_state_doubles(0) == 0 and lib.qrgpu_estimator_state_doubles(4096) == 96 + 3 * 4096
+    assert st.untouched() and out.untouched()
+
+    # ---- pack_state
+    mpc = Guarded(gpu_ctx, 28, n); fb = Guarded(gpu_ctx, 37, n)
+    com = np.zeros(3, np.float32); cp = com.ctypes.data_as(C.POINTER(C.c_float))
+    f = lib.qrgpu_pack_state_batch
+    for nn in (0, too_many):
+        bad(f(h, nn, cp, I, I, I, _ptr(mpc), _ptr(fb)))
+    bad(f(h, n, None, I, I, I, _ptr(mpc), _ptr(fb)))
+    bad(f(h, n, cp, None, I, I, _ptr(mpc), _ptr(fb)))
+    bad(f(h, n, cp, I, None, I, _ptr(mpc), _ptr(fb)))
+    bad(f(h, n, cp, I, I, I, None, None))                                              # neither output
+    bad(f(h, n, cp, I, I, None, _ptr(mpc), _ptr(fb)))                                  # d_mpc_state without d_rpy
+    bad(f(h, n, cp, I, I, None, _ptr(mpc), None))
+    assert mpc.untouched() and fb.untouched()
+
+    # ---- ground
+    gst = Guarded(gpu_ctx, 13, n, np.float64); gout = Guarded(gpu_ctx, 32, n); gest = Guarded(gpu_ctx, 54, n)
+    f = lib.qrgpu_ground_update_batch
+    for nn in (0, too_many):
+        bad(f(h, nn, 1, I, _ptr(gst), _ptr(gout), _ptr(gest)))
+    bad(f(h, n, 1, None, _ptr(gst), _ptr(gout), _ptr(gest)))
+    bad(f(h, n, 1, I, None, _ptr(gout), _ptr(gest)))
+    assert gst.untouched() and gout.untouched() and gest.untouched()
+
+    # ---- gait
+    st = Guarded(gpu_ctx, 52, n); out = Guarded(gpu_ctx, 24, n); fe = Guarded(gpu_ctx, 64, n)
+    gd = Q.gait_desc_struct(); lib.qrgpu_gait_desc_default(C.byref(gd))
+    f = lib.qrgpu_gait_update_batch
+    for nn in (0, too_many):
+        bad(f(h, nn, C.byref(gd), 0.0, 0, 1, I, _ptr(st), _ptr(out), _ptr(fe)))
+    bad(f(h, n, None, 0.0, 0, 1, I, _ptr(st), _ptr(out), _ptr(fe)))
+    bad(f(h, n, C.byref(gd), 0.0, 0, 1, None, _ptr(st), _ptr(out), _ptr(fe)))
+    bad(f(h, n, C.byref(gd), 0.0, 0, 1, I, None, _ptr(out), _ptr(fe)))
+    for r in (3, -1, 255):                                                             # reset is 0, QRGPU_GAIT_RESET_CONSTRUCT (1) or QRGPU_GAIT_RESET_LIVE (2)
+        bad(f(h, n, C.byref(gd), 0.0, 0, r, I, _ptr(st), _ptr(out), _ptr(fe)))
+    assert (Q.GAIT_RESET_CONSTRUCT, Q.GAIT_RESET_LIVE) == (1, 2)
+    for leg, duty, stance in ((0, 0.001, 0.5), (3, 0.0, 0.5), (1, -0.2, 0.5), (2, float("nan"), 0.5), (0, 0.6, 0.0), (3, 0.6, -0.1), (1, 0.6, float("nan"))):
+        g2 = Q.gait_desc_struct(); lib.qrgpu_gait_desc_default(C.byref(g2))
+        g2.duty_factor[leg] = duty; g2.stance_duration[leg] = stance
+        bad(f(h, n, C.byref(g2), 0.0, 0, 1, I, _ptr(st), _ptr(out), _ptr(fe)))
+    assert st.untouched() and out.untouched() and fe.untouched()
+
+    # ---- footholds
+    sw = Guarded(gpu_ctx, 58, n)
+    fd = Q.foothold_desc_struct(); lib.qrgpu_foothold_desc_default(C.byref(fd))
+    f = lib.qrgpu_footholds_batch
+    for nn in (0, too_many):
+        bad(f(h, nn, C.byref(fd), I, None, None, _ptr(sw)))
+    bad(f(h, n, None, I, None, None, _ptr(sw)))
+    bad(f(h, n, C.byref(fd), None, None, None, _ptr(sw)))
+    bad(f(h, n, C.byref(fd), I, None, None, None))
+    bad(f(h, n, C.byref(fd), I, I, None, _ptr(sw)))                                     # exactly one of d_gait_state / d_gait_out
+    bad(f(h, n, C.byref(fd), I, None, I, _ptr(sw)))
+    assert sw.untouched()
+
+    # ---- swing targets
+    cmd = Guarded(gpu_ctx, 67, n); tgt = Guarded(gpu_ctx, 12, n); qd = Guarded(gpu_ctx, 24, n)
+    f = lib.qrgpu_swing_targets_batch
+    for nn in (0, too_many):
+        bad(f(h, nn, C.byref(ed), I, _ptr(cmd), _ptr(tgt), _ptr(qd)))
+    bad(f(h, n, None, I, _ptr(cmd), _ptr(tgt), _ptr(qd)))
+    bad(f(h, n, C.byref(ed), None, _ptr(cmd), _ptr(tgt), _ptr(qd)))
+    bad(f(h, n, C.byref(ed), I, None, None, None))                                      # all three outputs NULL
+    assert cmd.untouched() and tgt.untouched() and qd.untouched()
+    some.free(); tick.free()

@@ -59,3 +59,34 @@ def test_swing_velocity_mode_parity(gpu_ctx, pkg, oracle):
         assert np.allclose(g[i, 24:][m[24:]], o[24:][m[24:]], rtol=0, atol=2e-5, equal_nan=True), (i, g[i, 24:36], o[24:36])
     assert written > 20 * n
     d_in.free(); d_out.free()
+
+
+@pytest.mark.parametrize("robot", ["a1", "lite3"])
+def test_joint_targets_against_the_model_on_the_ik_domain(gpu_ctx, pkg, robot):
+    """d_qdes of qrgpu_swing_targets_batch against tests/stage_ref.py: the model's forward kinematics (float64 chain) of the kernel's joint
+    targets lands on the target, |FK64(angles) - p| <= 5e-6 m, for every leg over the wide joint family restricted to |t1 + t2/2| <= 1.4
+    (derivation of the bar: stage_ref.check_ik); two unreachable targets give the current angles where the reference's angle is NaN."""
+    import stage_ref as SR
+    cfg = pkg.workload.estimator_cfg(robot)
+    geom, ho = cfg[:3], cfg[7:19]
+    q = SR.ik_joints(300, 51)
+    xu, cur = SR.unreachable_swing_in(cfg)
+    x = np.concatenate([SR.ik_swing_in(cfg, q), xu])
+    n = x.shape[0]
+    d_in = gpu_ctx.alloc((58, n)).upload(pkg.to_soa(x))
+    d_q = gpu_ctx.alloc((24, n)).upload(np.full((24, n), np.nan, np.float32))
+    gpu_ctx.swing_targets_batch(n, cfg, d_in, None, None, d_q)
+    gpu_ctx.sync()
+    ang = d_q.download().T[:, :12]
+    assert np.all(np.isfinite(ang))
+    SR.check_ik(cfg, x[:-2], ang[:-2])
+    print("gpu against stage_ref  %s IK residual %.3e, angle %.3e" % (robot, np.abs(SR.foot_positions(geom, ho, ang[:-2]).reshape(-1, 12) - x[:-2, 12:24]).max(),
+                                                                       np.abs(ang[:-2] - q).max()))
+    a0, a1 = ang[-2], ang[-1]
+    assert np.array_equal(a0[3:6], cur[3:6])                                            # beyond the leg's reach: all three angles fall back
+    want = SR.leg_ik(geom, ho, xu[1, 15:18], 1)
+    assert np.isnan(want[0]) and np.isnan(want[1])
+    assert np.array_equal(a1[3:5], cur[3:5]) and abs(a1[5] - want[2]) <= 2e-6           # inside the hip cylinder: abad and hip fall back, the knee is solved
+    for a in (a0, a1):
+        assert np.abs(np.delete(a, [3, 4, 5]) - np.delete(np.tile(SR.STAND, 4), [3, 4, 5])).max() <= 2e-5
+    d_in.free(); d_q.free()
