@@ -318,7 +318,14 @@ int qrgpu_set_torque_epilogue(qrgpu_ctx *ctx, int flags);
  * the reference trajectory d_traj only for robots that re-plan this tick (iterationCounter % (round(dt_mpc/dt_ctrl)/2) == 0
  * or < 50; d_mpc_updated[i] = 1, may be NULL), and rows 0-14 and 63-66 of d_wbc_cmd (may be NULL): pBody_des, vBody_des,
  * aBody_des = 0, pBody_RPY_des, vBody_Ori_des, contact_state.  The horizon is the one of qrgpu_mpc_setup.
- * Reference values: dt_ctrl 0.002, dt_mpc 0.06, num_horizon_l = max(2, int(fullCyclePeriod/0.4)) (:43-50). */
+ * Reference values: dt_ctrl 0.002, dt_mpc 0.06, num_horizon_l = max(2, int(fullCyclePeriod/0.4)) (:43-50).
+ * The re-plan period is round(dt_mpc/dt_ctrl)/2 by integer division (25 -> 12).  round(dt_mpc/dt_ctrl) must lie in 2 .. 2^24: below 2 the
+ * reference takes a remainder by zero, so the call returns QRGPU_ERR_BAD_ARG and launches nothing.
+ * iterationCounter is row 7 of d_fe_state, a float row that callers initialise with floats.  A float cannot count past 2^24 (9.3 h at 2 ms),
+ * so a counter that would reach 2^24 is stored as the smallest value >= 50 of its residue class modulo the period: the cadence, which
+ * only asks for counter % period and counter < 50, goes on exactly as the reference's integer counter would.  A caller that initialises the
+ * row gives it a whole number in 0 .. 2^24 (0 after a Reset); the kernel converts it to int, so NaN and values beyond the int range are
+ * undefined. */
 int qrgpu_mpc_frontend_batch(qrgpu_ctx *ctx, int n, int num_horizon_l, float dt_ctrl, float dt_mpc, const float *d_fe_in,
                              float *d_fe_state, float *d_traj, float *d_gait, float *d_wbc_cmd, int *d_mpc_updated);
 

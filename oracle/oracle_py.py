@@ -276,11 +276,13 @@ def tick_batch(mode, cfg, horizon, geom, model, mpc_state, traj, gait, fb_state,
 
 
 def mpc_frontend(horizon, num_horizon_l, in64, st8, dt=0.002, dt_mpc=0.06):
-    """-> traj[12h] (or None when this tick does not re-plan), gait[4h], wbc15, contact4, new state, updated flag"""
+    """-> traj[12h] (or None when this tick does not re-plan), gait[4h], wbc15, contact4, new state, updated flag.
+    ValueError unless 2 <= round(dt_mpc / dt) <= 2**24 (the front-end's QRGPU_ERR_BAD_ARG)."""
     i = np.ascontiguousarray(in64, _f); st = np.ascontiguousarray(st8, _f).copy()
     traj = np.full(12 * horizon, np.nan, _f); gait = np.zeros(4 * horizon, _f); wbc = np.zeros(15, _f); ct = np.zeros(4, _f)
     upd = C.c_int(0)
-    lib().qro_mpc_frontend(int(horizon), int(num_horizon_l), C.c_float(dt), C.c_float(dt_mpc), _fp(i), _fp(st), _fp(traj), _fp(gait), _fp(wbc), _fp(ct), C.byref(upd))
+    if lib().qro_mpc_frontend(int(horizon), int(num_horizon_l), C.c_float(dt), C.c_float(dt_mpc), _fp(i), _fp(st), _fp(traj), _fp(gait), _fp(wbc), _fp(ct), C.byref(upd)):
+        raise ValueError("mpc_frontend: round(dt_mpc / dt) outside 2 .. 2**24")
     return dict(traj=traj, gait=gait, wbc15=wbc, contact=ct, state=st, updated=upd.value)
 
 
@@ -344,15 +346,18 @@ def swing_targets(geom3, hip_offset12, in58, out72_prev=None):
     return out
 
 
-def walk_run(cfg26, time, contact, stop=None):
+def walk_run(cfg26, time, contact, stop=None, reset=None, want_state=False):
     """Walk gait generator of one robot as constructed + Reset(0): time [T], contact [T][4] -> out [T][41] (phaseInFullCycle,
     normalizedPhase, desiredLegState, legState, curLegState, detectedLegState, detectedEventTickPhase, moveBasePhase, contacts, fMinRatio,
-    fMaxRatio)."""
+    fMaxRatio).  reset [T]: non-zero = Reset() before that tick's Update.  want_state: also the kernel's walk_state rows [T][33]."""
     t = np.ascontiguousarray(time, _f); c = np.ascontiguousarray(contact, _f)
     out = np.zeros((t.shape[0], 41), _f)
     st = np.ascontiguousarray(stop, np.int32) if stop is not None else None
-    lib().qro_walk_run(_fp(np.ascontiguousarray(cfg26, _f)), t.shape[0], _fp(t), _fp(c), _ip(st) if st is not None else None, _fp(out))
-    return out
+    rs = np.ascontiguousarray(reset, np.int32) if reset is not None else None
+    state = np.zeros((t.shape[0], 33), _f) if want_state else None
+    lib().qro_walk_run(_fp(np.ascontiguousarray(cfg26, _f)), t.shape[0], _fp(t), _fp(c), _ip(st) if st is not None else None,
+                       _ip(rs) if rs is not None else None, _fp(out), _fp(state) if want_state else None)
+    return (out, state) if want_state else out
 
 
 def ground_run(in23):

@@ -287,8 +287,9 @@ void swing_targets(const LegGeom &geo, const float hip_offset[12], const float i
 //          quat_wxyz[4], footPosWorld[12] (leg major), footTargetWorld[12], contacts[4], phaseInFullCycle[4],
 //          dutyFactor[4], normalizedPhase[4], desiredLegState[4], legState[4], firstSwingBaseState x, y
 // st[8]  = xVelDes, yVelDes, yawTurnRate, yawDesTrue, posDesiredinWorld[3], iterationCounter   (in/out)
+// Returns false, with nothing written, unless 2 <= round(dtMPC / dt) <= 2^24 (the reference's cadence divides by half of it; include/qrgpu.h).
 // ---------------------------------------------------------------------------
-void mpc_frontend(int horizon, int numHorizonL, float dt, float dtMPC, const float in[64], float st[8], float *traj, float *gait, float *wbc15,
+bool mpc_frontend(int horizon, int numHorizonL, float dt, float dtMPC, const float in[64], float st[8], float *traj, float *gait, float *wbc15,
                   float contact_out[4], int *mpc_updated);
 
 }  // namespace qro

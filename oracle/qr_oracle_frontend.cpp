@@ -12,9 +12,11 @@ namespace qro {
 
 static inline float clipf(float c, float lo, float hi) { return c < lo ? lo : (c > hi ? hi : c); }   // QI/utils/qr_algebra.h:57-65
 
-void mpc_frontend(int horizon, int numHorizonL, float dt, float dtMPC, const float in[64], float st[8], float *traj, float *gait, float *wbc15 /*pBody vBody aBody rpy ori*/,
+bool mpc_frontend(int horizon, int numHorizonL, float dt, float dtMPC, const float in[64], float st[8], float *traj, float *gait, float *wbc15 /*pBody vBody aBody rpy ori*/,
                   float contact_out[4], int *mpc_updated)
 {
+    const float iterations = std::round(dtMPC / dt);                   // iterationsInaMPC (:51)
+    if (!(iterations >= 2.f && iterations <= 16777216.f)) return false;
     // dt = 0.002, dtMPC = 0.06 in the reference (:43-44)
     const double kPI = 3.14159265358979323846, k2PI = 6.28318530718;   // M_PI, M_2PI (QI/utils/qr_ctypes.h:51)
     const float des_height = in[0], des_pitch = in[2];
@@ -84,7 +86,7 @@ void mpc_frontend(int horizon, int numHorizonL, float dt, float dtMPC, const flo
     for (int j = 0; j < 4; ++j) gait[j] = (contacts[j] != 0.f) ? 1.f : 0.f;
 
     // ---- UpdateMPC (:342-381)
-    const int iterationsInaMPC = (int)std::round(dtMPC / dt);
+    const int iterationsInaMPC = (int)iterations;
     if (iterationCounter % (iterationsInaMPC / 2) == 0 || iterationCounter < 50) {
         const float xStart = clipf(posDes[0], p[0] - 0.1f, p[0] + 0.1f), yStart = clipf(posDes[1], p[1] - 0.1f, p[1] + 0.1f);
         posDes[0] = xStart; posDes[1] = yStart;
@@ -111,13 +113,21 @@ void mpc_frontend(int horizon, int numHorizonL, float dt, float dtMPC, const flo
     for (int j = 0; j < 4; ++j) contact_out[j] = (contacts[j] != 0.f) ? 1.f : 0.f;
     st[0] = xVelDes; st[1] = yVelDes; st[2] = yawTurnRate; st[3] = yawDesTrue;
     st[4] = posDes[0]; st[5] = posDes[1]; st[6] = posDes[2];
-    st[7] = (float)(iterationCounter + 1);
+    // st[7] is a float: a counter that would reach 2^24 (where + 1 is lost) goes to the smallest value >= 50 of its residue class modulo the period
+    int next = iterationCounter + 1;
+    if (next >= (1 << 24)) {
+        const int period = iterationsInaMPC / 2;
+        next %= period;
+        if (next < 50) next += period * ((50 - next + period - 1) / period);
+    }
+    st[7] = (float)next;
+    return true;
 }
 
 }  // namespace qro
 
-extern "C" void qro_mpc_frontend(int horizon, int numHorizonL, float dt, float dtMPC, const float *in64, float *st8, float *traj, float *gait, float *wbc15,
+extern "C" int qro_mpc_frontend(int horizon, int numHorizonL, float dt, float dtMPC, const float *in64, float *st8, float *traj, float *gait, float *wbc15,
                                  float *contact4, int *mpc_updated)
 {
-    qro::mpc_frontend(horizon, numHorizonL, dt, dtMPC, in64, st8, traj, gait, wbc15, contact4, mpc_updated);
+    return qro::mpc_frontend(horizon, numHorizonL, dt, dtMPC, in64, st8, traj, gait, wbc15, contact4, mpc_updated) ? 0 : -1;
 }

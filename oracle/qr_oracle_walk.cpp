@@ -111,7 +111,9 @@ void walk_update(const WalkConfig &c, const WalkDerived &d, float currentTime, c
 
 // cfg27: stance_duration[4], duty_factor[4], initial_leg_phase[4], initial_leg_state[4], contact_detection_phase_threshold, n_states,
 //        state_switch[4] (SubLegState values), state_ratio[4], pad
-extern "C" void qro_walk_run(const float *cfg, int nticks, const float *time, const float *contact /*[nticks][4]*/, const int *stop, float *out /*[nticks][41]*/)
+// reset (may be null): non-zero = Reset() on the running generator before that tick's Update.  state (may be null) [nticks][33]: the kernel's walk_state rows.
+extern "C" void qro_walk_run(const float *cfg, int nticks, const float *time, const float *contact /*[nticks][4]*/, const int *stop, const int *reset,
+                             float *out /*[nticks][41]*/, float *state)
 {
     qro::WalkConfig c;
     for (int l = 0; l < 4; ++l) { c.stance_duration[l] = cfg[l]; c.duty_factor[l] = cfg[4 + l]; c.initial_leg_phase[l] = cfg[8 + l]; c.initial_leg_state[l] = (int)cfg[12 + l]; }
@@ -121,5 +123,16 @@ extern "C" void qro_walk_run(const float *cfg, int nticks, const float *time, co
     qro::walk_derive(c, d);
     qro::WalkState s;
     qro::walk_reset(c, d, s, true);
-    for (int k = 0; k < nticks; ++k) qro::walk_update(c, d, time[k], contact + 4 * k, stop ? stop[k] != 0 : false, s, out + 41 * k);
+    for (int k = 0; k < nticks; ++k) {
+        if (reset && reset[k]) qro::walk_reset(c, d, s, false);
+        qro::walk_update(c, d, time[k], contact + 4 * k, stop ? stop[k] != 0 : false, s, out + 41 * k);
+        if (state) {
+            float *w = state + 33 * k;
+            for (int l = 0; l < 4; ++l) {
+                w[l] = (float)s.cur[l]; w[4 + l] = (float)s.desired[l]; w[8 + l] = (float)s.leg[l]; w[12 + l] = (float)s.detected[l]; w[16 + l] = (float)s.state_index[l];
+                w[20 + l] = s.phase[l]; w[24 + l] = s.nphase[l]; w[28 + l] = s.event_phase[l];
+            }
+            w[32] = s.move_base_phase;
+        }
+    }
 }

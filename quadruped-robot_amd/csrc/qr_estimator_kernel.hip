@@ -664,7 +664,10 @@ __global__ void __launch_bounds__(64) qr_ground_kernel(int n, int fresh, const f
         else if (r11 > r22) { const double S = sqrt(1.0 + r11 - r00 - r22) * 2.0; q0 = (r02 - r20) / S; q1 = (r01 + r10) / S; q2 = 0.25 * S; q3 = (r12 + r21) / S; }
         else { const double S = sqrt(1.0 + r22 - r00 - r11) * 2.0; q0 = (r10 - r01) / S; q1 = (r02 + r20) / S; q2 = (r12 + r21) / S; q3 = 0.25 * S; }
         double nr[3];
-        const double as = fmin(-2. * (q1 * q3 - q0 * q2), .99999);
+        // std::min(v, .99999) is (.99999 < v) ? .99999 : v: a NaN v stays NaN (fmin would drop it and hand back .99999), and with it the pitch
+        // of a frame whose x axis came out of 0 / 0 -- a base x axis that is exactly vertical
+        const double as_raw = -2. * (q1 * q3 - q0 * q2);
+        const double as = (.99999 < as_raw) ? .99999 : as_raw;
         nr[2] = atan2(2 * (q1 * q2 + q0 * q3), q0 * q0 + q1 * q1 - q2 * q2 - q3 * q3);
         nr[1] = asin(as);
         nr[0] = atan2(2 * (q2 * q3 + q0 * q1), q0 * q0 - q1 * q1 - q2 * q2 + q3 * q3);

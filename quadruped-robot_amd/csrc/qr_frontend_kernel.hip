@@ -23,9 +23,10 @@ __device__ __forceinline__ float fe_clip(float c, float lo, float hi) { return c
 // blockDim = (64 robots, horizon): thread (x, k) recomputes the short scalar prefix of robot x and writes row k of its contact table
 // and reference trajectory, so that the h-long store loops of one robot run side by side; thread k = 0 also writes the
 // controller memory, the WBC rows and the re-plan flag.  The barrier separates every read of fe_state from its rewrite.
-__global__ void __launch_bounds__(1024) qr_frontend_kernel(int n, int horizon, int numHorizonL, float dt, float dtMPC, const float *__restrict__ fin,
-                                                           float *__restrict__ fst, float *__restrict__ g_traj, float *__restrict__ g_gait,
-                                                           float *__restrict__ g_cmd, int *__restrict__ g_updated)
+// period = round(dtMPC / dt) / 2 in integers, 1 <= period <= 2^23: the entry point works it out once and refuses every other value.
+__global__ void __launch_bounds__(1024) qr_frontend_kernel(int n, int horizon, int numHorizonL, float dt, float dtMPC, int period,
+                                                           const float *__restrict__ fin, float *__restrict__ fst, float *__restrict__ g_traj,
+                                                           float *__restrict__ g_gait, float *__restrict__ g_cmd, int *__restrict__ g_updated)
 {
 #pragma clang fp contract(off)
     const int krow = threadIdx.y;
@@ -113,8 +114,6 @@ __global__ void __launch_bounds__(1024) qr_frontend_kernel(int n, int horizon, i
     }
 
     // UpdateMPC (:342-381): re-plan twice per MPC period and on each of the first 50 ticks
-    const int iterationsInaMPC = (int)roundf(dtMPC / dt);
-    const int period = iterationsInaMPC / 2 > 0 ? iterationsInaMPC / 2 : 1;
     const bool upd = (iterationCounter % period == 0) || iterationCounter < 50;
     if (upd) {
         posx = fe_clip(posx, px - 0.1f, px + 0.1f);
@@ -144,7 +143,15 @@ __global__ void __launch_bounds__(1024) qr_frontend_kernel(int n, int horizon, i
     }
     fst[0 * N + i] = xVelDes; fst[1 * N + i] = yVelDes; fst[2 * N + i] = yawTurnRate; fst[3 * N + i] = yawDesTrue;
     fst[4 * N + i] = posx; fst[5 * N + i] = posy; fst[6 * N + i] = posz;
-    fst[7 * N + i] = (float)(iterationCounter + 1);
+    // The counter lives in a float row: from 2^24 on, counter + 1 would round back onto itself and the cadence above would stop for good.
+    // A counter that would reach 2^24 goes to the smallest value >= 50 of its residue class modulo the period instead (below 50 + 2^23):
+    // neither term of the cadence can tell it from the reference's integer.
+    int next = iterationCounter + 1;
+    if (next >= (1 << 24)) {
+        next %= period;
+        if (next < 50) next += period * ((50 - next + period - 1) / period);
+    }
+    fst[7 * N + i] = (float)next;
 #undef FIN
 }
 

@@ -46,8 +46,8 @@ __global__ void qr_wbc_kernel_dbg(int n, const WbcConst *types, const int *type_
                                   const float *g_fr, int type_ready, int epilogue, float *g_qp, WbcPipe pipe);
 
 // qr_frontend_kernel.hip, qr_vmc_kernel.hip
-__global__ void qr_frontend_kernel(int n, int horizon, int numHorizonL, float dt, float dtMPC, const float *fin, float *fst, float *g_traj,
-                                   float *g_gait, float *g_cmd, int *g_updated);
+__global__ void qr_frontend_kernel(int n, int horizon, int numHorizonL, float dt, float dtMPC, int period, const float *fin, float *fst,
+                                   float *g_traj, float *g_gait, float *g_cmd, int *g_updated);
 __global__ void qr_vmc_kernel(VmcLaunch P, const int *type_id, const float *g_in, const float *g_q, float *g_force, float *g_tau, int *g_status);
 
 // qr_estimator_kernel.hip

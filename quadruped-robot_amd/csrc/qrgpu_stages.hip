@@ -321,9 +321,13 @@ int qrgpu_mpc_frontend_batch(qrgpu_ctx *c, int n, int num_horizon_l, float dt_ct
 {
     if (!batch_ok(c, n) || !d_fe_in || !d_fe_state || !d_traj || !d_gait) return QRGPU_ERR_BAD_ARG;
     if (num_horizon_l <= 0 || !(dt_ctrl > 0.f) || !(dt_mpc > 0.f)) return QRGPU_ERR_BAD_ARG;
+    // iterationsInaMPC = round(dtMPC / dt) (:51); the cadence takes a remainder by half of it, so the reference cannot run below 2.  The upper
+    // bound keeps the period within what the float counter row can hold (include/qrgpu.h).
+    const float iterations = roundf(dt_mpc / dt_ctrl);
+    if (!(iterations >= 2.f && iterations <= 16777216.f)) return QRGPU_ERR_BAD_ARG;
     if (!c->mpc_ready[0]) return QRGPU_ERR_NOT_SETUP;
-    return launch_stage(c, qr_frontend_kernel, per_robot(n), dim3(64, c->mpc.horizon), n, c->mpc.horizon, num_horizon_l, dt_ctrl, dt_mpc, d_fe_in, d_fe_state, d_traj,
-                        d_gait, d_wbc_cmd, d_mpc_updated);
+    return launch_stage(c, qr_frontend_kernel, per_robot(n), dim3(64, c->mpc.horizon), n, c->mpc.horizon, num_horizon_l, dt_ctrl, dt_mpc, (int)iterations / 2,
+                        d_fe_in, d_fe_state, d_traj, d_gait, d_wbc_cmd, d_mpc_updated);
 }
 
 void qrgpu_plant_params_default(qrgpu_plant_params *p)

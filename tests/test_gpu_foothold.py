@@ -74,3 +74,22 @@ def test_gait_to_swing_targets_chain_on_device(gpu_ctx, pkg, oracle):
         assert np.abs(g_cmd[i, 15:51] - o[:36]).max() <= 5e-6, i
     for v in (d_st, d_go, d_ct, d_fh, d_sw, d_cmd):
         v.free()
+
+
+@pytest.mark.parametrize("robot", ["a1", "lite3"])
+def test_kernel_is_the_model(gpu_ctx, pkg, robot):
+    """qr_foothold_kernel against tests/foothold_ref.py (float64, vectors and matrices) on its wide family -- raw attitudes to +-0.6, omega +-4,
+    v +-2, held legs on both sides of +-0.01, every leg state: flags and phases exact, the same rows written, footholds 1e-6 m; threshold ties
+    (at most 0.5 % of the planned legs) on their flags only."""
+    import foothold_ref as R
+    desc = pkg.workload.foothold_cfg(robot)
+    x = R.foothold_family(pkg, robot)
+    n = x.shape[0]
+    d_in = gpu_ctx.alloc((46, n)).upload(pkg.to_soa(x))
+    d_sw = gpu_ctx.alloc((58, n)).upload(np.full((58, n), R.SENTINEL, np.float32))
+    gpu_ctx.footholds_batch(n, desc, d_in, d_sw)
+    gpu_ctx.sync()
+    worst = {}
+    share = R.check_footholds(desc, x, d_sw.download().T, robot + " kernel", worst)
+    print("%s kernel against foothold_ref: tie share %.4f, worst %s" % (robot, share, worst))
+    d_in.free(); d_sw.free()

@@ -2,9 +2,13 @@
 MPCStanceLegController::SetupCommand / Run / UpdateMPC (qr_mpc_stance_leg_controller.cpp:158-382).
 
 Bar: bit-exact float32, except the three outputs that carry std::sin (height / pitch compensation: bodyHeight, rpyComp[1]),
-where libm and the device library may differ in the last bit of a double sine -> at most 1 float ulp."""
+where libm and the device library may differ in the last bit of a double sine -> at most 1 float ulp.
+
+The second half holds the kernel to tests/frontend_ref.py, the reference restated statement by statement, on every tick of every robot of its
+families at the same bar, and pins the two things that model found: the float tick counter at 2^24 and the re-plan period of zero."""
 import numpy as np
 
+import frontend_ref as R
 import gpu_helpers as G
 import pytest
 
@@ -122,4 +126,78 @@ def test_frontend_sequence_feeds_tick(gpu_ctx, pkg, oracle):
     assert np.all(st_o == 0)
     assert np.all(np.abs(tau - tau_o) <= tau_tol(tau_o, 1e-4)), np.abs(tau - tau_o).max()
     for v in list(d.values()) + [d_in, d_st, d_traj, d_gait, d_cmd, d_upd]:
+        v.free()
+
+
+# ----------------------------------------------------------------------------- the kernel against tests/frontend_ref.py
+def kernel_sequence(ctx, pkg, f, idx=None, guard=None):
+    """qr_frontend_kernel on a family of frontend_ref: the controller memory and the trajectory stay on the device from tick to tick.
+    -> outs[tick] = dict of [n][...] arrays in the oracle's layout"""
+    setup_a1(ctx, pkg, f["h"])
+    idx = np.arange(f["st"].shape[0]) if idx is None else idx
+    n, h, S = len(idx), f["h"], pkg.to_soa
+    d_in = ctx.alloc((64, n)); d_st = ctx.alloc((8, n)).upload(S(f["st"][idx]))
+    d_traj = ctx.alloc((12 * h, n)).upload(np.full((12 * h, n), np.nan, np.float32)); d_gait = ctx.alloc((4 * h, n))
+    d_cmd = ctx.alloc((67, n)).upload(np.full((67, n), np.nan, np.float32)); d_upd = ctx.alloc((n,), np.int32)
+    outs = []
+    for k in range(f["ticks"]):
+        if k < f["fe"].shape[0]:
+            d_in.upload(S(f["fe"][k][idx]))
+        ctx.mpc_frontend_batch(n, d_in, d_st, d_traj, d_gait, d_cmd, d_upd, num_horizon_l=f["L"], dt_ctrl=f["dt"], dt_mpc=f["dt_mpc"])
+        cmd = d_cmd.download().T
+        assert np.isnan(cmd[:, 15:63]).all()
+        outs.append(dict(traj=d_traj.download().T.copy(), gait=d_gait.download().T.copy(), wbc15=cmd[:, :15].copy(), contact=cmd[:, 63:67].copy(),
+                         state=d_st.download().T.copy(), updated=d_upd.download().copy()))
+    for v in (d_in, d_st, d_traj, d_gait, d_cmd, d_upd):
+        v.free()
+    return outs
+
+
+@pytest.mark.parametrize("name", R.NAMES)
+def test_kernel_is_the_model_on_every_tick(gpu_ctx, pkg, name):
+    """Every tick of every robot of every family of tests/frontend_ref.py: bit for bit, the sine rows to 1 ulp, the counter row as
+    include/qrgpu.h states it."""
+    f, want, _ = R.expected(pkg, name)
+    period = R.iterations_in_a_mpc(f["dt"], f["dt_mpc"]) // 2
+    got = kernel_sequence(gpu_ctx, pkg, f)
+    for k in range(f["ticks"]):
+        for r in range(R.N_ROBOTS):
+            R.compare({key: v[r] for key, v in got[k].items()}, want[r][k], period, (name, r, k))
+
+
+@pytest.mark.parametrize("ratio", [30, 25, 3])
+def test_counter_started_below_2p24_replans_like_an_integer(gpu_ctx, pkg, ratio):
+    """The counter row is a float: started at 2^24 - 3 it must go on re-planning on the ticks on which an integer counter does."""
+    f, _, _ = R.expected(pkg, "counter_2p24_%d" % ratio)
+    got = kernel_sequence(gpu_ctx, pkg, f)
+    integer = (((1 << 24) - 3 + np.arange(f["ticks"])) % (ratio // 2) == 0).astype(np.int32)
+    upd = np.stack([o["updated"] for o in got])                       # [tick][robot]
+    assert np.array_equal(upd, np.repeat(integer[:, None], R.N_ROBOTS, axis=1))
+    rows = np.stack([o["state"][:, 7] for o in got])
+    assert np.all(rows < 1 << 24) and np.all(rows[3:] >= 50)
+    # the fold tick stores the SMALLEST value >= 50 of 2^24's residue class, and the row counts on from it
+    assert np.all(rows[1] == (1 << 24) - 1) and np.all(rows[2] == R.folded(1 << 24, ratio // 2)) and R.folded(1 << 24, ratio // 2) - ratio // 2 < 50
+    assert np.array_equal(rows[2:], rows[2:3] + np.arange(rows.shape[0] - 2)[:, None])
+
+
+def test_period_of_zero_is_refused_and_nothing_is_written(gpu_ctx, pkg):
+    """round(dt_mpc / dt_ctrl) < 2 (the reference's remainder by zero) or beyond 2^24: QRGPU_ERR_BAD_ARG, no launch."""
+    setup_a1(gpu_ctx, pkg, 10)
+    n, S = 65, pkg.to_soa
+    fe, st = pkg.workload.make_frontend_batch(n, seed=4)
+    poison = lambda rows: np.full((rows, n), -7.5, np.float32)
+    d_in = gpu_ctx.alloc((64, n)).upload(S(fe)); d_st = gpu_ctx.alloc((8, n)).upload(S(st))
+    d_traj = gpu_ctx.alloc((120, n)).upload(poison(120)); d_gait = gpu_ctx.alloc((40, n)).upload(poison(40)); d_cmd = gpu_ctx.alloc((67, n)).upload(poison(67))
+    for dt, dt_mpc in ((0.002, 0.002), (0.002, 0.0029), (0.002, 0.0005), (0.06, 0.002), (0.002, 40000.0)):
+        with pytest.raises(pkg.QrgpuError, match="BAD_ARG"):
+            gpu_ctx.mpc_frontend_batch(n, d_in, d_st, d_traj, d_gait, d_cmd, None, dt_ctrl=dt, dt_mpc=dt_mpc)
+    gpu_ctx.sync()
+    assert np.array_equal(d_st.download(), S(st))
+    assert np.all(d_traj.download() == -7.5) and np.all(d_gait.download() == -7.5) and np.all(d_cmd.download() == -7.5)
+    # round = 2 and 3 are the smallest that run: a period of 1, a re-plan on every tick
+    d_upd = gpu_ctx.alloc((n,), np.int32)
+    for dt_mpc in (0.004, 0.006):
+        gpu_ctx.mpc_frontend_batch(n, d_in, d_st, d_traj, d_gait, d_cmd, d_upd, dt_mpc=dt_mpc)
+        assert np.all(d_upd.download() == 1)
+    for v in (d_in, d_st, d_traj, d_gait, d_cmd, d_upd):
         v.free()

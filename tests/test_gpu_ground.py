@@ -4,6 +4,8 @@ Bar: the same double arithmetic on both sides -- 1e-6 absolute on every output (
 import numpy as np
 import pytest
 
+import ground_ref as R
+
 pytestmark = pytest.mark.gpu
 
 
@@ -69,3 +71,23 @@ def test_ground_without_outputs_keeps_state(gpu_ctx, pkg, oracle):
         assert g[r, 31] == 1 and np.abs(g[r, :31].astype(np.float64) - o[1, :31]).max() < 1e-6
     for v in (d_in, d_out, d_st):
         v.free()
+
+
+@pytest.mark.parametrize("name", R.FAMILIES)
+def test_kernel_is_the_model_on_every_tick(gpu_ctx, pkg, name):
+    """qr_ground_kernel against tests/ground_ref.py (float64, an SVD least-squares plane, the frame from the heading) on every tick of every robot
+    of its families: the same ticks fire, the same entries are NaN (the exactly vertical x-axis), 1e-6 on every output; the plane coefficients of
+    the nearly-collinear family at the bar ground_ref states."""
+    x, want, _ = R.expected(name)
+    T, n = x.shape[0], x.shape[1]
+    d_in = gpu_ctx.alloc((23, n)); d_out = gpu_ctx.alloc((32, n))
+    d_st = gpu_ctx.alloc((13, n), np.float64).upload(np.full((13, n), np.nan))
+    got = np.zeros((n, T, 32), np.float32)
+    for t in range(T):
+        d_in.upload(pkg.to_soa(x[t]))
+        gpu_ctx.ground_update_batch(n, d_in, d_st, d_out, None, reset=(t == 0))
+        got[:, t] = d_out.download().T
+    for v in (d_in, d_out, d_st):
+        v.free()
+    worst, ratio = R.check(name, got, "kernel")
+    print("%-10s kernel against model: worst %.3e, collinear excess ratio %.3e" % (name, worst, ratio))

@@ -1,5 +1,6 @@
 """Batch edges, guard rows and error returns of the per-robot stage entry points: qrgpu_estimator_update_batch, qrgpu_pack_state_batch,
-qrgpu_ground_update_batch, qrgpu_gait_update_batch, qrgpu_footholds_batch, qrgpu_swing_targets_batch (one thread per robot, workgroups of 64).
+qrgpu_ground_update_batch, qrgpu_gait_update_batch, qrgpu_footholds_batch, qrgpu_swing_targets_batch, qrgpu_walk_gait_update_batch,
+qrgpu_swing_velocity_batch (one thread per robot, workgroups of 64), and qrgpu_mpc_frontend_batch at horizons 1 and 16 (workgroups of 64 robots x h rows).
 
   * batch edges: n = 1, 63, 64, 65.  A robot's outputs and memory are the same bits whether it runs in a batch of 65, in the first 63 or 64
     of it, alone (n = 1), or in the reversed batch.
@@ -19,6 +20,7 @@ pytestmark = pytest.mark.gpu
 N = 65
 P32 = np.float32(-12345.5)
 P64 = np.float64(-98765.25)
+PI = np.int32(-12345)
 BAD_ARG = 2
 
 
@@ -26,7 +28,7 @@ class Guarded:
     """A device array [rows + 1][n] whose last row is a poisoned guard; `fill` initialises the rows the call owns (None: poison as well)."""
 
     def __init__(self, ctx, rows, n, dtype=np.float32, fill=None):
-        self.rows, self.n, self.poison = rows, n, (P64 if np.dtype(dtype) == np.float64 else P32)
+        self.rows, self.n, self.poison = rows, n, (P64 if np.dtype(dtype) == np.float64 else PI if np.dtype(dtype) == np.int32 else P32)
         host = np.full((rows + 1, n), self.poison if fill is None else fill, dtype)
         host[rows] = self.poison
         self.d = ctx.alloc((rows + 1, n), dtype).upload(host)
@@ -63,13 +65,19 @@ def _inputs(pkg):
     gt = (np.arange(40) * 0.02).astype(np.float32)                      # 20 ms ticks: touch-downs, holds and early contacts within 40 ticks
     gcfg = W.gait_cfg(stance_duration=0.3, duty_factor=0.5, initial_leg_state=(0, 1, 1, 0), wait_time=0.06)
     rng = np.random.default_rng(92)
+    wt = (np.arange(60) * 0.02).astype(np.float32)                      # a 1 s walk cycle on 20 ms ticks: every sub-state and both contact events within 60
+    wcfg = W.walk_cfg(stance_duration=0.75)
     return dict(
         estimator=dict(x=x, stamp=stamp),
         pack=dict(x=x[:1], est=rng.uniform(-2, 2, (1, N, 42)).astype(np.float32), rpy=rng.uniform(-3, 3, (1, N, 3)).astype(np.float32)),
         ground=dict(x=G.ground_sequences(N, 16, seed=93)),
         gait=dict(c=GR.contacts(N, 40, gcfg, gt, 94), t=gt, cfg=gcfg),
         foothold=dict(x=W.make_foothold_batch(N, seed=95)[None]),
-        swing=dict(x=W.make_swing_batch(N, seed=96)[None]))
+        swing=dict(x=W.make_swing_batch(N, seed=96)[None]),
+        walk=dict(c=GR.contacts(N, 60, W.gait_cfg(stance_duration=0.75, duty_factor=0.75), wt, 99), t=wt, cfg=wcfg),
+        swing_velocity=dict(x=W.make_swing_velocity_batch(N, seed=100)[None]),
+        frontend_h1=dict(zip(("x", "st"), W.make_frontend_batch(N, seed=97)), h=1),
+        frontend_h16=dict(zip(("x", "st"), W.make_frontend_batch(N, seed=98)), h=16))
 
 
 def run_estimator(ctx, pkg, inp, idx):
@@ -150,7 +158,56 @@ def run_swing(ctx, pkg, inp, idx):
     return r
 
 
-RUNNERS = dict(estimator=run_estimator, pack=run_pack, ground=run_ground, gait=run_gait, foothold=run_foothold, swing=run_swing)
+def run_walk(ctx, pkg, inp, idx):
+    n = len(idx)
+    st = Guarded(ctx, 33, n); out = Guarded(ctx, 41, n); ratio = Guarded(ctx, 8, n); vmc = Guarded(ctx, 37, n)
+    d_c = ctx.alloc((4, n))
+    for k in range(inp["t"].size):
+        d_c.upload(pkg.to_soa(inp["c"][k][idx]))
+        ctx.walk_gait_update_batch(n, inp["cfg"], float(inp["t"][k]), d_c, st, out, ratio, vmc, stop=(30 <= k < 40), reset=2 if k == 0 else int(k == 45))
+    ctx.sync()
+    d_c.free()
+    r = dict(out=out.take(), state=st.take(), ratio=ratio.take(), vmc=vmc.take())
+    assert np.all(r["vmc"][:, :18] == P32) and np.all(r["vmc"][:, 22:] == P32)
+    return r
+
+
+def run_swing_velocity(ctx, pkg, inp, idx):
+    n = len(idx)
+    d_in = ctx.alloc((53, n)).upload(pkg.to_soa(inp["x"][0][idx]))
+    out = Guarded(ctx, 48, n)
+    ctx.swing_velocity_batch(n, _est_cfg(pkg), pkg.workload.swing_velocity_cfg("a1"), d_in, out)
+    ctx.sync()
+    d_in.free()
+    r = dict(out=out.take())
+    flagged = np.repeat(inp["x"][0][idx][:, 0:4] != 0, 3, axis=1)                       # [n][12]: leg-major rows of each of the four blocks
+    for b in range(4):
+        blk = r["out"][:, 12 * b:12 * b + 12]
+        assert np.all(blk[~flagged] == P32)                                             # legs that are not flagged are not written
+        assert b > 1 or np.all(blk[flagged] != P32)                                     # (an unreachable target leaves joint rows as they are)
+    return r
+
+
+def run_frontend(ctx, pkg, inp, idx):
+    """Three ticks at the horizon of inp["h"]: the block is (64, h), and the threads past the batch shadow its last robot up to a barrier."""
+    n, h = len(idx), inp["h"]
+    G.setup_a1(ctx, pkg, h)
+    st = Guarded(ctx, 8, n); traj = Guarded(ctx, 12 * h, n); gait = Guarded(ctx, 4 * h, n); cmd = Guarded(ctx, 67, n); upd = Guarded(ctx, 1, n, np.int32)
+    st.d.upload(np.concatenate([pkg.to_soa(inp["st"][idx]), np.full((1, n), P32)]))
+    d_in = ctx.alloc((64, n)).upload(pkg.to_soa(inp["x"][idx]))
+    for k in range(3):
+        ctx.mpc_frontend_batch(n, d_in, st, traj, gait, cmd, upd, num_horizon_l=3)
+    ctx.sync()
+    d_in.free()
+    r = dict(state=st.take(), traj=traj.take(), gait=gait.take(), cmd=cmd.take(), updated=upd.take())
+    assert np.all(r["cmd"][:, 15:63] == P32)
+    replan = r["updated"][:, 0] == 1                                                   # (counters 0 .. 119: both kinds in every batch but n = 1)
+    assert np.all(r["traj"][replan] != P32) and np.array_equal(r["state"][:, 7], inp["st"][idx, 7] + 3)
+    return r
+
+
+RUNNERS = dict(estimator=run_estimator, pack=run_pack, ground=run_ground, gait=run_gait, foothold=run_foothold, swing=run_swing, walk=run_walk, swing_velocity=run_swing_velocity,
+               frontend_h1=run_frontend, frontend_h16=run_frontend)
 
 
 @pytest.fixture(scope="module")
@@ -179,6 +236,8 @@ def test_batch_edges_and_guard_rows(gpu_ctx, pkg, inputs, stage):
         assert np.unique(full["state"][:, 0]).size > 3                                            # holds moved the robots' clocks apart
     if stage == "ground":
         assert (full["state"][:, 4:7] != 0).any()                                                 # the plane fit fired
+    if stage == "walk":
+        assert np.unique(full["out"][:, 20:28], axis=0).shape[0] > 8                              # contact events tell the robots apart
 
 
 # ----------------------------------------------------------------------------- error returns
@@ -278,4 +337,70 @@ def test_error_returns_leave_the_outputs_untouched(gpu_ctx, pkg):
     bad(f(h, n, C.byref(ed), None, _ptr(cmd), _ptr(tgt), _ptr(qd)))
     bad(f(h, n, C.byref(ed), I, None, None, None))                                      # all three outputs NULL
     assert cmd.untouched() and tgt.untouched() and qd.untouched()
+
+    # ---- walk gait
+    st = Guarded(gpu_ctx, 33, n); out = Guarded(gpu_ctx, 41, n); ratio = Guarded(gpu_ctx, 8, n); vmc = Guarded(gpu_ctx, 37, n)
+    wd = Q.walk_gait_desc_struct(); lib.qrgpu_walk_gait_desc_default(C.byref(wd))
+    f = lib.qrgpu_walk_gait_update_batch
+    call = lambda nn=n, d=wd, reset=2, c=I, s=st: f(h, nn, None if d is None else C.byref(d), 0.0, 0, reset, c, _ptr(s), _ptr(out), _ptr(ratio), _ptr(vmc))
+    for nn in (0, too_many, -1):
+        bad(call(nn=nn))
+    bad(call(d=None)); bad(call(c=None)); bad(call(s=None))
+    for r in (3, -1, 255):                                                             # reset is 0, 1 (Reset()) or 2 (as constructed)
+        bad(call(reset=r))
+
+    def walk_desc(**kw):
+        d = Q.walk_gait_desc_struct(); lib.qrgpu_walk_gait_desc_default(C.byref(d))
+        for k, v in kw.items():
+            if isinstance(v, tuple):
+                for j, x in enumerate(v):
+                    getattr(d, k)[j] = x
+            else:
+                setattr(d, k, v)
+        return d
+
+    for kw in (dict(state_ratio=(0.2, 0.3, 0.3, 0.3)), dict(state_ratio=(0.2, 0.3, 0.3, 0.1)), dict(state_ratio=(0.0, 0.0, 0.0, 0.0)),       # do not sum to 1
+               dict(state_ratio=(float("nan"), 0.3, 0.3, 0.2)), dict(n_states=0), dict(n_states=5), dict(n_states=-1), dict(n_states=3),   # (3: the first three sum to 0.8)
+               dict(duty_factor=(0.75, 0.0, 0.75, 0.75)), dict(duty_factor=(0.75, 0.75, 0.001, 0.75)), dict(duty_factor=(1.0, 0.75, 0.75, 0.75)),
+               dict(duty_factor=(0.75, 0.75, 0.75, float("nan"))), dict(stance_duration=(7.5, 0.0, 7.5, 7.5)), dict(stance_duration=(7.5, 7.5, -1.0, 7.5)),
+               dict(state_switch=(7, 6, 8, 4)), dict(state_switch=(7, 6, 8, 1))):                                                          # not a SubLegState
+        bad(call(d=walk_desc(**kw)))
+    assert st.untouched() and out.untouched() and ratio.untouched() and vmc.untouched()
+
+    # ---- swing action of the velocity mode
+    out = Guarded(gpu_ctx, 48, n)
+    vd = Q.swing_velocity_desc_struct()
+    f = lib.qrgpu_swing_velocity_batch
+    for nn in (0, too_many, -1):
+        bad(f(h, nn, C.byref(ed), C.byref(vd), I, _ptr(out)))
+    bad(f(h, n, None, C.byref(vd), I, _ptr(out)))
+    bad(f(h, n, C.byref(ed), None, I, _ptr(out)))
+    bad(f(h, n, C.byref(ed), C.byref(vd), None, _ptr(out)))
+    bad(f(h, n, C.byref(ed), C.byref(vd), I, None))
+    assert out.untouched()
+
+    # ---- MPC front-end
+    G.setup_a1(gpu_ctx, pkg, 10)
+    NOT_SETUP = 3
+    st = Guarded(gpu_ctx, 8, n); traj = Guarded(gpu_ctx, 120, n); gait = Guarded(gpu_ctx, 40, n); cmd = Guarded(gpu_ctx, 67, n); upd = Guarded(gpu_ctx, 1, n, np.int32)
+    f = lib.qrgpu_mpc_frontend_batch
+    call = lambda nn=n, L=2, dt=0.002, dtm=0.06, fin=I, s=st, t=traj, g=gait, hh=h: f(hh, nn, L, dt, dtm, fin, _ptr(s), _ptr(t), _ptr(g), _ptr(cmd), _ptr(upd))
+    for nn in (0, too_many, -1):
+        bad(call(nn=nn))
+    bad(call(fin=None)); bad(call(s=None)); bad(call(t=None)); bad(call(g=None))
+    for L in (0, -2):
+        bad(call(L=L))
+    for v in (0.0, -0.002, float("nan")):
+        bad(call(dt=v)); bad(call(dtm=v))
+    for dt, dtm in ((0.002, 0.002), (0.002, 0.0029), (0.06, 0.002), (0.002, 40000.0), (1e-42, 0.06)):      # round(dt_mpc / dt_ctrl) outside 2 .. 2^24
+        bad(call(dt=dt, dtm=dtm))
+    fresh = pkg.Context(device_id=0, max_batch=8, horizon_max=16)
+    try:
+        assert call(hh=fresh._h) == NOT_SETUP                                           # before qrgpu_mpc_setup
+        bad(call(hh=fresh._h, L=0))
+        fresh.sync()
+    finally:
+        fresh.close()
+    gpu_ctx.sync()
+    assert st.untouched() and traj.untouched() and gait.untouched() and cmd.untouched() and upd.untouched()
     some.free(); tick.free()

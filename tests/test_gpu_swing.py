@@ -90,3 +90,42 @@ def test_joint_targets_against_the_model_on_the_ik_domain(gpu_ctx, pkg, robot):
     for a in (a0, a1):
         assert np.abs(np.delete(a, [3, 4, 5]) - np.delete(np.tile(SR.STAND, 4), [3, 4, 5])).max() <= 2e-5
     d_in.free(); d_q.free()
+
+
+@pytest.mark.parametrize("robot", ["a1", "lite3"])
+def test_velocity_action_against_the_model(gpu_ctx, pkg, robot):
+    """qr_swing_velocity_kernel against tests/foothold_ref.py: the Raibert target through baseRInControlFrame 1e-6 m, the trajectory point at the
+    warped phase 2e-6 m, joint targets through the model's forward kinematics at 5e-6 m, legs that are not flagged untouched."""
+    import foothold_ref as R
+    W = pkg.workload
+    cfg, vd = W.estimator_cfg(robot), W.swing_velocity_cfg(robot)
+    x = R.velocity_family(pkg, robot)
+    n = x.shape[0]
+    d_in = gpu_ctx.alloc((53, n)).upload(pkg.to_soa(x))
+    d_out = gpu_ctx.alloc((48, n)).upload(np.full((48, n), R.SENTINEL, np.float32))
+    gpu_ctx.swing_velocity_batch(n, cfg, vd, d_in, d_out)
+    gpu_ctx.sync()
+    worst = {}
+    share = R.check_velocity(cfg, vd, x, d_out.download().T, robot + " kernel", worst)
+    print("%s kernel against foothold_ref: tie share %.4f, worst %s" % (robot, share, worst))
+    d_in.free(); d_out.free()
+
+
+@pytest.mark.parametrize("robot", ["a1", "lite3"])
+def test_swing_target_trajectory_against_the_model(gpu_ctx, pkg, robot):
+    """The trajectory part of qrgpu_swing_targets_batch against the model's generator at phaseModule = false: pFoot_des and the world-frame
+    foot targets 2e-6 (relative beyond 1 m), legs that are not flagged untouched.  (Its IK is pinned above.)"""
+    import foothold_ref as R
+    cfg = pkg.workload.estimator_cfg(robot)
+    x = R.targets_family(pkg, robot)
+    n = x.shape[0]
+    d_in = gpu_ctx.alloc((58, n)).upload(pkg.to_soa(x))
+    d_cmd = gpu_ctx.alloc((67, n)).upload(np.full((67, n), R.SENTINEL, np.float32))
+    d_tgt = gpu_ctx.alloc((12, n)).upload(np.full((12, n), R.SENTINEL, np.float32))
+    gpu_ctx.swing_targets_batch(n, cfg, d_in, d_cmd, d_tgt, None)
+    gpu_ctx.sync()
+    worst = {}
+    R.check_targets(x, np.concatenate([d_cmd.download().T[:, 15:51], d_tgt.download().T], axis=1), robot + " kernel", worst)
+    print("%s kernel against foothold_ref: worst %s" % (robot, worst))
+    for v in (d_in, d_cmd, d_tgt):
+        v.free()

@@ -4,6 +4,8 @@ world-frame force distribution.  Reference: qrWalkGaitGenerator::Update (qr_walk
 import numpy as np
 import pytest
 
+import walk_ref as R
+
 pytestmark = pytest.mark.gpu
 
 
@@ -64,3 +66,41 @@ def test_walk_bad_arguments(gpu_ctx, pkg):
     with pytest.raises(pkg.QrgpuError):                                # USERDEFINED_SWING legs are not built
         gpu_ctx.walk_gait_update_batch(n, W.walk_cfg(duty_factor=0.0), 0.0, d_c, d_state, reset=2)
     d_c.free(); d_state.free()
+
+
+# ----------------------------------------------------------------------------- the kernel against tests/walk_ref.py
+def kernel_run(ctx, pkg, f, optional=True):
+    """qr_walk_gait_kernel on a family of walk_ref, one launch per tick, every tick's outputs kept on the device and fetched once.
+    -> out [n][T][41], ratio [n][T][8], vmc_in [n][T][37] (None without the optional outputs), final state [n][33]"""
+    T, n = f["time"].size, f["contact"].shape[1]
+    d_c = ctx.alloc((T * 4, n)).upload(np.ascontiguousarray(f["contact"].transpose(0, 2, 1)).reshape(T * 4, n))
+    d_state = ctx.alloc((33, n)).upload(np.full((33, n), np.nan, np.float32))           # reset = 2 must not depend on what was there
+    d_out = ctx.alloc((T * 41, n)); d_ratio = ctx.alloc((T * 8, n))
+    d_vmc = ctx.alloc((T * 37, n)).upload(np.full((T * 37, n), -7.0, np.float32))
+    row = 4 * n                                                                          # bytes
+    for k in range(T):
+        o, r, v = (d_out.ptr + k * 41 * row, d_ratio.ptr + k * 8 * row, d_vmc.ptr + k * 37 * row) if optional else (None, None, None)
+        ctx.walk_gait_update_batch(n, f["cfg"], float(f["time"][k]), d_c.ptr + k * 4 * row, d_state, o, r, v, stop=bool(f["stop"][k]),
+                                   reset=2 if k == 0 else int(f["reset"][k]))
+    ctx.sync()
+    back = lambda d, rows: d.download().reshape(T, rows, n).transpose(2, 0, 1)
+    res = (back(d_out, 41), back(d_ratio, 8), back(d_vmc, 37)) if optional else (None, None, None)
+    state = d_state.download().T.copy()
+    for v in (d_c, d_state, d_out, d_ratio, d_vmc):
+        v.free()
+    return res + (state,)
+
+
+@pytest.mark.parametrize("name", R.FAMILIES)
+def test_kernel_is_the_model_on_every_tick(gpu_ctx, pkg, name):
+    """Every tick of every robot of every family of tests/walk_ref.py, bit for bit: the 41 output rows, d_ratio, the contact rows of d_vmc_in
+    (and nothing else of it), the generators' memory at the end -- which is the same bits when the optional outputs are not asked for."""
+    f, want, wst, _ = R.expected(pkg, name)
+    out, ratio, vmc, state = kernel_run(gpu_ctx, pkg, f)
+    bad = np.argwhere((out != want).any(axis=2))
+    assert bad.size == 0, (name, bad[:3], out[tuple(bad[0])], want[tuple(bad[0])])
+    assert np.array_equal(ratio, want[:, :, 33:41]) and np.array_equal(vmc[:, :, 18:22], want[:, :, 29:33])
+    assert np.all(vmc[:, :, :18] == -7.0) and np.all(vmc[:, :, 22:] == -7.0)
+    assert np.array_equal(state, wst[:, -1])
+    _, _, _, bare = kernel_run(gpu_ctx, pkg, f, optional=False)
+    assert bare.tobytes() == state.tobytes()
