@@ -810,6 +810,104 @@ int qrgpu_plant_step_body_batch(qrgpu_ctx *ctx, int n, const qrgpu_plant_params 
                                 const float *d_motor_cmd, float *d_plant_out, float *d_terrain_out, float *d_body_out, float *d_mpc_state,
                                 float *d_est_in, int *d_status);
 
+/* ---- episodes: per-robot termination, reset and spawn on the device ---------------------------------------------------------------------------
+ * qrgpu_episode_step_batch decides for every robot whether its episode ends at this call and, where it does, closes the episode's statistics and
+ * writes the robot's next spawn into d_fb_state -- no host copy, no host decision.  One memset (of d_done_count) and one launch on the context's
+ * stream.  It changes no other call.
+ *
+ * Termination: d_done [n] gets the robot's QRGPU_EP_* reason bits, every call; (d_done & QRGPU_EP_REASONS) == 0: the episode goes on.  All bits
+ * that apply are set.
+ *   EP_STATUS       d_plant_status[r] & status_mask was non-zero at this and the previous status_ticks - 1 calls (a per-robot counter in
+ *                   d_ep_state debounces it; the counter is cleared by a call that finds the masked status 0).  NULL array: never.
+ *   EP_TICK_STATUS  d_tick_status[r] & tick_mask is non-zero.  NULL array: never.
+ *   EP_NONFINITE    one of the robot's 37 d_fb_state rows is not finite.  Judged here, on the rows themselves.  The four geometric tests below are
+ *                   then not made (their bits stay 0): no comparison with a NaN decides a bit.
+ *   EP_TILT         R_zz = 1 - 2 (q_x^2 + q_y^2) / |q|^2 (fp64) < cos(tilt_max); tilt_max >= pi (as a float): never.  A zero quaternion is read as the identity, as
+ *                   the plant reads it.
+ *   EP_HEIGHT       base z - ground height under the base origin < min_clearance; ground height = the robot's field sampled at the base x, y
+ *                   (the sampler of qrgpu_plant_step_terrain_batch) + params->ground_z; without a terrain, params->ground_z (params NULL: 0).
+ *   EP_OFF_FIELD    with a terrain only: the base x, y lies outside [x0 + field_margin, x0 + (nx - 1) cell - field_margin] x (the same in y).
+ *   EP_TIMEOUT      the episode's tick count has reached max_ticks (0: never).  A truncation, not a failure.  The count is the number of calls
+ *                   since the one that spawned the episode, this one included: with one plant step between calls, the plant steps it ran.
+ *   EP_FORCED       d_force_reset[r] != 0 (NULL array: never), and every robot of a call with reset_all != 0.
+ *   QRGPU_EP_BAD_FIELD is no reason: with a terrain, d_field_id[r] outside 0..n_fields-1 -- field 0 was used (the rule of QRGPU_PL_BAD_FIELD).
+ *
+ * Random numbers: Philox-4x32-10, key (seed, robot index), counter (episode index, block k, 0, 0); uniform u = (word >> 8) 2^-24 in [0, 1), exact
+ * in float, widened to fp64; s = 2 u - 1.  A spawn depends on (seed, robot, episode index) alone -- not on n, the launch or the history.
+ * Draw order:  block 0: words 0..3 = spawn-table row, dx, dy, dyaw;  block 1: words 0, 1 = v_x, v_y (2, 3 unused);  block 2 + b, word j = joint
+ * 4 b + j (b = 0..2).
+ *
+ * Spawn, from d_spawn [4][n_spawn] (rows x, y, yaw, reserved):  row = min(floor(u n_spawn), n_spawn - 1);  x = x_row + xy_jitter s, y likewise,
+ * yaw = yaw_row + yaw_jitter s.  Ground height z_g and unit normal nrm of the robot's field at (x, y) as above (no terrain: ground_z, (0, 0, 1)).
+ * Base position (x, y, z_g) + spawn_height nrm.  Attitude: align_to_slope != 0: q_tilt (x) q_yaw with q_tilt = (1 + nrm_z, -nrm_y, nrm_x, 0) /
+ * |.| (the shortest rotation of e_z onto nrm: the base z axis is nrm) and q_yaw = (cos yaw/2, 0, 0, sin yaw/2); otherwise q_yaw.  Written
+ * normalised with w >= 0.  Joints q_spawn[j] + q_jitter s; v_body x, y = v_jitter s; every other velocity 0.
+ *
+ * Bookkeeping.  d_ep_state [QRGPU_EPISODE_STATE_ROWS][n] int32: 0 ticks in this episode, 1 episode index, 2 status debounce counter, 3 reason of
+ * the last episode ended, 4 episodes ended with any bit other than EP_TIMEOUT, 5 episodes ended by EP_TIMEOUT alone.
+ * d_ep_stats [QRGPU_EPISODE_STATS_ROWS][n] float: 0-3 spawn x, y, z, yaw of the running episode (the base position written); of the last
+ * episode ended: 4 its length in ticks, 5, 6 its world displacement x - spawn x, y - spawn y (0 for a robot with EP_NONFINITE), 7 its minimum
+ * clearance; 8 the running minimum of the clearance judged at each call (started at spawn_height; a call with EP_NONFINITE leaves it).
+ * reset_all != 0: every robot starts episode 0 as on fresh arrays -- rows zeroed, spawned, d_done = EP_FORCED, nothing closed or counted; what
+ * d_ep_state, d_ep_stats and d_fb_state held is not read.  The first call on new arrays is such a call -- or the caller, who wants the
+ * robots to start where they stand, zeroes d_ep_state and writes rows 0-3 and 8 of d_ep_stats itself.
+ *
+ * A robot that is reset gets: its 37 d_fb_state rows; d_prev_ori rows 0 (if given); its d_motor_cmd column (if given) as a joint PD hold at the
+ * joints drawn: p = q, Kp = kp, d = 0, Kd = kd, tua = 0 -- the next plant step does not apply a torque computed for the fallen pose.  Of a robot
+ * that is not reset only rows 0 and 2 of d_ep_state and row 8 of d_ep_stats are written.
+ * d_done_list [n] (may be NULL): the indices of the robots reset in this call; d_done_count [1]: how many (required with d_done_list, may be given
+ * alone).  THE ORDER OF THE LIST IS UNSPECIFIED across wavefronts (ascending inside one): each wavefront with a reset claims its span with one
+ * atomic add.
+ *
+ * Contracts.
+ *   Order: the intended loop is episode step, plant step, tick.  The plant step that follows a reset writes mpc_state, est_in and plant_out of
+ *     the new state, so this call writes none of them; a robot's first tick after a reset is computed from its post-reset state.
+ *   Warm start: a robot's stored MPC working set is not cleared: it is speed only (qrgpu_set_warm_start), a stale set leaves row by row.
+ *   Overlapped ticks: this call is "another launch of the context" -- the next tick is not chained (qrgpu_set_tick_overlap, rule 2).  It does not
+ *     touch the hand-over words of prev_ori.
+ *   Out of scope: the stage kernels (gait, swing, estimator) take a scalar reset, not a per-robot one; d_done is the mask such a change would take.
+ * QRGPU_ERR_BAD_ARG (nothing launched; qrgpu_last_error names the argument): n < 1 or n > max_batch; NULL desc, d_fb_state, d_ep_state,
+ * d_ep_stats, d_done or d_spawn; n_spawn < 1; a terrain the terrain call would refuse (nx or ny < 2, n_fields < 1, cell <= 0 or not finite, x0 or y0 not finite), or a terrain without
+ * d_height; d_done_list without
+ * d_done_count; status_ticks < 1, max_ticks < 0; a negative or non-finite tilt_max, min_clearance, field_margin, spawn_height, jitter, kp or kd;
+ * a non-finite q_spawn. */
+#define QRGPU_EP_STATUS       0x1
+#define QRGPU_EP_TICK_STATUS  0x2
+#define QRGPU_EP_NONFINITE    0x4
+#define QRGPU_EP_TILT         0x8
+#define QRGPU_EP_HEIGHT       0x10
+#define QRGPU_EP_OFF_FIELD    0x20
+#define QRGPU_EP_TIMEOUT      0x40
+#define QRGPU_EP_FORCED       0x80
+#define QRGPU_EP_REASONS      0xff          /* a robot is reset when (d_done & QRGPU_EP_REASONS) != 0 */
+#define QRGPU_EP_BAD_FIELD    0x01000000    /* not a reason: d_field_id outside the stack, field 0 was used */
+#define QRGPU_EPISODE_STATE_ROWS 6
+#define QRGPU_EPISODE_STATS_ROWS 9
+struct qrgpu_episode_desc {
+    int   status_mask;          /* QRGPU_PL_* bits of d_plant_status that end an episode */
+    int   status_ticks;         /* ... after this many consecutive calls, >= 1 */
+    int   tick_mask;            /* bits of d_tick_status that end an episode */
+    int   max_ticks;            /* 0 = no timeout */
+    unsigned seed;
+    int   align_to_slope;
+    float tilt_max;             /* rad */
+    float min_clearance;        /* m */
+    float field_margin;         /* m */
+    float spawn_height;         /* m, along the ground's normal */
+    float xy_jitter, yaw_jitter, q_jitter, v_jitter;     /* +- m, rad, rad, m/s */
+    float q_spawn[12];
+    float kp, kd;               /* the PD hold written into d_motor_cmd */
+};
+typedef struct qrgpu_episode_desc qrgpu_episode_desc;
+/* PL_NONFINITE | PL_QUAT_ZERO | PL_TRUNK_CONTACT, 1, 0, 0, seed 1, level, 1.0, 0.10, 0, 0.30, jitters 0, (0, 0.8, -1.6) per leg, 100, 2 */
+void qrgpu_episode_desc_default(qrgpu_episode_desc *d);
+int  qrgpu_episode_step_batch(qrgpu_ctx *ctx, int n, const qrgpu_episode_desc *desc, int reset_all, const qrgpu_plant_params *params,
+                              const qrgpu_terrain_desc *terrain /* NULL = flat at ground_z */, const float *d_height,
+                              const int *d_field_id /* [n], NULL = field 0 */, const float *d_spawn /* [4][n_spawn] */, int n_spawn,
+                              const int *d_plant_status, const int *d_tick_status, const int *d_force_reset, float *d_fb_state,
+                              float *d_prev_ori, float *d_motor_cmd, int *d_ep_state, float *d_ep_stats, int *d_done, int *d_done_list,
+                              int *d_done_count);
+
 /* ---- multi-GPU: all-gather of the per-robot torques over RCCL / xGMI ----------------------------------------
  * One process per GPU, one context per process; rank r of N owns a contiguous shard of the robot population and there is no exchange
  * inside a tick.  The only collective of the path collects every rank's tau[12][n_local] on every rank:

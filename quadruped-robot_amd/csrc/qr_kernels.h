@@ -89,4 +89,10 @@ __global__ void qr_plant_step_body_kernel(int n, qrgpu_plant_params P, qrgpu_ter
                                           const int *type_id, int type_ready, const float *g_height, const int *g_field, const float *g_push, float *g_state,
                                           const float *g_cmd, float *g_out, float *g_tout, float *g_bout, float *g_mpc, float *g_est, int *g_status);
 
+// qr_episode_kernel.hip: one lane per robot; termination, statistics, spawn, the list of the robots reset
+__global__ void qr_episode_kernel(int n, qrgpu_episode_desc D, double cos_tilt, int reset_all, float ground_z, int has_terrain, qrgpu_terrain_desc T,
+                                  const float *g_height, const int *g_field, const float *g_spawn, int n_spawn, const int *g_pstatus, const int *g_tstatus,
+                                  const int *g_force, float *g_state, float *g_prev, float *g_cmd, int *g_st, float *g_stats, int *g_done, int *g_list,
+                                  int *g_count);
+
 }  // namespace qrgpu

@@ -8,6 +8,7 @@
 #include <cstring>
 
 #include "qrgpu_ctx.h"
+#include "qr_episode.h"
 
 // One launch of a stage kernel on the context's stream.
 template <typename... KArgs, typename... Args>
@@ -429,6 +430,64 @@ int qrgpu_plant_step_body_batch(qrgpu_ctx *c, int n, const qrgpu_plant_params *p
     return launch_stage(c, qr_plant_step_body_kernel, per_quad(n), dim3(64), n, *params, *terrain, (const WbcConst *)c->d_wbc, (const qrgpu_plant_body_desc *)c->d_body,
                         d_type_id, ready_mask(c->wbc_ready), d_height, d_field_id, d_base_push, d_fb_state, d_motor_cmd, d_plant_out, d_terrain_out, d_body_out,
                         d_mpc_state, d_est_in, d_status);
+}
+
+void qrgpu_episode_desc_default(qrgpu_episode_desc *d)
+{   // spawn height, stand pose and settle gains of tools/closed_loop.py
+    if (!d) return;
+    memset(d, 0, sizeof(*d));
+    d->status_mask = QRGPU_PL_NONFINITE | QRGPU_PL_QUAT_ZERO | QRGPU_PL_TRUNK_CONTACT; d->status_ticks = 1;
+    d->seed = 1u;
+    d->tilt_max = 1.0f; d->min_clearance = 0.10f; d->spawn_height = 0.30f;
+    for (int l = 0; l < 4; ++l) { d->q_spawn[3 * l] = 0.f; d->q_spawn[3 * l + 1] = 0.8f; d->q_spawn[3 * l + 2] = -1.6f; }
+    d->kp = 100.f; d->kd = 2.f;
+}
+
+// BAD_ARG with the argument's name in qrgpu_last_error
+static int bad_arg(qrgpu_ctx *c, const char *what)
+{
+    if (c) c->err = std::string("qrgpu_episode_step_batch: ") + what;
+    return QRGPU_ERR_BAD_ARG;
+}
+
+int qrgpu_episode_step_batch(qrgpu_ctx *c, int n, const qrgpu_episode_desc *desc, int reset_all, const qrgpu_plant_params *params, const qrgpu_terrain_desc *terrain,
+                             const float *d_height, const int *d_field_id, const float *d_spawn, int n_spawn, const int *d_plant_status, const int *d_tick_status,
+                             const int *d_force_reset, float *d_fb_state, float *d_prev_ori, float *d_motor_cmd, int *d_ep_state, float *d_ep_stats, int *d_done,
+                             int *d_done_list, int *d_done_count)
+{
+    if (!c) return QRGPU_ERR_BAD_ARG;
+    if (!batch_ok(c, n)) return bad_arg(c, "n");
+    if (!desc) return bad_arg(c, "desc");
+    if (!d_fb_state) return bad_arg(c, "d_fb_state");
+    if (!d_ep_state) return bad_arg(c, "d_ep_state");
+    if (!d_ep_stats) return bad_arg(c, "d_ep_stats");
+    if (!d_done) return bad_arg(c, "d_done");
+    if (!d_spawn) return bad_arg(c, "d_spawn");
+    if (n_spawn < 1) return bad_arg(c, "n_spawn");
+    if (d_done_list && !d_done_count) return bad_arg(c, "d_done_count");
+    qrgpu_terrain_desc T;
+    memset(&T, 0, sizeof(T));
+    if (terrain) {
+        if (terrain->nx < 2 || terrain->ny < 2 || terrain->n_fields < 1 || !(terrain->cell > 0.f) || !std::isfinite(terrain->cell) || !std::isfinite(terrain->x0) ||
+            !std::isfinite(terrain->y0)) return bad_arg(c, "terrain");
+        if (!d_height) return bad_arg(c, "d_height");
+        T = *terrain;
+    }
+    if (desc->status_ticks < 1) return bad_arg(c, "status_ticks");
+    if (desc->max_ticks < 0) return bad_arg(c, "max_ticks");
+    const struct { const char *name; float v; } nonneg[] = {{"tilt_max", desc->tilt_max}, {"min_clearance", desc->min_clearance}, {"field_margin", desc->field_margin},
+        {"spawn_height", desc->spawn_height}, {"xy_jitter", desc->xy_jitter}, {"yaw_jitter", desc->yaw_jitter}, {"q_jitter", desc->q_jitter},
+        {"v_jitter", desc->v_jitter}, {"kp", desc->kp}, {"kd", desc->kd}};
+    for (const auto &a : nonneg) if (!std::isfinite(a.v) || !(a.v >= 0.f)) return bad_arg(c, a.name);
+    for (int k = 0; k < 12; ++k) if (!std::isfinite(desc->q_spawn[k])) return bad_arg(c, "q_spawn");
+    const float ground_z = params ? params->ground_z : 0.f;
+    if (!std::isfinite(ground_z)) return bad_arg(c, "params->ground_z");
+    c->ov_chain = false;                                             // another launch of the context: the next overlapped tick is not chained
+    HIPCHK(c, hipSetDevice(c->device));
+    if (d_done_count) HIPCHK(c, hipMemsetAsync(d_done_count, 0, sizeof(int), c->stream));
+    return launch_stage(c, qr_episode_kernel, per_robot(n), dim3(64), n, *desc, episode::cos_tilt_of(desc->tilt_max), reset_all != 0 ? 1 : 0, ground_z, terrain ? 1 : 0, T,
+                        d_height, d_field_id, d_spawn, n_spawn, d_plant_status, d_tick_status, d_force_reset, d_fb_state, d_prev_ori, d_motor_cmd, d_ep_state,
+                        d_ep_stats, d_done, d_done_list, d_done_count);
 }
 
 }  // extern "C"

@@ -58,11 +58,11 @@ def _set_fields(d, fields):
             raise AttributeError("%s has no field %r" % (type(d).__name__, name))
         t = ctype_of[name]
         if issubclass(t, C.Array):
-            conv = int if issubclass(t._type_, C.c_int) else float
+            conv = int if issubclass(t._type_, (C.c_int, C.c_uint)) else float
             arr = getattr(d, name)
             for k, x in enumerate(v): arr[k] = conv(x)
         else:
-            setattr(d, name, (int if issubclass(t, C.c_int) else float)(v))
+            setattr(d, name, (int if issubclass(t, (C.c_int, C.c_uint)) else float)(v))
     return d
 
 
@@ -228,6 +228,26 @@ def plant_body_desc(robot="a1", **fields):
     return _set_fields(_set_fields(d, PLANT_BODY[robot]), fields)
 
 
+EP_STATUS, EP_TICK_STATUS, EP_NONFINITE, EP_TILT, EP_HEIGHT, EP_OFF_FIELD, EP_TIMEOUT, EP_FORCED = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20, 0x40, 0x80
+EP_REASONS, EP_BAD_FIELD = 0xff, 0x01000000
+EPISODE_STATE_ROWS, EPISODE_STATS_ROWS = 6, 9
+
+
+class episode_desc_struct(C.Structure):
+    _fields_ = [("status_mask", C.c_int), ("status_ticks", C.c_int), ("tick_mask", C.c_int), ("max_ticks", C.c_int), ("seed", C.c_uint),
+                ("align_to_slope", C.c_int), ("tilt_max", C.c_float), ("min_clearance", C.c_float), ("field_margin", C.c_float),
+                ("spawn_height", C.c_float), ("xy_jitter", C.c_float), ("yaw_jitter", C.c_float), ("q_jitter", C.c_float), ("v_jitter", C.c_float),
+                ("q_spawn", C.c_float * 12), ("kp", C.c_float), ("kd", C.c_float)]
+
+
+def episode_desc(**fields):
+    """qrgpu_episode_desc: the library's defaults (a fall is PL_NONFINITE | PL_QUAT_ZERO | PL_TRUNK_CONTACT for one call, a tilt beyond 1 rad or a
+    clearance under 0.10 m; spawn 0.30 above the ground at the stand pose, no jitter, no timeout, seed 1), with any field overridden."""
+    d = episode_desc_struct()
+    load_library().qrgpu_episode_desc_default(C.byref(d))
+    return _set_fields(d, fields)
+
+
 EPILOGUE_HIP_COMP, EPILOGUE_CLIP = 1, 2
 COMM_ID_BYTES = 128
 
@@ -260,7 +280,8 @@ EXPORTS = ["qrgpu_model_desc_default", "qrgpu_create", "qrgpu_destroy", "qrgpu_s
            "qrgpu_tick_fence", "qrgpu_tick_overlap_stats", "qrgpu_swing_mode_desc_default", "qrgpu_swing_update_batch", "qrgpu_swing_action_batch",
            "qrgpu_stance_desc_default", "qrgpu_stance_update_batch", "qrgpu_stance_command_batch", "qrgpu_stance_tick_batch",
            "qrgpu_pose_plan_desc_default", "qrgpu_pose_plan_batch", "qrgpu_plant_params_default", "qrgpu_forward_dynamics_batch", "qrgpu_plant_step_batch",
-           "qrgpu_plant_step_terrain_batch", "qrgpu_plant_body_desc_default", "qrgpu_plant_body_setup", "qrgpu_plant_step_body_batch"]
+           "qrgpu_plant_step_terrain_batch", "qrgpu_plant_body_desc_default", "qrgpu_plant_body_setup", "qrgpu_plant_step_body_batch",
+           "qrgpu_episode_desc_default", "qrgpu_episode_step_batch"]
 
 
 def load_library():
@@ -344,6 +365,8 @@ def load_library():
     lib.qrgpu_plant_body_desc_default.argtypes = [C.POINTER(plant_body_desc_struct)]; lib.qrgpu_plant_body_desc_default.restype = None
     lib.qrgpu_plant_body_setup.argtypes = [vp, ip, C.POINTER(plant_body_desc_struct)]
     lib.qrgpu_plant_step_body_batch.argtypes = [vp, ip, C.POINTER(plant_params_struct), C.POINTER(terrain_desc_struct)] + [vp] * 12
+    lib.qrgpu_episode_desc_default.argtypes = [C.POINTER(episode_desc_struct)]; lib.qrgpu_episode_desc_default.restype = None
+    lib.qrgpu_episode_step_batch.argtypes = [vp, ip, C.POINTER(episode_desc_struct), ip, C.POINTER(plant_params_struct), C.POINTER(terrain_desc_struct), vp, vp, vp, ip] + [vp] * 11
     lib.qrgpu_vmc_force1.argtypes = [vp, ip, fp, fp, fp, fp, C.POINTER(ip)]
     lib.qrgpu_vmc_force_world1.argtypes = [vp, ip, fp, fp, fp, fp, fp, C.POINTER(ip)]
     lib.qrgpu_mpc_frontend_batch.argtypes = [vp, ip, ip, C.c_float, C.c_float] + [vp] * 6
@@ -760,6 +783,20 @@ class Context:
         self._chk(self._lib.qrgpu_plant_step_body_batch(self._h, n, C.byref(params), C.byref(terrain), _dp(height), _dp(field_id), _dp(base_push),
                                                         _dp(type_id), _dp(fb_state), _dp(motor_cmd), _dp(plant_out), _dp(terrain_out), _dp(body_out),
                                                         _dp(mpc_state), _dp(est_in), _dp(status)))
+
+    def episode_step_batch(self, n, desc, fb_state, spawn, n_spawn, ep_state, ep_stats, done, reset_all=False, params=None, terrain=None, height=None,
+                           field_id=None, plant_status=None, tick_status=None, force_reset=None, prev_ori=None, motor_cmd=None, done_list=None,
+                           done_count=None):
+        """Per-robot termination, reset and spawn (desc: episode_desc()): done [n] gets each robot's EP_* reason bits; a robot whose episode ends
+        is spawned from the table spawn [4][n_spawn] (x, y, yaw, reserved) into fb_state [37][n], with prev_ori [3][n] zeroed and its motor_cmd
+        [60][n] column set to a joint PD hold (both optional).  ep_state [EPISODE_STATE_ROWS][n] int32 and ep_stats [EPISODE_STATS_ROWS][n] carry
+        the bookkeeping; reset_all starts every robot at episode 0 (the first call on new arrays).  terrain / height / field_id as in
+        plant_step_terrain_batch (None: flat at params.ground_z; params None: 0).  done_list [n], done_count [1] int32: the robots reset, compacted,
+        in no fixed order.  Intended loop: episode step, plant step, tick."""
+        self._chk(self._lib.qrgpu_episode_step_batch(self._h, n, C.byref(desc), int(bool(reset_all)), None if params is None else C.byref(params),
+                                                     None if terrain is None else C.byref(terrain), _dp(height), _dp(field_id), _dp(spawn), int(n_spawn),
+                                                     _dp(plant_status), _dp(tick_status), _dp(force_reset), _dp(fb_state), _dp(prev_ori), _dp(motor_cmd),
+                                                     _dp(ep_state), _dp(ep_stats), _dp(done), _dp(done_list), _dp(done_count)))
 
     def mpc_frontend_batch(self, n, fe_in, fe_state, traj, gait, wbc_cmd=None, mpc_updated=None, num_horizon_l=2, dt_ctrl=0.002, dt_mpc=0.06):
         """SetupCommand + Run + UpdateMPC (without the solve) of n robots: qr_mpc_stance_leg_controller.cpp:158-382."""

@@ -6,6 +6,7 @@ inside the loop.
   rocprofv3 --kernel-trace --stats -d DIR -- python tools/closed_loop.py --profile    the same loop as the workload of a kernel trace
   python tools/closed_loop.py --terrain plane:0.2 [--push 30]                         the same loop on a height field, with a push on the base
   python tools/closed_loop.py --body [--terrain stairs:0.04] [--push 30]              the same loop with knee and trunk contact and joint limits
+  python tools/closed_loop.py --episodes [--max-ticks 400] [--terrain plane:0.2]      episode step -> plant -> tick: robots that fall start again
 
 The robots are dropped from z = 0.30 onto joint PD at the stand pose (400 ticks of 1 ms), shoved by up to 0.3 m/s in x and y, and handed to
 MPC + WBC: qrgpu_plant_step_batch (include/qrgpu.h) writes the ground-truth mpc_state and fb_state the tick reads, and the tick -- the plain
@@ -19,10 +20,21 @@ controller's trajectory and command stay the level ones: what it makes of a pitc
 the run is the flat one.  --body runs the settle phase and the loop through qrgpu_plant_step_body_batch (on the flat field unless --terrain names
 another): a robot that loses its footing comes to rest on knees and trunk instead of sinking through the ground, and is counted.
 
+--episodes (implies --body) puts qrgpu_episode_step_batch in front of every plant step of the loop, warm-up included: a robot whose trunk touches
+the ground, that tilts beyond 1 rad, sinks under 0.10 m of clearance, leaves the field (margin 0.2 m) or -- with --max-ticks N -- has run N ticks is
+spawned again on the device at spawn height 0.30 on a 3 x 3 grid of points around the field's centre (--spawn-spread, default 0.05 m between
+points: the controller's command holds the origin, so a wide grid would measure the WBC's position task, not the episode layer), aligned with the
+slope on a plane, with the run's shove as its spawn velocity, on the joint PD hold the call writes (the tick's torque is added to it, as the motor law
+adds them).  Episode 0 is the settled, shoved state of the other runs: nothing is spawned before the first fall.  Without the option the tool runs
+exactly what it ran.
+
   ticks_per_s   closed-loop control ticks per second: every robot advances one tick per (plant step + controller tick)
   in_band       share of the robots that end inside the stand band: |z - 0.27| <= 0.01, |x|, |y| <= 0.03, |roll|, |pitch| <= 0.03
   fallen        (--body) robots that raised PL_TRUNK_CONTACT or PL_KNEE_CONTACT at any tick of the loop, warm-up included
   nonfinite     robots whose state left the finite numbers
+  episodes_finished, by_reason, mean_episode_ticks   (--episodes) episodes ended in the loop, warm-up included; how often each EP_* bit was among the
+                reasons; their mean length in ticks
+  alive_at_end  (--episodes) share of the robots that are finite, within 0.5 rad of level and off their knees and trunk at the last tick
 """
 import argparse
 import importlib.util
@@ -61,8 +73,12 @@ def main():
     ap.add_argument("--terrain", default=None, metavar="KIND[:ARG]", help="run on a height field: flat, plane:0.2, stairs:0.04, gap:0.1, rough:0.01")
     ap.add_argument("--push", type=float, default=0.0, metavar="N", help="world-frame force along +x on every base during the timed loop, newtons")
     ap.add_argument("--body", action="store_true", help="knee and trunk contact and joint limits: qrgpu_plant_step_body_batch")
+    ap.add_argument("--episodes", action="store_true", help="per-robot termination and respawn on the device: qrgpu_episode_step_batch (implies --body)")
+    ap.add_argument("--max-ticks", type=int, default=0, metavar="N", help="(--episodes) truncate an episode after N ticks; 0 = never")
+    ap.add_argument("--spawn-spread", type=float, default=0.05, metavar="M", help="(--episodes) spacing of the 3 x 3 grid of spawn points, metres")
     ap.add_argument("--profile", action="store_true", help="the run a profiler traces: fewer ticks, nothing else changed")
     a = ap.parse_args()
+    a.body = a.body or a.episodes
     pkg = _load_pkg()
     pkg._build.build()
     n, h = a.robots, HORIZON
@@ -95,6 +111,15 @@ def main():
         d["bout"] = ctx.alloc((pkg.qrgpu.BODY_OUT_ROWS, n))
         d["status_log"] = ctx.alloc((ticks + 20, n), np.int32).zero()        # every tick's plant status: read once, after the loop
 
+    if a.episodes:
+        q = pkg.qrgpu
+        cx, cy = grid.x0 + 0.5 * (grid.nx - 1) * grid.cell, grid.y0 + 0.5 * (grid.ny - 1) * grid.cell
+        gx, gy = np.meshgrid(cx + a.spawn_spread * np.arange(-1, 2), cy + a.spawn_spread * np.arange(-1, 2))
+        table = np.zeros((4, 9), np.float32); table[0] = gx.ravel(); table[1] = gy.ravel()
+        edesc = pkg.episode_desc(max_ticks=a.max_ticks, seed=a.seed, align_to_slope=int(kind == "plane"), field_margin=0.2, v_jitter=0.3)
+        d.update(table=ctx.alloc((4, 9)).upload(table), ep_state=ctx.alloc((q.EPISODE_STATE_ROWS, n), np.int32).zero(), ep_stats=ctx.alloc((q.EPISODE_STATS_ROWS, n)),
+                 done_log=ctx.alloc((ticks + 20, n), np.int32).zero(), done_list=ctx.alloc((n,), np.int32), done_count=ctx.alloc((1,), np.int32))
+
     def plant(par, **out):
         if a.body:
             ctx.plant_step_body_batch(n, par, tdesc, d["height"], d["fb"], d["cmd"], base_push=d["push"], terrain_out=d["tout"], body_out=d["bout"], **out)
@@ -119,9 +144,16 @@ def main():
     tau = d["cmd"].row(48)
 
     done = [0]
+    if a.episodes:      # episode 0 is the state at hand: its spawn rows written here, not drawn
+        stats = np.zeros((pkg.qrgpu.EPISODE_STATS_ROWS, n), np.float32); stats[0:3] = fb[4:7]; stats[8] = 0.30
+        d["ep_stats"].upload(stats)
 
     def loop(k):
         for _ in range(k):
+            if a.episodes:
+                ctx.episode_step_batch(n, edesc, d["fb"], d["table"], 9, d["ep_state"], d["ep_stats"], d["done_log"].row(done[0]), params=params, terrain=tdesc,
+                                       height=d["height"], plant_status=d["status_log"].row(done[0] - 1) if done[0] else None, tick_status=None,
+                                       prev_ori=d["prev"], motor_cmd=d["cmd"], done_list=d["done_list"], done_count=d["done_count"])
             plant(params, plant_out=d["out"], mpc_state=d["mpc"], status=d["status_log"].row(done[0]) if a.body else d["plant_status"])
             done[0] += 1
             ctx.tick_batch(n, d["mpc"], d["traj"], d["gait"], d["fb"], d["wcmd"], d["prev"], d["force"], tau, d["tick_status"])
@@ -152,6 +184,20 @@ def main():
         seen = np.bitwise_or.reduce(log, axis=0)
         res.update(body=True, fallen=int(((seen & (q.PL_TRUNK_CONTACT | q.PL_KNEE_CONTACT)) != 0).sum()), at_a_stop=int(((seen & q.PL_JOINT_LIMIT) != 0).sum()),
                    fallen_at_end=int(((plant_flags & (q.PL_TRUNK_CONTACT | q.PL_KNEE_CONTACT)) != 0).sum()))
+    if a.episodes:
+        q = pkg.qrgpu
+        dl = d["done_log"].download() & q.EP_REASONS
+        st = d["ep_state"].download()
+        names = ("status", "tick_status", "nonfinite", "tilt", "height", "off_field", "timeout", "forced")
+        lengths = []
+        for r in range(n):                                              # episode lengths from the log of reason words: ticks between a robot's ends
+            t = np.nonzero(dl[:, r])[0]
+            lengths.extend(np.diff(np.concatenate([[-1], t])).tolist())
+        fell = (plant_flags & (q.PL_TRUNK_CONTACT | q.PL_KNEE_CONTACT)) != 0
+        alive = np.isfinite(fb).all(0) & (np.nan_to_num(np.abs(rp).max(1), nan=9.0) < 0.5) & ~fell
+        res.update(episodes=True, max_ticks=a.max_ticks, episodes_finished=int(st[4].sum() + st[5].sum()), episodes_failed=int(st[4].sum()),
+                   episodes_timed_out=int(st[5].sum()), by_reason={nm: int(((dl >> k) & 1).sum()) for k, nm in enumerate(names)},
+                   mean_episode_ticks=float(np.mean(lengths)) if lengths else None, alive_at_end=float(alive.mean()))
     print(json.dumps(res))
     ctx.close()
 
