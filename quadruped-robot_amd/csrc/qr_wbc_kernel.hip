@@ -176,10 +176,22 @@ __device__ __forceinline__ void psd_pinv(int lane, const real *W, int n, real th
         }
         // Winv = V diag(1/l if l > thr) V^T   (singular values of a PSD matrix are |eigenvalues|)
         real *ev = scr + n * n;
+        // (rolled loops: unrolled for the compile-time n of the contact level, this rare path sets the kernel's register demand and spills)
+#pragma unroll 1
         for (int i = 0; i < n; ++i) { const real l = fabs(Am[i * n + i]); ev[i] = (l > thr) ? 1.0 / Am[i * n + i] : 0.0; }
-        for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) Am[i * n + j] = V[i * n + j] * ev[j];      // V D
+#pragma unroll 1
+        for (int e = 0; e < n * n; ++e) { const int j = e % n; Am[e] = V[e] * ev[j]; }      // V D
         real *tmp = scr + n * n + n;   // n*n more
-        for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) { real a = 0; for (int k = 0; k < n; ++k) a += Am[i * n + k] * V[j * n + k]; tmp[i * n + j] = a; }
+#pragma unroll 1
+        for (int i = 0; i < n; ++i)
+#pragma unroll 1
+            for (int j = 0; j < n; ++j) {
+                real a = 0;
+#pragma unroll 1
+                for (int k = 0; k < n; ++k) a += Am[i * n + k] * V[j * n + k];
+                tmp[i * n + j] = a;
+            }
+#pragma unroll 1
         for (int e = 0; e < n * n; ++e) Winv[e] = tmp[e];
     }
     wave_sync();
@@ -260,27 +272,36 @@ __device__ __forceinline__ bool wbc_qp_setup(const int lane, const WbcConst &K, 
     real *tv = Q.tv, *Nq = Q.Nq, *Sq = Q.Sq, *qd_ = Q.qd_, *qx = Q.qx;
     const int nz = 6 + dimFr, np_ = 6, mi = 6 * nc;
     // gen (tv) = A qdd + C + G - Jc^T Fr_des  (all 18 rows; rows 6.. are reused for the torque): here without the last term
+    // (dot18's rule in this part: static trip counts, every load issued before the first use; one accumulator in the written order)
     if (lane < 18) {
+        real av[18], qv[18];
+#pragma unroll
+        for (int k = 0; k < 18; ++k) { av[k] = A[lane * 18 + k]; qv[k] = qdd[k]; }
         real acc = Cv[lane] + Gv[lane];
-        for (int k = 0; k < 18; ++k) acc += A[lane * 18 + k] * qdd[k];
+#pragma unroll
+        for (int k = 0; k < 18; ++k) acc += av[k] * qv[k];
         tv[lane] = acc;
     }
     // constraint normals Nq[c][0:nz]
-    for (int e = lane; e < (np_ + mi) * nz; e += 64) {
-        const int c = e / nz, j = e - c * nz;
-        real v = 0.0;
-        if (c < 6) v = (j < 6) ? A[c * 18 + j] : -JC[(j - 6) * 18 + c];
-        else {
-            const int u = c - 6, k = u / 6, tt = u - 6 * k;      // Uf row tt of contact k
-            if (j >= 6 && (j - 6) / 3 == k) {
-                const int ax = (j - 6) - 3 * k;
-                // Uf rows: [0 0 1] [1 0 mu] [-1 0 mu] [0 1 mu] [0 -1 mu] [0 0 -1]   (qr_single_contact.cpp:40-62)
-                if (tt == 0) v = (ax == 2) ? 1.0 : 0.0;
-                else if (tt == 5) v = (ax == 2) ? -1.0 : 0.0;
-                else { const int a2 = (tt - 1) >> 1; v = (ax == a2) ? (((tt - 1) & 1) ? -1.0 : 1.0) : ((ax == 2) ? (real)K.mu : 0.0); }
-            }
-        }
-        Nq[c * 18 + j] = v;
+    // (no division by the run-time nz: the six equality rows over 6 x 18 with constant divisors, columns past nz left alone; the inequality
+    //  rows zeroed as one contiguous range -- their columns past nz are never read -- and then the three entries each of them has)
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        const int e = lane + 64 * u, c = e / 18, j = e - 18 * c;
+        if (e < 108 && j < nz) Nq[e] = (j < 6) ? A[c * 18 + j] : -JC[(j - 6) * 18 + c];
+    }
+    for (int e = lane; e < 9 * mi; e += 64) { Nq[108 + 2 * e] = 0.0; Nq[108 + 2 * e + 1] = 0.0; }
+    wave_sync();
+    if (lane < mi) {
+        const int k = lane / 6, tt = lane - 6 * k;               // Uf row tt of contact k
+        // Uf rows: [0 0 1] [1 0 mu] [-1 0 mu] [0 1 mu] [0 -1 mu] [0 0 -1]   (qr_single_contact.cpp:40-62)
+        const int a2 = (tt - 1) >> 1;
+        const real sg = ((tt - 1) & 1) ? -1.0 : 1.0, ends = (tt == 0) ? 1.0 : -1.0;
+        const bool side = tt != 0 && tt != 5;
+        real *r = Nq + (6 + lane) * 18 + 6 + 3 * k;
+        r[0] = (side && a2 == 0) ? sg : 0.0;
+        r[1] = (side && a2 == 1) ? sg : 0.0;
+        r[2] = side ? (real)K.mu : ends;
     }
     if (lane < 18) qx[lane] = 0.0;        // g0 = 0  =>  unconstrained minimiser z = 0
     if (lane < 32) sI[32 + lane] = -1;    // constraint -> position or -1
@@ -290,8 +311,12 @@ __device__ __forceinline__ bool wbc_qp_setup(const int lane, const WbcConst &K, 
     const real iw_fb = 1.0 / (real)K.w_fb, iw_fr = 1.0 / (real)K.w_fr;
     if (lane < 36) {
         const int a = lane / 6, b2 = lane - 6 * a;
+        real av[18], bv[18];
+#pragma unroll
+        for (int j = 0; j < 18; ++j) { const bool ok = j < nz; av[j] = ok ? Nq[a * 18 + j] : 0.0; bv[j] = ok ? Nq[b2 * 18 + j] : 0.0; }      // (a term past nz adds +0)
         real acc = 0.0;
-        for (int j = 0; j < nz; ++j) acc += Nq[a * 18 + j] * ((j < 6) ? iw_fb : iw_fr) * Nq[b2 * 18 + j];
+#pragma unroll
+        for (int j = 0; j < 18; ++j) acc += av[j] * ((j < 6) ? iw_fb : iw_fr) * bv[j];
         Sq[a * 18 + b2] = acc;
     }
     wave_sync();
@@ -318,8 +343,12 @@ __device__ __forceinline__ void wbc_qp_and_store(const int lane, const int rid, 
     //   inequalities    :  Uf (Fr_des + z_f) - ineqVec >= 0
     const int nz = 6 + dimFr, np_ = 6, mi = 6 * nc;
     if (lane < 18) {
+        real jv[12], fv[12];
+#pragma unroll
+        for (int k = 0; k < 12; ++k) { const bool ok = k < dimFr; jv[k] = ok ? JC[k * 18 + lane] : 0.0; fv[k] = ok ? cm[51 + 3 * CLEG(k / 3) + k % 3] : 0.0; }
         real acc = tv[lane];
-        for (int k = 0; k < dimFr; ++k) acc -= JC[k * 18 + lane] * cm[51 + 3 * CLEG(k / 3) + k % 3];
+#pragma unroll
+        for (int k = 0; k < 12; ++k) acc -= jv[k] * fv[k];
         tv[lane] = acc;
     }
     wave_sync();
@@ -398,6 +427,14 @@ __device__ __forceinline__ void wbc_qp_and_store(const int lane, const int rid, 
                 // an inequality row touches the three force unknowns of one contact: its products are three terms, not a reduction
                 const int pj = 6 + 3 * ((p - 6) / 6);
                 const real pn0 = Nq[p * 18 + pj], pn1 = Nq[p * 18 + pj + 1], pn2 = Nq[p * 18 + pj + 2];
+                // Loads that wait for none of the reductions below are issued here, ahead of them: the operands of s_p, and the first six columns
+                // of this lane's row of S^-1 and of the working set's normals (q >= 6: the first chunk of either loop always runs).
+                const real qcp = qc0[p], qxp0 = qx[pj], qxp1 = qx[pj + 1], qxp2 = qx[pj + 2];
+                const real *Srow = Sq + ((lane < q) ? lane : 0) * 18;
+                const int lz = (lane < nz) ? lane : 0;
+                real sv0[6], nv0[6];
+#pragma unroll
+                for (int j = 0; j < 6; ++j) { sv0[j] = Srow[j]; nv0[j] = Nq[__builtin_amdgcn_readlane(act_r, j) * 18 + lz]; }
                 const real delta = (pn0 * pn0 + pn1 * pn1 + pn2 * pn2) * iw_fr;
                 // w = M n_p is iw_fr * n_p on those three unknowns and zero elsewhere
                 const real w0 = iw_fr * pn0, w1 = iw_fr * pn1, w2 = iw_fr * pn2;
@@ -406,13 +443,12 @@ __device__ __forceinline__ void wbc_qp_and_store(const int lane, const int rid, 
                 // r = S^-1 d: lane i walks row i, d_j by v_readlane
                 real rq_ = 0.0;
                 {
-                    const real *Srow = Sq + ((lane < q) ? lane : 0) * 18;
 #pragma unroll
                     for (int c = 0; c < 18; c += 6) {           // chunks of six columns, a chunk's loads in flight together
                         if (c >= q) continue;
                         real sv[6];
 #pragma unroll
-                        for (int j = 0; j < 6; ++j) sv[j] = Srow[c + j];                        // (row stride 18: in bounds; columns >= q are stale, masked below)
+                        for (int j = 0; j < 6; ++j) sv[j] = (c == 0) ? sv0[j] : Srow[c + j];                        // (row stride 18: in bounds; columns >= q are stale, masked below)
 #pragma unroll
                         for (int j = 0; j < 6; ++j) rq_ += (c + j < q) ? sv[j] * readlane_d(dq_, c + j) : 0.0;
                     }
@@ -426,7 +462,7 @@ __device__ __forceinline__ void wbc_qp_and_store(const int lane, const int rid, 
                     t1 = wave_min_d(tt);
                     lpos = (t1 < INF_) ? first_lane(tt == t1) : 0x7fffffff;
                 }
-                const real sp = qc0[p] + (pn0 * qx[pj] + pn1 * qx[pj + 1] + pn2 * qx[pj + 2]);
+                const real sp = qcp + (pn0 * qxp0 + pn1 * qxp1 + pn2 * qxp2);
                 const bool have_z = zc > 1e-13 * delta;
                 const real izc = fast_rcp(zc);
                 const real t2 = have_z ? -sp * izc : INF_;
@@ -435,13 +471,12 @@ __device__ __forceinline__ void wbc_qp_and_store(const int lane, const int rid, 
                 if (have_z) {
                     // z = w - M N r ; x += t z
                     real acc = 0.0;
-                    const int lz = (lane < nz) ? lane : 0;
 #pragma unroll
                     for (int c = 0; c < 18; c += 6) {
                         if (c >= q) continue;
                         real nv[6];
 #pragma unroll
-                        for (int j = 0; j < 6; ++j) nv[j] = Nq[__builtin_amdgcn_readlane(act_r, c + j) * 18 + lz];     // (lanes >= q hold act_r = 0: a valid row)
+                        for (int j = 0; j < 6; ++j) nv[j] = (c == 0) ? nv0[j] : Nq[__builtin_amdgcn_readlane(act_r, c + j) * 18 + lz];     // (lanes >= q hold act_r = 0: a valid row)
 #pragma unroll
                         for (int j = 0; j < 6; ++j) acc += (c + j < q) ? nv[j] * readlane_d(rq_, c + j) : 0.0;
                     }
@@ -502,9 +537,16 @@ __device__ __forceinline__ void wbc_qp_and_store(const int lane, const int rid, 
     // qddot[0:6] += z[0:6];  tau = (A qddot + C + G - Jc^T (Fr_des + z_f))[6:18]
     if (lane < 12) {
         const int row = 6 + lane;
+        real av[6], xv[6], jv[12], zv[12];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) { av[k] = A[row * 18 + k]; xv[k] = qx[k]; }
+#pragma unroll
+        for (int k = 0; k < 12; ++k) { const bool ok = k < dimFr; jv[k] = ok ? JC[k * 18 + row] : 0.0; zv[k] = ok ? qx[6 + k] : 0.0; }
         real acc = tv[row];                                  // (A qdd_cmd + C + G - Jc^T Fr_des)[row]
-        for (int k = 0; k < 6; ++k) acc += A[row * 18 + k] * qx[k];
-        for (int k = 0; k < dimFr; ++k) acc -= JC[k * 18 + row] * qx[6 + k];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) acc += av[k] * xv[k];
+#pragma unroll
+        for (int k = 0; k < 12; ++k) acc -= jv[k] * zv[k];
         const int leg = lane / 3;
         const bool stance = cm[63 + leg] != 0.0;
         if (!epilogue) {
@@ -839,16 +881,29 @@ void qr_wbc_kernel(int n, const WbcConst *__restrict__ types, const int *__restr
         }
         wave_sync();
     };
-    // N_pre <- N_pre - T JtPre  (T = N_pre pinv, 18 x 3): the rank-3 form of N_pre (I - pinv JtPre)
-    auto npre_update = [&](const real *T) {
+    // jt_npre is N_pre's only reader, and it reads the three rows c0.. of tasks still to come: only those rows are kept (in place: the layout stays
+    // 18 x 18).  With tasks `first`.. to come, compact index m < 3 (nt - first) stands for row live_row(first, m); 18 * 3 = 54 elements per task.
+    auto live_row = [&](int first, int m) -> int {
+        const int q3 = (m * 11) >> 5, tk = first + q3;            // m / 3 for m < 32
+        return ((tk == 0) ? 0 : (tk == 1) ? 3 : 6 + 3 * TLEG((tk - 2) & 3)) + (m - 3 * q3);
+    };
+    // N_pre <- N_pre - T JtPre  (T = N_pre pinv, 18 x 3): the rank-3 form of N_pre (I - pinv JtPre), on the rows of tasks `first`..
+    auto npre_update = [&](const real *T, int first) {
+        const int cnt = 54 * (nt - first);
 #pragma unroll
         for (int u = 0; u < 6; ++u) {
+            if (64 * u >= cnt) break;
             const int e = lane + 64 * u;
-            if (e < 324) {
-                const int i = fdiv16(e, rcp16(18)), j = e - 18 * i;
-                Np[e] -= (T[3 * i] * JtP[j] + T[3 * i + 1] * JtP[18 + j]) + T[3 * i + 2] * JtP[36 + j];
+            if (e < cnt) {
+                const int m = fdiv16(e, rcp16(18)), j = e - 18 * m, i = live_row(first, m);
+                Np[i * 18 + j] -= (T[3 * i] * JtP[j] + T[3 * i + 1] * JtP[18 + j]) + T[3 * i + 2] * JtP[36 + j];
             }
         }
+        wave_sync();
+    };
+    // N_pre = I without contacts (flight), on the rows of every task
+    auto npre_identity = [&]() {
+        for (int e = lane; e < 54 * nt; e += 64) { const int m = fdiv16(e, rcp16(18)), j = e - 18 * m, i = live_row(0, m); Np[i * 18 + j] = (i == j) ? 1.0 : 0.0; }
         wave_sync();
     };
     // lamI (registers, every lane) <- pinv of the 3 x 3 in `lam` with eigenvalue cut thr
@@ -892,18 +947,20 @@ void qr_wbc_kernel(int n, const WbcConst *__restrict__ types, const int *__restr
             for (int k = 0; k < D; ++k) acc -= JB[lane * D + k] * Jcd[3 * CLEG(k / 3) + k % 3];
             qdd[lane] = acc;
         }
+        const int cnt = 54 * nt;                       // the rows of every task (live_row)
 #pragma unroll
         for (int u = 0; u < 6; ++u) {
+            if (64 * u >= cnt) break;
             const int e = lane + 64 * u;
-            if (e < 324) {
-                const int i = fdiv16(e, rcp16(18)), j = e - 18 * i;
+            if (e < cnt) {
+                const int m = fdiv16(e, rcp16(18)), j = e - 18 * m, i = live_row(0, m);
                 real av[D], bv[D];
 #pragma unroll
                 for (int k = 0; k < D; ++k) { av[k] = JB[i * D + k]; bv[k] = JC[k * 18 + j]; }
                 real a0 = 0.0, a1 = 0.0, a2 = 0.0;
 #pragma unroll
                 for (int k = 0; k < D; k += 3) { a0 += av[k] * bv[k]; a1 += av[k + 1] * bv[k + 1]; a2 += av[k + 2] * bv[k + 2]; }
-                Np[e] = ((i == j) ? 1.0 : 0.0) - ((a0 + a1) + a2);
+                Np[i * 18 + j] = ((i == j) ? 1.0 : 0.0) - ((a0 + a1) + a2);
             }
         }
         wave_sync();
@@ -920,9 +977,7 @@ void qr_wbc_kernel(int n, const WbcConst *__restrict__ types, const int *__restr
             case 2: contact_part(std::integral_constant<int, 6>{}, false, thr2); break;
             case 3: contact_part(std::integral_constant<int, 9>{}, false, thr2); break;
             case 4: contact_part(std::integral_constant<int, 12>{}, false, thr2); break;
-            default:
-                for (int e = lane; e < 324; e += 64) Np[e] = ((e / 18) == (e % 18)) ? 1.0 : 0.0;
-                wave_sync();
+            default: npre_identity();
         }
         for (int t = 0; t < nt; ++t) {
             TASK_COLS(t, c0, J3, ld);
@@ -951,10 +1006,10 @@ void qr_wbc_kernel(int n, const WbcConst *__restrict__ types, const int *__restr
                 }
                 upd = ((t > 0) ? prevv[i] : 0.0) + ((JtB[3 * i] * tv3[0] + JtB[3 * i + 1] * tv3[1]) + JtB[3 * i + 2] * tv3[2]);
             }
-            if (t < nt - 1 && lane < 54) { const int r = lane / 3, j = lane - 3 * r; T1[lane] = dot18(Np + r * 18, 1, JtB + j, 3, 18); }
+            if (lane < 9 * (nt - 1 - t)) { const int m = lane / 3, j = lane - 3 * m, r = live_row(t + 1, m); T1[3 * r + j] = dot18(Np + r * 18, 1, JtB + j, 3, 18); }
             wave_sync();
             if (lane < 36) { if (lane < 18) dq1[lane] = upd; else dq2[lane - 18] = upd; }
-            if (t < nt - 1) npre_update(T1); else wave_sync();
+            if (t < nt - 1) npre_update(T1, t + 1); else wave_sync();
         }
         if (lane < 12) {
             st_through(&g_qdes[(size_t)lane * n + rid], (float)(qj[lane] + dq1[6 + lane]), pipe.flag != nullptr);
@@ -975,8 +1030,7 @@ void qr_wbc_kernel(int n, const WbcConst *__restrict__ types, const int *__restr
         case 4: contact_part(std::integral_constant<int, 12>{}, true, thrW); break;
         default:
             if (lane < 18) qdd[lane] = 0.0;
-            for (int e = lane; e < 324; e += 64) Np[e] = ((e / 18) == (e % 18)) ? 1.0 : 0.0;
-            wave_sync();
+            npre_identity();
     }
     QW_TS(12);
     for (int t = 0; t < nt; ++t) {
@@ -1004,10 +1058,10 @@ void qr_wbc_kernel(int n, const WbcConst *__restrict__ types, const int *__restr
                 tv3[k] = tkX[3 * t + k] - ((t >= 2) ? Jcd[c0 - 6 + k] : 0.0) - ((J3[k * ld] * qdd[c0] + J3[k * ld + 1] * qdd[c0 + 1]) + J3[k * ld + 2] * qdd[c0 + 2]);
             upd = qdd[lane] + ((JtB[3 * lane] * tv3[0] + JtB[3 * lane + 1] * tv3[1]) + JtB[3 * lane + 2] * tv3[2]);
         }
-        if (t < nt - 1 && lane < 54) { const int r = lane / 3, j = lane - 3 * r; T2[lane] = dot18(Np + r * 18, 1, JtB + j, 3, 18); }
+        if (lane < 9 * (nt - 1 - t)) { const int m = lane / 3, j = lane - 3 * m, r = live_row(t + 1, m); T2[3 * r + j] = dot18(Np + r * 18, 1, JtB + j, 3, 18); }
         wave_sync();
         if (lane < 18) qdd[lane] = upd;
-        if (t < nt - 1) npre_update(T2); else wave_sync();
+        if (t < nt - 1) npre_update(T2, t + 1); else wave_sync();
     }
 
     QW_TS(7);
