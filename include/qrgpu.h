@@ -572,7 +572,9 @@ int qrgpu_swing_action_batch(qrgpu_ctx *ctx, int n, const qrgpu_swing_mode_desc 
  *   d_stance_state [QRGPU_STANCE_STATE_FLOATS][n] the controller's memory: row 0 heightInControlFrame, which est_out reports as NaN while no
  *                foot is in stance and the reference then keeps; reset != 0 starts it at desc->body_height (qr_robot_pose_estimator.cpp:50)
  * current_time and desc->pose_reset_time give the WALK pose phase while robot_stop (GetIntermediateBasePose(currentTime)); otherwise that
- * phase is moveBasePhase.  robot_stop (:95-102) sets every contact, ratios 0.01 / 10 and N = 4 in every mode, over what the walk kernel wrote.
+ * phase is moveBasePhase.  Under a stage-reset binding with d_ticks (qrgpu_set_stage_reset) current_time is the robot's own;
+ * desc->pose_reset_time stays one scalar for the batch (it is read only while robot_stop; a per-robot pose-planner reset time is out of scope).
+ * robot_stop (:95-102) sets every contact, ratios 0.01 / 10 and N = 4 in every mode, over what the walk kernel wrote.
  * In POSITION mode qrComAdjuster::Update runs in the kernel (erf in double); in ADVANCED_TROT the reference never calls it, so
  * comPosInBaseFrame is the zero vector of its Reset.  Dead branches of the reference that are not built: qr_stance_kernel.hip's header.
  * Outputs, each may be NULL:
@@ -865,7 +867,8 @@ int qrgpu_plant_step_body_batch(qrgpu_ctx *ctx, int n, const qrgpu_plant_params 
  *   Warm start: a robot's stored MPC working set is not cleared: it is speed only (qrgpu_set_warm_start), a stale set leaves row by row.
  *   Overlapped ticks: this call is "another launch of the context" -- the next tick is not chained (qrgpu_set_tick_overlap, rule 2).  It does not
  *     touch the hand-over words of prev_ori.
- *   Out of scope: the stage kernels (gait, swing, estimator) take a scalar reset, not a per-robot one; d_done is the mask such a change would take.
+ *   Stage memory: the controller stages in front of the tick reset a robot of their own accord when bound to d_done and d_ep_state with
+ *     qrgpu_set_stage_reset (below).  The loop is then: episode step, plant step, ground, estimator, gait, swing, front-end or stance, tick.
  * QRGPU_ERR_BAD_ARG (nothing launched; qrgpu_last_error names the argument): n < 1 or n > max_batch; NULL desc, d_fb_state, d_ep_state,
  * d_ep_stats, d_done or d_spawn; n_spawn < 1; a terrain the terrain call would refuse (nx or ny < 2, n_fields < 1, cell <= 0 or not finite, x0 or y0 not finite), or a terrain without
  * d_height; d_done_list without
@@ -907,6 +910,45 @@ int  qrgpu_episode_step_batch(qrgpu_ctx *ctx, int n, const qrgpu_episode_desc *d
                               const int *d_plant_status, const int *d_tick_status, const int *d_force_reset, float *d_fb_state,
                               float *d_prev_ori, float *d_motor_cmd, int *d_ep_state, float *d_ep_stats, int *d_done, int *d_done_list,
                               int *d_done_count);
+
+/* ---- per-robot reset and clock of the stage kernels -------------------------------------------------------------------------------------------
+ * qrgpu_set_stage_reset binds the stages with memory to a device mask and a device tick count, so that a robot that qrgpu_episode_step_batch has
+ * respawned starts its gait, swing, estimator, ground, stance, pose-planner and front-end memory afresh at its next stage calls, with a clock of
+ * its own -- in the reference qrLocomotionController::Reset restarts timeSinceReset (qr_locomotion_controller.cpp:56-66), which Update feeds to the
+ * gait generator (:69-76): time is per robot.  Off by default; r == NULL switches it off.  The struct is copied; the arrays are read when the
+ * kernels run on the context's stream, not at this call: an episode step queued before the stage calls is ordered before them.  With
+ * d_mask = d_done, bits = QRGPU_EP_REASONS, d_ticks = d_ep_state (row 0: ticks in this episode) and tick_dt the control period, the loop is
+ *     episode step, plant step, ground, estimator, gait, swing, front-end or stance, tick.
+ * While a binding is set, robot r's reset level at a stage call is the call's scalar `reset` if that is non-zero (exactly as without a binding);
+ * otherwise the bound level if (d_mask[r] & bits) != 0; otherwise 0.  The bound level in each stage's own numbers:
+ *     stage                                              CONSTRUCT   LIVE
+ *     qrgpu_gait_update_batch                            1           2
+ *     qrgpu_walk_gait_update_batch                       2           1
+ *     qrgpu_swing_update_batch                           2           1
+ *     ground, stance update / tick, pose plan            their one level
+ * What a scalar reset writes beside the state (d_swing_flags cleared, the lift-off rows of d_swing_in, d_swing_vel_in and d_fe_in, d_stance_state
+ * at body_height) a masked robot gets in the same way.  qrgpu_pose_plan_batch launches for a masked robot also where event is 0.
+ * The two stages without a scalar reset:
+ *     qrgpu_estimator_update_batch   a masked robot's d_est_state column is taken as zeros (its content is not read); the update goes on from there.
+ *     qrgpu_mpc_frontend_batch       a masked robot's d_fe_state column gets MPCStanceLegController::Reset (qr_mpc_stance_leg_controller.cpp:78-81,
+ *                                    :92) before the update: row 2 = 0, row 3 = fe_in row 9, rows 4-6 = fe_in rows 6-8, row 7 = 0; rows 0, 1 are
+ *                                    kept at LIVE and 0 at CONSTRUCT (the members' initialisers, qr_mpc_stance_leg_controller.h:126,131).
+ * With d_ticks, qrgpu_gait_update_batch, qrgpu_walk_gait_update_batch, qrgpu_stance_update_batch and qrgpu_stance_tick_batch use
+ * current_time_r = (float)d_ticks[r] * tick_dt (one float product) where they use the scalar current_time, which is then ignored;
+ * desc->pose_reset_time of the stance stage stays scalar.  No other entry point reads the binding: not the pack, footholds, swing targets, swing
+ * velocity, swing action and stance command calls, the tick, the plant or the episode step.
+ * QRGPU_ERR_BAD_ARG (nothing changed: an earlier binding stays in force; qrgpu_last_error names the field): d_mask and d_ticks both NULL; d_mask
+ * with bits == 0; d_mask with a level that is neither of the two; d_ticks with a tick_dt that is not finite or not greater than 0. */
+#define QRGPU_STAGE_RESET_CONSTRUCT 1   /* the stage as constructed, then its Reset() */
+#define QRGPU_STAGE_RESET_LIVE      2   /* Reset() on the running stage */
+typedef struct {
+    const int *d_mask;    /* [n] or NULL; robot r is reset at a stage call when (d_mask[r] & bits) != 0 */
+    unsigned   bits;      /* e.g. QRGPU_EP_REASONS with d_mask = d_done */
+    int        level;     /* one of the two above */
+    const int *d_ticks;   /* [n] or NULL; per-robot clock: current_time_r = (float)d_ticks[r] * tick_dt, one float32 product */
+    float      tick_dt;   /* e.g. 0.002f with d_ticks = d_ep_state (row 0: ticks in this episode) */
+} qrgpu_stage_reset;
+int qrgpu_set_stage_reset(qrgpu_ctx *ctx, const qrgpu_stage_reset *r /* NULL: off */);
 
 /* ---- multi-GPU: all-gather of the per-robot torques over RCCL / xGMI ----------------------------------------
  * One process per GPU, one context per process; rank r of N owns a contiguous shard of the robot population and there is no exchange

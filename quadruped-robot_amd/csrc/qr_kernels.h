@@ -74,6 +74,48 @@ __global__ void qr_stance_command_kernel(int n, qrgpu_stance_desc S, int stop, c
 __global__ void qr_pose_plan_kernel(int n, qrgpu_pose_plan_desc D, int event, const int *g_event, int reset, const float *g_est_in, const float *g_est_out,
                                     const float *g_ground, const float *g_rpy, const float *g_walk, float *g_state, float *g_cmd, float *g_out, int *g_flags);
 
+// The per-robot forms of the eight stage kernels with memory (qrgpu_set_stage_reset): the same kernel text, compiled a second time with
+// QR_STAGE_PR 1 (the *.inc.h files beside the kernel files), which names it NAME_pr and gives it the binding as one more argument.  The binding's level
+// is already the stage's own number (the front-end takes the QRGPU_STAGE_RESET_* value itself).
+#define QR_STAGE_CAT_(a, b) a##b
+#define QR_STAGE_CAT(a, b) QR_STAGE_CAT_(a, b)
+#define QR_STAGE_K_0(name) name
+#define QR_STAGE_K_1(name) name##_pr
+#define QR_STAGE_PARAM_0
+#define QR_STAGE_PARAM_1 , StageResetArgs SR
+#define QR_STAGE_K(name) QR_STAGE_CAT(QR_STAGE_K_, QR_STAGE_PR)(name)
+#define QR_STAGE_PARAM QR_STAGE_CAT(QR_STAGE_PARAM_, QR_STAGE_PR)
+struct StageResetArgs {
+    const int *mask;      // [n] or null
+    unsigned bits;
+    int level;
+    const int *ticks;     // [n] or null
+    float tick_dt;
+};
+// Robot i's mask word (0 without a mask) and clock (the call's scalar without a tick array): one row load each, issued with the first state loads.
+__device__ __forceinline__ bool stage_masked(const StageResetArgs &R, int i) { return R.mask && ((unsigned)R.mask[i] & R.bits) != 0u; }
+__device__ __forceinline__ float stage_time(const StageResetArgs &R, int i, float scalar)
+{
+#pragma clang fp contract(off)
+    return R.ticks ? (float)R.ticks[i] * R.tick_dt : scalar;
+}
+__global__ void qr_frontend_kernel_pr(int n, int horizon, int numHorizonL, float dt, float dtMPC, int period, const float *fin, float *fst,
+                                      float *g_traj, float *g_gait, float *g_cmd, int *g_updated, StageResetArgs R);
+__global__ void qr_estimator_kernel_pr(int n, qrgpu_estimator_desc D, const float *g_in, const unsigned *g_tick, double *st, float *g_out, StageResetArgs R);
+__global__ void qr_gait_kernel_pr(int n, qrgpu_gait_desc D, float currentTime, int stop, int fresh, const float *g_contact, float *st, float *g_out, float *g_fe,
+                                  StageResetArgs R);
+__global__ void qr_ground_kernel_pr(int n, int fresh, const float *g_in, double *g_st, float *g_out, float *g_est_in, StageResetArgs R);
+__global__ void qr_walk_gait_kernel_pr(int n, WalkDesc D, float currentTime, int stop, int fresh, const float *g_contact, float *st, float *g_out, float *g_ratio,
+                                       float *g_vmc_in, StageResetArgs R);
+__global__ void qr_swing_update_kernel_pr(int n, qrgpu_swing_mode_desc M, int reset, int stop, const float *g_est_in, const float *g_est_out, const float *g_gait_out,
+                                          float *g_st, float *g_swing_in, float *g_swing_vel_in, float *g_fe_in, int *g_flags, StageResetArgs R);
+__global__ void qr_stance_update_kernel_pr(int n, qrgpu_stance_desc S, float current_time, int stop, int reset, const float *g_est_in, const float *g_est_out,
+                                           const float *g_ground, const float *g_rpy, const float *g_gait_out, const float *g_gait_state, const float *g_cmd,
+                                           float *g_st, float *g_vmc_in, float *g_ratio, float *g_out, StageResetArgs R);
+__global__ void qr_pose_plan_kernel_pr(int n, qrgpu_pose_plan_desc D, int event, const int *g_event, int reset, const float *g_est_in, const float *g_est_out,
+                                       const float *g_ground, const float *g_rpy, const float *g_walk, float *g_state, float *g_cmd, float *g_out, int *g_flags,
+                                       StageResetArgs R);
+
 // qr_plant_kernel.hip: four lanes per robot, sixteen robots per workgroup of one wavefront
 __global__ void qr_fwd_dyn_kernel(int n, const WbcConst *types, const int *type_id, int type_ready, const float *g_state, const float *g_tau, const float *g_ff,
                                   float *g_nudot, int *g_status);

@@ -98,6 +98,9 @@ struct qrgpu_ctx {
     qrgpu_plant_body_desc *d_body = nullptr;
     bool body_ready[QRGPU_MAX_TYPES] = {false, false, false, false};
     bool body_dirty = true;
+    // the stage kernels' per-robot reset and clock (qrgpu_set_stage_reset): while on, the stage entry points launch the _pr kernels
+    qrgpu_stage_reset stage_reset{};
+    bool stage_reset_on = false;
     // scratch for the single-robot calls and the fused tick
     // Staging of the single-robot calls.  Default: ONE block of pinned, mapped host memory that the kernels read and write in place (zero
     // copy: d_* are the device-side addresses of h_*), so a call is "fill h_in1, one launch, wait, read h_out1" with no copy command on the

@@ -248,6 +248,23 @@ def episode_desc(**fields):
     return _set_fields(d, fields)
 
 
+STAGE_RESET_CONSTRUCT, STAGE_RESET_LIVE = 1, 2
+
+
+class stage_reset_struct(C.Structure):
+    _fields_ = [("d_mask", C.c_void_p), ("bits", C.c_uint), ("level", C.c_int), ("d_ticks", C.c_void_p), ("tick_dt", C.c_float)]
+
+
+def stage_reset(mask=None, bits=EP_REASONS, level=STAGE_RESET_CONSTRUCT, ticks=None, tick_dt=0.002):
+    """qrgpu_stage_reset: mask [n] int32 on the device (robot r is reset at a stage call when (mask[r] & bits) != 0; e.g. the episode step's `done`),
+    level STAGE_RESET_CONSTRUCT / STAGE_RESET_LIVE, ticks [n] int32 on the device (current_time_r = float32(ticks[r]) * tick_dt; e.g. row 0 of
+    ep_state).  Either array may be None, not both."""
+    d = stage_reset_struct()
+    d.d_mask = None if mask is None else _dp(mask).value; d.bits = int(bits); d.level = int(level)
+    d.d_ticks = None if ticks is None else _dp(ticks).value; d.tick_dt = float(tick_dt)
+    return d
+
+
 EPILOGUE_HIP_COMP, EPILOGUE_CLIP = 1, 2
 COMM_ID_BYTES = 128
 
@@ -281,7 +298,7 @@ EXPORTS = ["qrgpu_model_desc_default", "qrgpu_create", "qrgpu_destroy", "qrgpu_s
            "qrgpu_stance_desc_default", "qrgpu_stance_update_batch", "qrgpu_stance_command_batch", "qrgpu_stance_tick_batch",
            "qrgpu_pose_plan_desc_default", "qrgpu_pose_plan_batch", "qrgpu_plant_params_default", "qrgpu_forward_dynamics_batch", "qrgpu_plant_step_batch",
            "qrgpu_plant_step_terrain_batch", "qrgpu_plant_body_desc_default", "qrgpu_plant_body_setup", "qrgpu_plant_step_body_batch",
-           "qrgpu_episode_desc_default", "qrgpu_episode_step_batch"]
+           "qrgpu_episode_desc_default", "qrgpu_episode_step_batch", "qrgpu_set_stage_reset"]
 
 
 def load_library():
@@ -367,6 +384,7 @@ def load_library():
     lib.qrgpu_plant_step_body_batch.argtypes = [vp, ip, C.POINTER(plant_params_struct), C.POINTER(terrain_desc_struct)] + [vp] * 12
     lib.qrgpu_episode_desc_default.argtypes = [C.POINTER(episode_desc_struct)]; lib.qrgpu_episode_desc_default.restype = None
     lib.qrgpu_episode_step_batch.argtypes = [vp, ip, C.POINTER(episode_desc_struct), ip, C.POINTER(plant_params_struct), C.POINTER(terrain_desc_struct), vp, vp, vp, ip] + [vp] * 11
+    lib.qrgpu_set_stage_reset.argtypes = [vp, C.POINTER(stage_reset_struct)]
     lib.qrgpu_vmc_force1.argtypes = [vp, ip, fp, fp, fp, fp, C.POINTER(ip)]
     lib.qrgpu_vmc_force_world1.argtypes = [vp, ip, fp, fp, fp, fp, fp, C.POINTER(ip)]
     lib.qrgpu_mpc_frontend_batch.argtypes = [vp, ip, ip, C.c_float, C.c_float] + [vp] * 6
@@ -797,6 +815,17 @@ class Context:
                                                      None if terrain is None else C.byref(terrain), _dp(height), _dp(field_id), _dp(spawn), int(n_spawn),
                                                      _dp(plant_status), _dp(tick_status), _dp(force_reset), _dp(fb_state), _dp(prev_ori), _dp(motor_cmd),
                                                      _dp(ep_state), _dp(ep_stats), _dp(done), _dp(done_list), _dp(done_count)))
+
+    def set_stage_reset(self, binding=None, **fields):
+        """Bind the stages with memory (ground, estimator, gait, walk gait, swing update, stance update / tick, pose plan, MPC front-end) to a device
+        mask and a device tick count: binding = stage_reset(...), or its fields as keywords.  A masked robot is reset at its next stage calls
+        (a non-zero scalar reset of a call still wins), and with ticks the gaits and the stance stage run on the robot's own clock.  The arrays
+        are read when the kernels run.  Loop: episode step, plant step, ground, estimator, gait, swing, front-end or stance, tick."""
+        b = stage_reset(**fields) if binding is None else binding
+        self._chk(self._lib.qrgpu_set_stage_reset(self._h, C.byref(b)))
+
+    def clear_stage_reset(self):
+        self._chk(self._lib.qrgpu_set_stage_reset(self._h, None))
 
     def mpc_frontend_batch(self, n, fe_in, fe_state, traj, gait, wbc_cmd=None, mpc_updated=None, num_horizon_l=2, dt_ctrl=0.002, dt_mpc=0.06):
         """SetupCommand + Run + UpdateMPC (without the solve) of n robots: qr_mpc_stance_leg_controller.cpp:158-382."""

@@ -6,8 +6,9 @@
 Each directory holds one sub-directory per kernel translation unit (qr_mpc_kernel, ..., qr_plant_kernel), made there by
   hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=fast-honor-pragmas -fPIC -Wno-unused-value --save-temps
         -Rpass-analysis=kernel-resource-usage -c csrc/UNIT.hip -o UNIT.o > remarks.txt 2>&1
-Normalised: the __hip_cuid_* symbol, white space, assembler comments (no instruction is a comment).  The report goes to stdout in the form of
-profiles/*_isa_compare.txt."""
+Normalised: the __hip_cuid_* symbol, white space, assembler comments (no instruction is a comment), and the function's ordinal in local labels
+(.LBB<k>_<j>, .LJTI<k>_<j>: <k> counts the functions of the unit, so a kernel added in front of another renumbers it).  The report goes to stdout
+in the form of profiles/*_isa_compare.txt."""
 import glob
 import os
 import re
@@ -22,7 +23,7 @@ def kernels(unit_dir):
     for ln in open(s[0]):
         ln = re.sub(r"__hip_cuid_\w+", "__hip_cuid", ln.split(";")[0]).strip()
         if ln:
-            lines.append(re.sub(r"\s+", " ", ln))
+            lines.append(re.sub(r"\.L(BB|JTI|CPI)\d+_", r".L\1_", re.sub(r"\s+", " ", ln)))
     out, name, body = {}, None, []
     desc = {}
     i = 0
@@ -86,7 +87,7 @@ def main():
             if k not in b:
                 differ += 1
                 print("   %-100s GONE" % k)
-    print("KERNELS COMPARED: %d\nKERNELS THAT DIFFER: %d\n\nResource usage as built (branch), the plant kernels:" % (compared, differ))
+    print("KERNELS COMPARED: %d\nKERNELS THAT DIFFER: %d\n\nResource usage as built (branch), the new kernels and the plant kernels:" % (compared, differ))
     for k, r in report:
         print("   %-100s %s" % (k, r))
     return 1 if differ else 0

@@ -4,7 +4,9 @@ action for the walk and position modes -- meant to run under
 
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -o walk -- python tools/prof_stance.py walk
 
-once per mode (velocity, position, walk, advanced_trot), each in a run of its own."""
+once per mode (velocity, position, walk, advanced_trot), each in a run of its own.  --bound (after the mode) alternates the ticks between unbound
+calls and calls under qrgpu_set_stage_reset with an all-zero mask: one trace then holds the gait, swing update and stance update kernels and their
+per-robot forms (qr_*_kernel_pr) side by side."""
 import os
 import sys
 
@@ -18,7 +20,7 @@ import stance_ref as R  # noqa: E402
 MODES = {"velocity": 0, "position": 1, "walk": 2, "advanced_trot": 3}
 
 
-def main(name, n=1024, ticks=2000):
+def main(name, n=1024, ticks=2000, bound=False):
     mode = MODES[name]
     pkg = load_pkg()
     pkg._build.build()
@@ -40,7 +42,15 @@ def main(name, n=1024, ticks=2000):
     d_st, d_vmc, d_ratio, d_out = ctx.alloc((1, n)), ctx.alloc((37, n)), ctx.alloc((8, n)), ctx.alloc((33, n))
     d_f, d_t, d_s, d_mc = ctx.alloc((12, n)), ctx.alloc((12, n)), ctx.alloc((n,), np.int32), ctx.alloc((60, n))
     acts = mode in (1, 2)
+    if bound:
+        d_mask = ctx.alloc((n,), np.int32).upload(np.zeros(n, np.int32)); d_ticks = ctx.alloc((n,), np.int32)
     for k in range(ticks):
+        if bound:                                  # odd ticks: the per-robot kernels on an all-zero mask and the robots' own (equal) clocks
+            d_ticks.upload(np.full(n, k, np.int32))    # (every tick, so that both kinds of tick start behind the same blocking copy)
+            if k % 2:
+                ctx.set_stage_reset(mask=d_mask, ticks=d_ticks, tick_dt=0.002)
+            else:
+                ctx.clear_stage_reset()
         if mode == 2:
             ctx.walk_gait_update_batch(n, gcfg, k * 0.002, d_ct, d_gs, d_go, reset=2 if k == 0 else 0)
         else:
@@ -59,4 +69,4 @@ def main(name, n=1024, ticks=2000):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1] if len(sys.argv) > 1 else "walk")
+    main(sys.argv[1] if len(sys.argv) > 1 else "walk", bound="--bound" in sys.argv[2:])

@@ -4,6 +4,9 @@ at 1024 robots, gait generator -> swing update -> swing action, meant to run und
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -o walk     -- python tools/prof_swing_modes.py walk
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -o position -- python tools/prof_swing_modes.py position
 
+--bound (after the mode) alternates the ticks between unbound calls and calls under qrgpu_set_stage_reset with an all-zero mask, so that one trace
+holds the gait and swing update kernels and their per-robot forms (qr_*_kernel_pr) side by side.
+
 The walk runs the shortened cycle (0.75 s stance); the position mode uses a1_sim's gaps, whose plan is made at the first leg-0 lift-off
 (the slowest update launch of the run)."""
 import os
@@ -16,7 +19,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 from conftest import load_pkg  # noqa: E402
 
 
-def main(mode, n=1024, ticks=2000):
+def main(mode, n=1024, ticks=2000, bound=False):
     pkg = load_pkg()
     pkg._build.build()
     W = pkg.workload
@@ -37,7 +40,15 @@ def main(mode, n=1024, ticks=2000):
     else:
         d_gs, d_go = ctx.alloc((52, n)).upload(np.zeros((52, n), np.float32)), ctx.alloc((24, n))
         gcfg, desc = W.gait_cfg(), pkg.swing_mode_desc(1)
+    if bound:
+        d_mask = ctx.alloc((n,), np.int32).upload(np.zeros(n, np.int32)); d_ticks = ctx.alloc((n,), np.int32)
     for k in range(ticks):
+        if bound:                                  # odd ticks: the per-robot kernels on an all-zero mask and the robots' own (equal) clocks
+            d_ticks.upload(np.full(n, k, np.int32))    # (every tick, so that both kinds of tick start behind the same blocking copy)
+            if k % 2:
+                ctx.set_stage_reset(mask=d_mask, ticks=d_ticks, tick_dt=0.002)
+            else:
+                ctx.clear_stage_reset()
         if mode == "walk":
             ctx.walk_gait_update_batch(n, gcfg, k * 0.002, d_ct, d_gs, d_go, reset=2 if k == 0 else 0)
         else:
@@ -51,4 +62,4 @@ def main(mode, n=1024, ticks=2000):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1] if len(sys.argv) > 1 else "walk")
+    main(sys.argv[1] if len(sys.argv) > 1 else "walk", bound="--bound" in sys.argv[2:])
