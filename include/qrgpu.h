@@ -935,7 +935,8 @@ int  qrgpu_episode_step_batch(qrgpu_ctx *ctx, int n, const qrgpu_episode_desc *d
  *                                    kept at LIVE and 0 at CONSTRUCT (the members' initialisers, qr_mpc_stance_leg_controller.h:126,131).
  * With d_ticks, qrgpu_gait_update_batch, qrgpu_walk_gait_update_batch, qrgpu_stance_update_batch and qrgpu_stance_tick_batch use
  * current_time_r = (float)d_ticks[r] * tick_dt (one float product) where they use the scalar current_time, which is then ignored;
- * desc->pose_reset_time of the stance stage stays scalar.  No other entry point reads the binding: not the pack, footholds, swing targets, swing
+ * desc->pose_reset_time of the stance stage stays scalar.  qrgpu_observe_batch (below) reads the mask, not d_ticks: a masked robot starts from a zero
+ * d_obs_state column, as under its scalar reset.  No other entry point reads the binding: not the pack, footholds, swing targets, swing
  * velocity, swing action and stance command calls, the tick, the plant or the episode step.
  * QRGPU_ERR_BAD_ARG (nothing changed: an earlier binding stays in force; qrgpu_last_error names the field): d_mask and d_ticks both NULL; d_mask
  * with bits == 0; d_mask with a level that is neither of the two; d_ticks with a tick_dt that is not finite or not greater than 0. */
@@ -949,6 +950,82 @@ typedef struct {
     float      tick_dt;   /* e.g. 0.002f with d_ticks = d_ep_state (row 0: ticks in this episode) */
 } qrgpu_stage_reset;
 int qrgpu_set_stage_reset(qrgpu_ctx *ctx, const qrgpu_stage_reset *r /* NULL: off */);
+
+/* ---- the sensor stage: qrRobot*::ReceiveObservation on the device ------------------------------------------------------------------------------
+ * qrgpu_observe_batch turns the raw sensor rows a plant call writes (rows 0-40 of est_in "without ReceiveObservation's filters") into what the
+ * estimator chain reads per tick -- the filtered rows of est_in, d_rpy for qrgpu_pack_state_batch, d_ground_in for qrgpu_ground_update_batch, d_tick
+ * for qrgpu_estimator_update_batch -- so that plant, observe, ground, estimator, pack, tick run without the host touching a robot.  One launch on
+ * the context's stream, one lane per robot.  It changes no other call.  The reference: qr_robot_a1_sim.cpp:606-670 (qrRobotSim: qr_robot_sim.cpp:547-),
+ * qr_robot_a1.cpp:140-193; the filters qr_robot.cpp:30-37, their Reset :55-58; qrMovingWindowFilter<float, N> qr_moving_window_filter.hpp:139-189.
+ * Arithmetic is float32 where the reference's is, its double literals promoting where they do there, contraction off.
+ *
+ * Per robot, in this order (d_raw rows as qrgpu_plant_step_batch's d_est_in; rows 3-5 of d_raw are not read):
+ *   noise (OURS; the reference has none): row += amplitude * s, one float product and one float sum, s = 2 u - 1, u = (word >> 8) 2^-24 from
+ *     Philox-4x32-10 with key (seed, robot index) and counter (step, block, 0x0b5e7, 0).  Block 0, words 0-2: accelerometer x, y, z; block 1, words
+ *     0-2: gyro; blocks 2-4, word j of block 2 + b: q of joint 4 b + j; blocks 5-7: qd likewise.  An amplitude of 0 skips the add: the row's bits are
+ *     those read.  The noise depends on (seed, robot, step) alone -- not on the history, n or the launch; step is the caller's loop count.  The
+ *     attitude carries no noise.
+ *   est_in rows 0-2    the (noised) accelerometer, baseAccInBaseFrame
+ *   est_in rows 3-5    accFilter.CalculateAverage of it: window 5, Neumaier sum with its correction, divided by the length after the push
+ *   roll, pitch, yaw   raw = quatToRPY(d_raw rows 6-9) (state.imu.rpy); calibratedYaw = yaw - yaw_offset, -= M_2PI where >= M_PI, += M_2PI where
+ *                      <= -M_PI (M_2PI is the reference's 6.28318530718, qr_ctypes.h:51).  filter_rpy != 0 (the sim classes): if
+ *                      |baseRollPitchYaw[2] of the previous call - calibratedYaw| >= M_PI the rpy filter is cleared (rpyFilter.Reset()); then
+ *                      rpyFilter.CalculateAverage (window 5) of (roll, pitch, calibratedYaw); then the averaged yaw is folded in the same way.
+ *                      filter_rpy == 0 (the hardware classes): (roll, pitch, calibratedYaw) as it is.
+ *   d_rpy [3][n]       that baseRollPitchYaw
+ *   est_in rows 6-9    baseOrientation = rpyToQuat(baseRollPitchYaw) = rotationMatrixToQuaternion(rpyToRotMat(.)) in float (qr_se3.h:145-178, 228-235)
+ *   est_in rows 10-12  gyroFilter.CalculateAverage (window 5) of the (noised) gyro
+ *   est_in rows 13-16  foot contacts, copied: the plant's contact_threshold default of 5 N is the sim classes' footForce >= 5
+ *                      (qr_robot_a1_sim.cpp:662; the hardware class compares with 15, qr_robot_a1.cpp:183: set contact_threshold)
+ *   est_in rows 17-28  the (noised) q, copied
+ *   est_in rows 29-40  the (noised) qd: filter_motor_velocity != 0 (the hardware classes) through motorVFilter, a 12-vector window of 20
+ *                      (qr_robot_a1.cpp:176); otherwise copied
+ *   est_in rows 41-53  never written: they belong to the gait (41-44) and to qrgpu_ground_update_batch (45-53)
+ *   d_ground_in [23][n] (may be NULL)  rows 0-3 the contacts of this tick; 4-15 FootPositionsInBaseFrame(q) of this tick's angles (UpdateDataFlow,
+ *                      qr_robot.cpp:68; hip_l, upper_l, lower_l, hip_offset as in qrgpu_estimator_desc); 16-18 basePosition = rows 36-38 of
+ *                      d_est_out_prev, the estimator's output of the previous tick -- (0, 0, base_height) when that array is NULL or the robot is
+ *                      reset at this call (qrRobot::Reset, qr_robot.cpp:53); 19-22 the quaternion of rows 6-9
+ *   d_tick [n] (may be NULL)  count * tick_ms, count = the robot's calls since its reset, this one included: the first call gives tick_ms, never 0
+ *                      (the estimators take a last timestamp of 0 for "first sample")
+ * Deliberate readings: abs(baseRollPitchYaw[2] - calibratedYaw) (qr_robot_a1_sim.cpp:630) is read as std::abs(float), the project's standing
+ * reading of the reference's unqualified abs; the hardware class's groundPitch (qr_robot_a1.cpp:160) is computed there and never used; the
+ * motor torques, accelerations and ComputeMoment of UpdateDataFlow feed nothing the library runs and are not produced.
+ *
+ * d_obs_state [qrgpu_observe_state_rows(desc)][n] float32, the stage's memory (the filters are float in the reference: a float row holds them
+ * exactly).  Zero = as constructed / after Reset().  Row 0: the call counter, an unsigned 32-bit integer in the row's bits.  Row 1: baseRollPitchYaw[2]
+ * of the previous call.  Rows 2-24 accFilter, 25-47 gyroFilter, 48-70 rpyFilter, each: sum[3], correction[3], the deque's length, head (the ring slot
+ * the next push writes), ring[5 slots][3 axes].  Rows 71-336, read, written and needed only with filter_motor_velocity: sum[12], correction[12],
+ * length, head, ring[20 slots][12].  A length or head row that does not hold an integer of its range is read as 0.
+ * reset != 0: every robot starts from a zero column; what the column held is not read, and it is zero before the call writes to it.  Under
+ * qrgpu_set_stage_reset a robot with (d_mask[r] & bits) != 0 is reset in the same way when the scalar is 0; d_ticks is not read.
+ * d_est_in may be d_raw itself (the plant's rows filtered in place): a lane loads all its raw rows before its first store.  No other two arrays
+ * may overlap.
+ * QRGPU_ERR_BAD_ARG (nothing launched; qrgpu_last_error names the argument): n < 1 or n > max_batch; a NULL desc, d_raw, d_obs_state, d_est_in or
+ * d_rpy; tick_ms == 0; a negative or non-finite noise amplitude; a non-finite yaw_offset, base_height, hip_l, upper_l, lower_l or hip_offset. */
+#define QRGPU_OBS_SIM      0            /* qrRobotA1Sim, qrRobotSim */
+#define QRGPU_OBS_HARDWARE 1            /* qrRobotA1 */
+#define QRGPU_OBSERVE_STATE_ROWS    71  /* without the motor-velocity window */
+#define QRGPU_OBSERVE_STATE_ROWS_MV 337 /* with it */
+struct qrgpu_observe_desc {
+    int   filter_rpy;               /* sim classes: 1 (rpyFilter, with its Reset at a yaw jump >= pi); hardware classes: 0 */
+    int   filter_motor_velocity;    /* hardware classes: 1 (window 20); sim classes: 0 */
+    float yaw_offset;               /* yawOffset: 0 in the sim classes; the hardware class reads it at start-up (qr_robot_a1.cpp:133) */
+    float hip_l, upper_l, lower_l;  /* FootPositionsInBaseFrame, as qrgpu_estimator_desc */
+    float hip_offset[12];
+    float base_height;              /* qrRobot::Reset basePosition z: A1_BODY_HIGHT 0.27 */
+    unsigned tick_ms;               /* milliseconds per call: 2 */
+    unsigned seed;                  /* sensor noise, OURS */
+    float acc_noise, gyro_noise, q_noise, qd_noise;     /* amplitudes, m/s^2, rad/s, rad, rad/s; 0 = none */
+};
+typedef struct qrgpu_observe_desc qrgpu_observe_desc;
+/* variant QRGPU_OBS_SIM: 1, 0; QRGPU_OBS_HARDWARE: 0, 1; both: 0, A1's geometry (0.08505, 0.2, 0.2, (+-0.1805, +-0.047, 0)), 0.27, 2, seed 1, no noise */
+void qrgpu_observe_desc_default(qrgpu_observe_desc *d, int variant);
+int  qrgpu_observe_state_rows(const qrgpu_observe_desc *d);      /* rows of d_obs_state; 0 for NULL */
+int  qrgpu_observe_batch(qrgpu_ctx *ctx, int n, const qrgpu_observe_desc *desc, int reset, unsigned step,
+                         const float *d_raw /* [41][n]: rows 0-40 as the plant writes them */,
+                         const float *d_est_out_prev /* [42][n] of the previous tick, or NULL */, float *d_obs_state,
+                         float *d_est_in /* [54][n]; may be d_raw itself */, float *d_rpy /* [3][n] */,
+                         float *d_ground_in /* [23][n], may be NULL */, unsigned *d_tick /* [n], may be NULL */);
 
 /* ---- multi-GPU: all-gather of the per-robot torques over RCCL / xGMI ----------------------------------------
  * One process per GPU, one context per process; rank r of N owns a contiguous shard of the robot population and there is no exchange

@@ -137,4 +137,8 @@ __global__ void qr_episode_kernel(int n, qrgpu_episode_desc D, double cos_tilt, 
                                   const int *g_force, float *g_state, float *g_prev, float *g_cmd, int *g_st, float *g_stats, int *g_done, int *g_list,
                                   int *g_count);
 
+// qr_observe_kernel.hip: one lane per robot; ReceiveObservation's filters, yaw logic and quaternion, the inputs of the ground and estimator stages
+__global__ void qr_observe_kernel(int n, qrgpu_observe_desc D, int reset, unsigned step, StageResetArgs R, const float *g_raw, const float *g_prev, float *g_st,
+                                  float *g_est_in, float *g_rpy, float *g_ground_in, unsigned *g_tick);
+
 }  // namespace qrgpu

@@ -535,4 +535,48 @@ int qrgpu_set_stage_reset(qrgpu_ctx *c, const qrgpu_stage_reset *r)
     return QRGPU_OK;
 }
 
+void qrgpu_observe_desc_default(qrgpu_observe_desc *d, int variant)
+{   // qr_robot.cpp:30-37 (the windows are the kernel's), qr_robot_a1_sim.cpp:606-670, qr_robot_a1.cpp:140-193; geometry as qrgpu_estimator_desc_default
+    if (!d) return;
+    memset(d, 0, sizeof(*d));
+    const bool hardware = variant == QRGPU_OBS_HARDWARE;
+    d->filter_rpy = hardware ? 0 : 1; d->filter_motor_velocity = hardware ? 1 : 0;
+    d->hip_l = 0.08505f; d->upper_l = 0.2f; d->lower_l = 0.2f;
+    const float ho[12] = {0.1805f, -0.047f, 0.f, 0.1805f, 0.047f, 0.f, -0.1805f, -0.047f, 0.f, -0.1805f, 0.047f, 0.f};
+    memcpy(d->hip_offset, ho, sizeof(ho));
+    d->base_height = 0.27f; d->tick_ms = 2u; d->seed = 1u;
+}
+
+int qrgpu_observe_state_rows(const qrgpu_observe_desc *d) { return !d ? 0 : d->filter_motor_velocity ? QRGPU_OBSERVE_STATE_ROWS_MV : QRGPU_OBSERVE_STATE_ROWS; }
+
+static int observe_bad(qrgpu_ctx *c, const char *what)
+{
+    if (c) c->err = std::string("qrgpu_observe_batch: ") + what;
+    return QRGPU_ERR_BAD_ARG;
+}
+
+int qrgpu_observe_batch(qrgpu_ctx *c, int n, const qrgpu_observe_desc *desc, int reset, unsigned step, const float *d_raw, const float *d_est_out_prev,
+                        float *d_obs_state, float *d_est_in, float *d_rpy, float *d_ground_in, unsigned *d_tick)
+{
+    if (!c) return QRGPU_ERR_BAD_ARG;
+    if (!batch_ok(c, n)) return observe_bad(c, "n");
+    if (!desc) return observe_bad(c, "desc");
+    if (!d_raw) return observe_bad(c, "d_raw");
+    if (!d_obs_state) return observe_bad(c, "d_obs_state");
+    if (!d_est_in) return observe_bad(c, "d_est_in");
+    if (!d_rpy) return observe_bad(c, "d_rpy");
+    if (desc->tick_ms == 0u) return observe_bad(c, "tick_ms");
+    const struct { const char *name; float v; } noise[] = {{"acc_noise", desc->acc_noise}, {"gyro_noise", desc->gyro_noise}, {"q_noise", desc->q_noise},
+        {"qd_noise", desc->qd_noise}};
+    for (const auto &a : noise) if (!std::isfinite(a.v) || !(a.v >= 0.f)) return observe_bad(c, a.name);
+    const struct { const char *name; float v; } finite[] = {{"yaw_offset", desc->yaw_offset}, {"base_height", desc->base_height}, {"hip_l", desc->hip_l},
+        {"upper_l", desc->upper_l}, {"lower_l", desc->lower_l}};
+    for (const auto &a : finite) if (!std::isfinite(a.v)) return observe_bad(c, a.name);
+    for (int k = 0; k < 12; ++k) if (!std::isfinite(desc->hip_offset[k])) return observe_bad(c, "hip_offset");
+    // the binding as the kernel takes it, always: a null mask is "unbound"; the clock is not read
+    const StageResetArgs R = c->stage_reset_on ? StageResetArgs{c->stage_reset.d_mask, c->stage_reset.bits, 1, nullptr, 0.f} : StageResetArgs{nullptr, 0u, 1, nullptr, 0.f};
+    return launch_stage(c, qr_observe_kernel, per_robot(n), dim3(64), n, *desc, reset != 0 ? 1 : 0, step, R, d_raw, d_est_out_prev, d_obs_state, d_est_in, d_rpy,
+                        d_ground_in, d_tick);
+}
+
 }  // extern "C"

@@ -265,6 +265,24 @@ def stage_reset(mask=None, bits=EP_REASONS, level=STAGE_RESET_CONSTRUCT, ticks=N
     return d
 
 
+OBS_SIM, OBS_HARDWARE = 0, 1
+OBSERVE_STATE_ROWS, OBSERVE_STATE_ROWS_MV = 71, 337
+
+
+class observe_desc_struct(C.Structure):
+    _fields_ = [("filter_rpy", C.c_int), ("filter_motor_velocity", C.c_int), ("yaw_offset", C.c_float), ("hip_l", C.c_float), ("upper_l", C.c_float),
+                ("lower_l", C.c_float), ("hip_offset", C.c_float * 12), ("base_height", C.c_float), ("tick_ms", C.c_uint), ("seed", C.c_uint),
+                ("acc_noise", C.c_float), ("gyro_noise", C.c_float), ("q_noise", C.c_float), ("qd_noise", C.c_float)]
+
+
+def observe_desc(variant="sim", **fields):
+    """qrgpu_observe_desc of the "sim" classes (rpy filter on, motor velocities as read) or the "hardware" class (rpy as read, motor velocities through
+    the window of 20): A1's geometry, base height 0.27, 2 ms ticks, seed 1, no noise, with any field overridden (scalars or sequences by name)."""
+    d = observe_desc_struct()
+    load_library().qrgpu_observe_desc_default(C.byref(d), {"sim": OBS_SIM, "hardware": OBS_HARDWARE}[variant] if isinstance(variant, str) else int(variant))
+    return _set_fields(d, fields)
+
+
 EPILOGUE_HIP_COMP, EPILOGUE_CLIP = 1, 2
 COMM_ID_BYTES = 128
 
@@ -298,7 +316,8 @@ EXPORTS = ["qrgpu_model_desc_default", "qrgpu_create", "qrgpu_destroy", "qrgpu_s
            "qrgpu_stance_desc_default", "qrgpu_stance_update_batch", "qrgpu_stance_command_batch", "qrgpu_stance_tick_batch",
            "qrgpu_pose_plan_desc_default", "qrgpu_pose_plan_batch", "qrgpu_plant_params_default", "qrgpu_forward_dynamics_batch", "qrgpu_plant_step_batch",
            "qrgpu_plant_step_terrain_batch", "qrgpu_plant_body_desc_default", "qrgpu_plant_body_setup", "qrgpu_plant_step_body_batch",
-           "qrgpu_episode_desc_default", "qrgpu_episode_step_batch", "qrgpu_set_stage_reset"]
+           "qrgpu_episode_desc_default", "qrgpu_episode_step_batch", "qrgpu_set_stage_reset",
+           "qrgpu_observe_desc_default", "qrgpu_observe_state_rows", "qrgpu_observe_batch"]
 
 
 def load_library():
@@ -385,6 +404,9 @@ def load_library():
     lib.qrgpu_episode_desc_default.argtypes = [C.POINTER(episode_desc_struct)]; lib.qrgpu_episode_desc_default.restype = None
     lib.qrgpu_episode_step_batch.argtypes = [vp, ip, C.POINTER(episode_desc_struct), ip, C.POINTER(plant_params_struct), C.POINTER(terrain_desc_struct), vp, vp, vp, ip] + [vp] * 11
     lib.qrgpu_set_stage_reset.argtypes = [vp, C.POINTER(stage_reset_struct)]
+    lib.qrgpu_observe_desc_default.argtypes = [C.POINTER(observe_desc_struct), ip]; lib.qrgpu_observe_desc_default.restype = None
+    lib.qrgpu_observe_state_rows.argtypes = [C.POINTER(observe_desc_struct)]
+    lib.qrgpu_observe_batch.argtypes = [vp, ip, C.POINTER(observe_desc_struct), ip, C.c_uint] + [vp] * 7
     lib.qrgpu_vmc_force1.argtypes = [vp, ip, fp, fp, fp, fp, C.POINTER(ip)]
     lib.qrgpu_vmc_force_world1.argtypes = [vp, ip, fp, fp, fp, fp, fp, C.POINTER(ip)]
     lib.qrgpu_mpc_frontend_batch.argtypes = [vp, ip, ip, C.c_float, C.c_float] + [vp] * 6
@@ -826,6 +848,19 @@ class Context:
 
     def clear_stage_reset(self):
         self._chk(self._lib.qrgpu_set_stage_reset(self._h, None))
+
+    def observe_state_rows(self, desc):
+        """Rows of obs_state for desc: OBSERVE_STATE_ROWS, or OBSERVE_STATE_ROWS_MV with the motor-velocity window."""
+        return self._lib.qrgpu_observe_state_rows(C.byref(desc))
+
+    def observe_batch(self, n, desc, raw, obs_state, est_in, rpy, ground_in=None, tick=None, est_out_prev=None, reset=False, step=0):
+        """qrRobot*::ReceiveObservation of n robots (desc: observe_desc()): raw [41][n] = rows 0-40 as a plant call writes them -> the filtered rows
+        0-40 of est_in [54][n] (may be raw itself), rpy [3][n], ground_in [23][n] and tick [n] uint32 (both optional) for ground_update_batch,
+        estimator_update_batch and pack_state_batch.  obs_state [observe_state_rows(desc)][n] float32 is the stage's memory, zero = fresh; reset
+        starts every robot afresh, and a stage-reset binding's mask does so per robot.  est_out_prev [42][n]: the estimator's output of the
+        previous tick (None: the base position is (0, 0, base_height)).  step: the caller's loop count, the sensor noise's counter."""
+        self._chk(self._lib.qrgpu_observe_batch(self._h, n, C.byref(desc), int(bool(reset)), int(step) & 0xffffffff, _dp(raw), _dp(est_out_prev),
+                                                _dp(obs_state), _dp(est_in), _dp(rpy), _dp(ground_in), _dp(tick)))
 
     def mpc_frontend_batch(self, n, fe_in, fe_state, traj, gait, wbc_cmd=None, mpc_updated=None, num_horizon_l=2, dt_ctrl=0.002, dt_mpc=0.06):
         """SetupCommand + Run + UpdateMPC (without the solve) of n robots: qr_mpc_stance_leg_controller.cpp:158-382."""

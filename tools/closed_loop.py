@@ -7,6 +7,7 @@ inside the loop.
   python tools/closed_loop.py --terrain plane:0.2 [--push 30]                         the same loop on a height field, with a push on the base
   python tools/closed_loop.py --body [--terrain stairs:0.04] [--push 30]              the same loop with knee and trunk contact and joint limits
   python tools/closed_loop.py --episodes [--max-ticks 400] [--terrain plane:0.2]      episode step -> plant -> tick: robots that fall start again
+  python tools/closed_loop.py --estimator [--sensor-noise 0.02]                       the tick reads the estimator chain's state, not the plant's truth
 
 The robots are dropped from z = 0.30 onto joint PD at the stand pose (400 ticks of 1 ms), shoved by up to 0.3 m/s in x and y, and handed to
 MPC + WBC: qrgpu_plant_step_batch (include/qrgpu.h) writes the ground-truth mpc_state and fb_state the tick reads, and the tick -- the plain
@@ -28,6 +29,13 @@ slope on a plane, with the run's shove as its spawn velocity, on the joint PD ho
 adds them).  Episode 0 is the settled, shoved state of the other runs: nothing is spawned before the first fall.  Without the option the tool runs
 exactly what it ran.
 
+--estimator closes the loop from the sensors: [episode step,] plant (which writes its sensor rows 0-40 into est_in), qrgpu_observe_batch (the
+robot class's filters, in place), qrgpu_ground_update_batch, qrgpu_estimator_update_batch, qrgpu_pack_state_batch into arrays of their own, and the tick
+on those; the plant's true fb_state is read by the plant alone.  All-stance gait: rows 41-44 of est_in are STANCE, uploaded once.  With --episodes the
+stage-reset binding (mask = the step's done words, ticks = ep_state) restarts the observe, ground and estimator memory of a respawned robot.
+--sensor-noise A adds the stage's noise (accelerometer 10 A m/s^2, gyro A rad/s, q 0.1 A rad, qd A rad/s).  How the standing batch fares on the
+estimate, and how far the estimate lies from the truth, is reported, not judged; the trot in this loop and stability under noise are not claimed.
+
   ticks_per_s   closed-loop control ticks per second: every robot advances one tick per (plant step + controller tick)
   in_band       share of the robots that end inside the stand band: |z - 0.27| <= 0.01, |x|, |y| <= 0.03, |roll|, |pitch| <= 0.03
   fallen        (--body) robots that raised PL_TRUNK_CONTACT or PL_KNEE_CONTACT at any tick of the loop, warm-up included
@@ -35,6 +43,8 @@ exactly what it ran.
   episodes_finished, by_reason, mean_episode_ticks   (--episodes) episodes ended in the loop, warm-up included; how often each EP_* bit was among the
                 reasons; their mean length in ticks
   alive_at_end  (--episodes) share of the robots that are finite, within 0.5 rad of level and off their knees and trunk at the last tick
+  est_err_velocity / height / roll_pitch _mean, _max   (--estimator) |estimated - true| of the base velocity (world, m/s), the height (m) and roll and
+                pitch (rad) over the robots whose estimate and truth are finite (estimate_finite) at the last tick; sensor_noise: A
 """
 import argparse
 import importlib.util
@@ -76,9 +86,13 @@ def main():
     ap.add_argument("--episodes", action="store_true", help="per-robot termination and respawn on the device: qrgpu_episode_step_batch (implies --body)")
     ap.add_argument("--max-ticks", type=int, default=0, metavar="N", help="(--episodes) truncate an episode after N ticks; 0 = never")
     ap.add_argument("--spawn-spread", type=float, default=0.05, metavar="M", help="(--episodes) spacing of the 3 x 3 grid of spawn points, metres")
+    ap.add_argument("--estimator", action="store_true", help="the tick reads the estimator chain's state (plant sensor rows -> observe -> ground -> estimator -> pack), not the plant's truth")
+    ap.add_argument("--sensor-noise", type=float, default=0.0, metavar="A", help="(--estimator) sensor noise: acc 10 A m/s^2, gyro A rad/s, q 0.1 A rad, qd A rad/s")
     ap.add_argument("--profile", action="store_true", help="the run a profiler traces: fewer ticks, nothing else changed")
     a = ap.parse_args()
     a.body = a.body or a.episodes
+    if a.sensor_noise != 0.0 and not a.estimator:
+        ap.error("--sensor-noise needs --estimator")
     pkg = _load_pkg()
     pkg._build.build()
     n, h = a.robots, HORIZON
@@ -120,6 +134,17 @@ def main():
         d.update(table=ctx.alloc((4, 9)).upload(table), ep_state=ctx.alloc((q.EPISODE_STATE_ROWS, n), np.int32).zero(), ep_stats=ctx.alloc((q.EPISODE_STATS_ROWS, n)),
                  done_log=ctx.alloc((ticks + 20, n), np.int32).zero(), done_list=ctx.alloc((n,), np.int32), done_count=ctx.alloc((1,), np.int32))
 
+    if a.estimator:     # the sensor-driven chain's arrays: the plant's rows are filtered in place (est_in = raw); rows 41-44 of est_in are STANCE, uploaded once
+        A = a.sensor_noise
+        odesc = pkg.observe_desc("sim", seed=a.seed, acc_noise=10.0 * A, gyro_noise=A, q_noise=0.1 * A, qd_noise=A)
+        ecfg = pkg.workload.estimator_cfg("a1")
+        com = np.asarray(pkg.workload.ROBOTS["a1"]["com_offset"], np.float32)
+        est0 = np.zeros((54, n), np.float32); est0[41:45] = 1.0
+        nd = ctx.estimator_state_doubles(int(ecfg[6]))                    # (the window)
+        d.update(est_in=ctx.alloc((54, n)).upload(est0), obs=ctx.alloc((ctx.observe_state_rows(odesc), n)), rpy=ctx.alloc((3, n)), gin=ctx.alloc((23, n)),
+                 stamp=ctx.alloc((n,), np.uint32), gst=ctx.alloc((13, n), np.float64), est_state=ctx.alloc((nd, n), np.float64).zero(),
+                 est_out=ctx.alloc((42, n)).zero(), mpc_est=ctx.alloc((28, n)), fb_est=ctx.alloc((37, n)))
+
     def plant(par, **out):
         if a.body:
             ctx.plant_step_body_batch(n, par, tdesc, d["height"], d["fb"], d["cmd"], base_push=d["push"], terrain_out=d["tout"], body_out=d["bout"], **out)
@@ -154,9 +179,22 @@ def main():
                 ctx.episode_step_batch(n, edesc, d["fb"], d["table"], 9, d["ep_state"], d["ep_stats"], d["done_log"].row(done[0]), params=params, terrain=tdesc,
                                        height=d["height"], plant_status=d["status_log"].row(done[0] - 1) if done[0] else None, tick_status=None,
                                        prev_ori=d["prev"], motor_cmd=d["cmd"], done_list=d["done_list"], done_count=d["done_count"])
-            plant(params, plant_out=d["out"], mpc_state=d["mpc"], status=d["status_log"].row(done[0]) if a.body else d["plant_status"])
+            if a.estimator and a.episodes:    # the observe, ground and estimator stages restart a robot this episode step respawned
+                ctx.set_stage_reset(mask=d["done_log"].row(done[0]), ticks=d["ep_state"])
+            plant(params, plant_out=d["out"], mpc_state=d["mpc"], status=d["status_log"].row(done[0]) if a.body else d["plant_status"],
+                  **(dict(est_in=d["est_in"]) if a.estimator else {}))
+            if a.estimator:                   # the plant's true fb_state is read by the plant alone: the tick gets mpc_est, fb_est
+                first = done[0] == 0
+                ctx.observe_batch(n, odesc, d["est_in"], d["obs"], d["est_in"], d["rpy"], ground_in=d["gin"], tick=d["stamp"], est_out_prev=d["est_out"],
+                                  reset=first, step=done[0])
+                ctx.ground_update_batch(n, d["gin"], d["gst"], None, d["est_in"], reset=first)
+                ctx.estimator_update_batch(n, ecfg, d["est_in"], d["stamp"], d["est_state"], d["est_out"])
+                ctx.pack_state_batch(n, com, d["est_in"], d["est_out"], d["rpy"], d["mpc_est"], d["fb_est"])
             done[0] += 1
-            ctx.tick_batch(n, d["mpc"], d["traj"], d["gait"], d["fb"], d["wcmd"], d["prev"], d["force"], tau, d["tick_status"])
+            if a.estimator:
+                ctx.tick_batch(n, d["mpc_est"], d["traj"], d["gait"], d["fb_est"], d["wcmd"], d["prev"], d["force"], tau, d["tick_status"])
+            else:
+                ctx.tick_batch(n, d["mpc"], d["traj"], d["gait"], d["fb"], d["wcmd"], d["prev"], d["force"], tau, d["tick_status"])
 
     loop(20)                                                          # warm-up: the first launches, the scheduler's history
     ctx.sync()
@@ -172,6 +210,14 @@ def main():
     plant_flags = log[-1] if a.body else d["plant_status"].download()
     res = dict(metric="closed_loop_ticks_per_s", value=ticks / sec, robot_ticks_per_s=n * ticks / sec, ms_per_tick=1e3 * sec / ticks, robots=n, ticks=ticks,
                substeps=a.substeps, in_band=float(ok.mean()), last_tick_flagged=int(((tick_flags != 0) | (plant_flags != 0)).sum()), profile=bool(a.profile))
+    if a.estimator:   # how far the estimate the tick read lies from the plant's truth at the last tick: reported, not judged
+        est, tru = d["mpc_est"].download().astype(np.float64), d["mpc"].download().astype(np.float64)
+        fin = np.isfinite(est).all(0) & np.isfinite(tru).all(0)
+        err = dict(velocity=np.abs(est[3:6] - tru[3:6]).max(0), height=np.abs(est[2] - tru[2]), roll_pitch=np.abs(est[25:27] - tru[25:27]).max(0))
+        res.update(estimator=True, sensor_noise=a.sensor_noise, estimate_finite=int(fin.sum()))
+        for k, e in err.items():
+            res["est_err_%s_mean" % k] = float(e[fin].mean()) if fin.any() else None
+            res["est_err_%s_max" % k] = float(e[fin].max()) if fin.any() else None
     if on_field:      # what the controllers made of it: reported, not judged
         out = d["out"].download()
         fin = np.isfinite(fb).all(0)                                    # a robot whose state left the finite numbers is counted, not averaged
