@@ -936,7 +936,8 @@ int  qrgpu_episode_step_batch(qrgpu_ctx *ctx, int n, const qrgpu_episode_desc *d
  * With d_ticks, qrgpu_gait_update_batch, qrgpu_walk_gait_update_batch, qrgpu_stance_update_batch and qrgpu_stance_tick_batch use
  * current_time_r = (float)d_ticks[r] * tick_dt (one float product) where they use the scalar current_time, which is then ignored;
  * desc->pose_reset_time of the stance stage stays scalar.  qrgpu_observe_batch (below) reads the mask, not d_ticks: a masked robot starts from a zero
- * d_obs_state column, as under its scalar reset.  No other entry point reads the binding: not the pack, footholds, swing targets, swing
+ * d_obs_state column, as under its scalar reset; so do qrgpu_command_update_batch (d_cmd_state) and qrgpu_mpc_command_batch (d_cmd_mem), further below.
+ * No other entry point reads the binding: not the pack, footholds, swing targets, swing
  * velocity, swing action and stance command calls, the tick, the plant or the episode step.
  * QRGPU_ERR_BAD_ARG (nothing changed: an earlier binding stays in force; qrgpu_last_error names the field): d_mask and d_ticks both NULL; d_mask
  * with bits == 0; d_mask with a level that is neither of the two; d_ticks with a tick_dt that is not finite or not greater than 0. */
@@ -1026,6 +1027,89 @@ int  qrgpu_observe_batch(qrgpu_ctx *ctx, int n, const qrgpu_observe_desc *desc, 
                          const float *d_est_out_prev /* [42][n] of the previous tick, or NULL */, float *d_obs_state,
                          float *d_est_in /* [54][n]; may be d_raw itself */, float *d_rpy /* [3][n] */,
                          float *d_ground_in /* [23][n], may be NULL */, unsigned *d_tick /* [n], may be NULL */);
+
+/* ---- the trot's command, data-flow and motor-command stages --------------------------------------------------------------------------------------
+ * The three pieces of the reference that lie between the stage kernels of the MPC trot (LocomotionMode::ADVANCED_TROT with MPC + WBC).  With them a
+ * trot tick is queued on the context's stream with no host copy: [episode step,] plant, observe, ground, estimator, pack, command, gait (d_contact =
+ * rows 13-16 of est_in), trot inputs, swing update, footholds, swing targets, MPC front-end, tick, MPC command (tools/closed_loop.py --trot).
+ * One launch each, one lane per robot, float32 where the reference is float32, its double literals promoting where they do there, contraction off.
+ * QRGPU_ERR_BAD_ARG (nothing launched, outputs untouched; qrgpu_last_error names the argument): a NULL required array or desc, n < 1, n > max_batch,
+ * a reset other than 0 or 1.
+ *
+ * qrgpu_command_update_batch: qrDesiredStateCommand::Update (QS/controllers/qr_desired_state_command.cpp:164-265).
+ *   d_joy [QRGPU_JOY_ROWS][n]  0-2 joyCmdVx, Vy, Vz; 3-5 joyCmdRollRate, PitchRate, YawRate (already scaled, as the members are); 6 joycmdBodyHeight;
+ *                      7 joyCtrlState, an RC_MODE value as a float (HARD_CODE 0, JOY_TROT 1, JOY_ADVANCED_TROT 2, JOY_WALK 3, JOY_STAND 4, BODY_UP 5,
+ *                      BODY_DOWN 6, EXIT 7; anything else is read as EXIT).  The button state machine (JoyCallback, and the joyCtrlStateChangeRequest
+ *                      block of Update, :173-211) is per event and stays with the caller, who supplies the resulting mode.  In HARD_CODE rows 0-2 and
+ *                      3-5 are vDesInBodyFrame / wDesInBodyFrame, taken unfiltered.  The rows are not written: the zeros JOY_STAND assigns to the
+ *                      joyCmd members are the next JoyCallback's to overwrite.
+ *   d_cmd_state [QRGPU_CMD_STATE_ROWS][n]  the stage's memory: filteredVel[3], filteredOmega[3].  reset 1: every robot starts from zeros (as
+ *                      constructed, :36-37); under qrgpu_set_stage_reset a robot with (d_mask[r] & bits) != 0 does so when the scalar is 0.
+ *   d_state_des [12][n] stateDes.  As written in the reference: (0), (1) and (5) are dt times entries of the vector just zeroed; (4) is
+ *                      clip(filteredOmega[1] * dt, pitch); (2) is joycmdBodyHeight, times the double 0.85 where stateDes(6) < -0.01; the JOY_STAND and
+ *                      else branches zero the filter state as well as the output; the filter is state * float(1.0 - filterFactor) + cmd * filterFactor.
+ *   the rows the existing kernels read, no other row of those arrays touched: d_fe_in 0-5 (stateDes 2, 3, 4, 6, 7, 11), d_fh_in 16-20 (6, 7, 8, 11, 2),
+ *                      d_swing_vel_in 23-26 (6, 7, 8, 11), d_stance_cmd 0-6 (2, 6, 7, 8, 9, 10, 11).  Each of the five outputs may be NULL. */
+#define QRGPU_JOY_ROWS 8
+#define QRGPU_CMD_STATE_ROWS 6
+struct qrgpu_command_desc {
+    float dt;                         /* qr_desired_state_command.hpp:155: 0.002 */
+    float filter_factor;              /* :266: 0.02 */
+    float body_height;                /* robot->bodyHeight, what joycmdBodyHeight is constructed with (qr_desired_state_command.cpp:49; a1_sim: 0.28):
+                                         the value for row 6 of d_joy; the kernel reads the row */
+    float min_velx, max_velx;         /* :317, :312: -0.15, 0.2 */
+    float min_vely, max_vely;         /* :327, :322: -0.1, 0.1 */
+    float min_yawrate, max_yawrate;   /* :337, :332: -0.2, 0.2 */
+    float min_pitch, max_pitch;       /* :307, :302: -0.5, 0.5 */
+};
+typedef struct qrgpu_command_desc qrgpu_command_desc;
+void qrgpu_command_desc_default(qrgpu_command_desc *d);
+int  qrgpu_command_update_batch(qrgpu_ctx *ctx, int n, const qrgpu_command_desc *desc, int reset, const float *d_joy, float *d_cmd_state,
+                                float *d_state_des, float *d_fe_in, float *d_fh_in, float *d_swing_vel_in, float *d_stance_cmd);
+
+/* qrgpu_trot_inputs_batch: the getters of qrRobot / qrStateDataFlow / the gait generator that the trot's controllers call, from arrays the device holds.
+ * Reads d_est_in (quat_wxyz 6-9, rpyRate 10-12, motor angles 17-28), d_est_out (baseVInWorldFrame 3-5, baseVelocityInBaseFrame 6-8,
+ * footPositionsInBaseFrame 12-23, basePosition 36-38), d_rpy [3][n] (as qrgpu_pack_state_batch takes it), d_gait_out [24][n] (desiredLegState 8-11,
+ * legState 12-15) and, for the contacts alone, d_gait_state (allowSwitchLegState 20-23; required with d_fe_in, else may be NULL).
+ * Writes, each array may be NULL, other rows left alone:
+ *   d_fe_in     6-8 basePosition; 9 yaw; 10-13 quat_wxyz; 14-25 foot positions in the world frame, invertRigidTransform(basePosition, baseOrientation,
+ *               footPositionsInBaseFrame) (qrRobot::GetFootPositionsInWorldFrame, qr_robot.cpp:222-230); 38-41 the contacts
+ *               MPCStanceLegController::Run reads (:212), which UpdateDesCommand's UpdateFRatio sets: (desiredLegState STANCE and
+ *               allowSwitchLegState) or legState EARLY_CONTACT (qr_torque_stance_leg_controller.cpp:109-123), 1 or 0
+ *   d_fh_in     21-32 footPositionsInBaseFrame; 33-36 quat_wxyz; 37-39 rpy; 40-42 baseVelocityInBaseFrame; 43-45 rpyRate
+ *   d_swing_in  36-38 basePosition; 39-42 quat_wxyz; 43-45 baseVInWorldFrame; 46-57 motor angles
+ *   d_est_in_next  rows 41-44: desiredLegState of this tick's gait, which the next estimator update reads.  Usually d_est_in itself: the rows written
+ *               are not among the rows read, and a lane loads every row it reads before its first store.  No other two arrays may overlap. */
+int  qrgpu_trot_inputs_batch(qrgpu_ctx *ctx, int n, const float *d_est_in, const float *d_est_out, const float *d_rpy, const float *d_gait_out,
+                             const float *d_gait_state, float *d_fe_in, float *d_fh_in, float *d_swing_in, float *d_est_in_next);
+
+/* qrgpu_mpc_command_batch: the motor command of the MPC mode -- MPCStanceLegController::GetAction's command (qr_mpc_stance_leg_controller.cpp:129-156)
+ * merged with the swing command (qrRaibertSwingLegController::GetAction, qr_swing_leg_controller.cpp:419, :426-459) as
+ * qrLocomotionController::GetAction merges them (qr_locomotion_controller.cpp:128-147).
+ *   d_tau [12][n] of qrgpu_tick_batch; d_qdes [24][n] of qrgpu_swing_targets_batch (angles, velocities: a leg not recomputed this tick keeps its last
+ *   targets there, as the map does); d_swing_in rows 0-3 (the legs that call computed); d_gait_out (desiredLegState 8-11, legState 12-15, curLegState
+ *   16-19); d_gait_state (allowSwitchLegState 20-23)
+ *   d_cmd_mem [1][n] int  bit l: leg l has an entry in swingJointAnglesVelocities.  reset 1 clears it for every robot (Reset(), :100), a stage-reset
+ *                      binding's mask per robot; then the legs flagged in d_swing_in are added.
+ *   d_motor_cmd [QRGPU_MOTOR_CMD_ROWS][n] = p[12], Kp[12], d[12], Kd[12], tua[12].  A leg with an entry whose flag of :450-452 holds (legState SWING or
+ *                      USERDEFINED_SWING, or curLegState SWING while allowSwitchLegState is false): {q, kp, qd, kd, tua_s}; every other motor
+ *                      {0, early_contact_abad_kp on the abad of an EARLY_CONTACT leg else 0, 0, stance_kd, tau}.
+ * The torque epilogue, as read from qr_fsm_state_locomotion.cpp:140-157, qr_wbc_locomotion_controller.cpp:205-217 and qr_safety_checker.cpp:48-66: the
+ * compensation is added to tua of every motor after GetAction, swing commands included; UpdateLegCMD then overwrites tua of the legs in contact_state
+ * with the WBC's torque; the clip comes last.  qrgpu_tick_batch applies the context's epilogue to d_tau accordingly, so tau is taken as it comes.
+ * tua_s of a swing command is 0 with desc->epilogue applied to it (QRGPU_EPILOGUE_HIP_COMP: -+0.9 on the abad; QRGPU_EPILOGUE_CLIP) -- this call does not
+ * read the context's flags, the caller passes the ones it set -- except on a leg that is also in contact_state (the contacts of
+ * qrgpu_trot_inputs_batch), where the WBC's overwrite leaves d_tau. */
+struct qrgpu_mpc_command_desc {
+    float kp[12], kd[12];             /* robot->GetMotorKps / GetMotorKdp, config/a1_sim: (100, 100, 100) / (1, 2, 2) per leg */
+    float stance_kd;                  /* qr_mpc_stance_leg_controller.cpp:145, :149: 3.0 */
+    float early_contact_abad_kp;      /* :145: 100.0 */
+    int   epilogue;                   /* QRGPU_EPILOGUE_* bits as given to qrgpu_set_torque_epilogue: 0 */
+};
+typedef struct qrgpu_mpc_command_desc qrgpu_mpc_command_desc;
+void qrgpu_mpc_command_desc_default(qrgpu_mpc_command_desc *d);
+int  qrgpu_mpc_command_batch(qrgpu_ctx *ctx, int n, const qrgpu_mpc_command_desc *desc, int reset, const float *d_tau, const float *d_qdes,
+                             const float *d_swing_in, const float *d_gait_out, const float *d_gait_state, int *d_cmd_mem, float *d_motor_cmd);
 
 /* ---- multi-GPU: all-gather of the per-robot torques over RCCL / xGMI ----------------------------------------
  * One process per GPU, one context per process; rank r of N owns a contiguous shard of the robot population and there is no exchange

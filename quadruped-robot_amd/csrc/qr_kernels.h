@@ -141,4 +141,12 @@ __global__ void qr_episode_kernel(int n, qrgpu_episode_desc D, double cos_tilt, 
 __global__ void qr_observe_kernel(int n, qrgpu_observe_desc D, int reset, unsigned step, StageResetArgs R, const float *g_raw, const float *g_prev, float *g_st,
                                   float *g_est_in, float *g_rpy, float *g_ground_in, unsigned *g_tick);
 
+// qr_dataflow_kernel.hip: one lane per robot; the operator's command, the getters between the trot's stages, the motor command of the MPC mode
+__global__ void qr_command_kernel(int n, qrgpu_command_desc D, int reset, StageResetArgs R, const float *g_joy, float *g_st, float *g_des, float *g_fe, float *g_fh,
+                                  float *g_sv, float *g_sc);
+__global__ void qr_trot_inputs_kernel(int n, const float *g_est_in, const float *g_est_out, const float *g_rpy, const float *g_gait_out, const float *g_gait_state,
+                                      float *g_fe, float *g_fh, float *g_sw, float *g_est_w);
+__global__ void qr_mpc_command_kernel(int n, qrgpu_mpc_command_desc D, int reset, StageResetArgs R, const float *g_tau, const float *g_qdes, const float *g_sw,
+                                      const float *g_gait_out, const float *g_gait_state, int *g_mem, float *g_cmd);
+
 }  // namespace qrgpu

@@ -283,6 +283,36 @@ def observe_desc(variant="sim", **fields):
     return _set_fields(d, fields)
 
 
+JOY_ROWS, CMD_STATE_ROWS = 8, 6
+RC_HARD_CODE, RC_JOY_TROT, RC_JOY_ADVANCED_TROT, RC_JOY_WALK, RC_JOY_STAND, RC_BODY_UP, RC_BODY_DOWN, RC_EXIT = range(8)
+
+
+class command_desc_struct(C.Structure):
+    _fields_ = [("dt", C.c_float), ("filter_factor", C.c_float), ("body_height", C.c_float), ("min_velx", C.c_float), ("max_velx", C.c_float),
+                ("min_vely", C.c_float), ("max_vely", C.c_float), ("min_yawrate", C.c_float), ("max_yawrate", C.c_float), ("min_pitch", C.c_float),
+                ("max_pitch", C.c_float)]
+
+
+def command_desc(**fields):
+    """qrgpu_command_desc: qrDesiredStateCommand's constants (dt 0.002, filter factor 0.02, body height 0.28, the velocity, yaw-rate and pitch
+    clips), with any field overridden."""
+    d = command_desc_struct()
+    load_library().qrgpu_command_desc_default(C.byref(d))
+    return _set_fields(d, fields)
+
+
+class mpc_command_desc_struct(C.Structure):
+    _fields_ = [("kp", C.c_float * 12), ("kd", C.c_float * 12), ("stance_kd", C.c_float), ("early_contact_abad_kp", C.c_float), ("epilogue", C.c_int)]
+
+
+def mpc_command_desc(**fields):
+    """qrgpu_mpc_command_desc: a1_sim's motor gains (100 / 1, 2, 2), stance Kd 3.0, EARLY_CONTACT abad Kp 100.0, epilogue 0 (the EPILOGUE_* bits the
+    caller gave set_torque_epilogue), with any field overridden (scalars or sequences by name)."""
+    d = mpc_command_desc_struct()
+    load_library().qrgpu_mpc_command_desc_default(C.byref(d))
+    return _set_fields(d, fields)
+
+
 EPILOGUE_HIP_COMP, EPILOGUE_CLIP = 1, 2
 COMM_ID_BYTES = 128
 
@@ -317,7 +347,9 @@ EXPORTS = ["qrgpu_model_desc_default", "qrgpu_create", "qrgpu_destroy", "qrgpu_s
            "qrgpu_pose_plan_desc_default", "qrgpu_pose_plan_batch", "qrgpu_plant_params_default", "qrgpu_forward_dynamics_batch", "qrgpu_plant_step_batch",
            "qrgpu_plant_step_terrain_batch", "qrgpu_plant_body_desc_default", "qrgpu_plant_body_setup", "qrgpu_plant_step_body_batch",
            "qrgpu_episode_desc_default", "qrgpu_episode_step_batch", "qrgpu_set_stage_reset",
-           "qrgpu_observe_desc_default", "qrgpu_observe_state_rows", "qrgpu_observe_batch"]
+           "qrgpu_observe_desc_default", "qrgpu_observe_state_rows", "qrgpu_observe_batch",
+           "qrgpu_command_desc_default", "qrgpu_command_update_batch", "qrgpu_trot_inputs_batch", "qrgpu_mpc_command_desc_default",
+           "qrgpu_mpc_command_batch"]
 
 
 def load_library():
@@ -407,6 +439,11 @@ def load_library():
     lib.qrgpu_observe_desc_default.argtypes = [C.POINTER(observe_desc_struct), ip]; lib.qrgpu_observe_desc_default.restype = None
     lib.qrgpu_observe_state_rows.argtypes = [C.POINTER(observe_desc_struct)]
     lib.qrgpu_observe_batch.argtypes = [vp, ip, C.POINTER(observe_desc_struct), ip, C.c_uint] + [vp] * 7
+    lib.qrgpu_command_desc_default.argtypes = [C.POINTER(command_desc_struct)]; lib.qrgpu_command_desc_default.restype = None
+    lib.qrgpu_command_update_batch.argtypes = [vp, ip, C.POINTER(command_desc_struct), ip] + [vp] * 7
+    lib.qrgpu_trot_inputs_batch.argtypes = [vp, ip] + [vp] * 9
+    lib.qrgpu_mpc_command_desc_default.argtypes = [C.POINTER(mpc_command_desc_struct)]; lib.qrgpu_mpc_command_desc_default.restype = None
+    lib.qrgpu_mpc_command_batch.argtypes = [vp, ip, C.POINTER(mpc_command_desc_struct), ip] + [vp] * 7
     lib.qrgpu_vmc_force1.argtypes = [vp, ip, fp, fp, fp, fp, C.POINTER(ip)]
     lib.qrgpu_vmc_force_world1.argtypes = [vp, ip, fp, fp, fp, fp, fp, C.POINTER(ip)]
     lib.qrgpu_mpc_frontend_batch.argtypes = [vp, ip, ip, C.c_float, C.c_float] + [vp] * 6
@@ -580,6 +617,10 @@ class Context:
 
     def alloc_pinned(self, shape, dtype=np.float32):
         return PinnedArray(self, shape, dtype)
+
+    def copy_rows(self, dst, src, count, dtype=np.float32):
+        """Asynchronous device -> device copy of `count` elements on the context stream (dst, src: device pointers, e.g. DeviceArray.row())."""
+        self._chk(self._lib.qrgpu_memcpy_async(self._h, _dp(dst), _dp(src), int(count) * np.dtype(dtype).itemsize, 2))
 
     def mark(self, index):
         """Record timing mark `index` on the context stream."""
@@ -861,6 +902,27 @@ class Context:
         previous tick (None: the base position is (0, 0, base_height)).  step: the caller's loop count, the sensor noise's counter."""
         self._chk(self._lib.qrgpu_observe_batch(self._h, n, C.byref(desc), int(bool(reset)), int(step) & 0xffffffff, _dp(raw), _dp(est_out_prev),
                                                 _dp(obs_state), _dp(est_in), _dp(rpy), _dp(ground_in), _dp(tick)))
+
+    def command_update(self, n, desc, joy, cmd_state, state_des=None, fe_in=None, fh_in=None, swing_vel_in=None, stance_cmd=None, reset=0):
+        """qrDesiredStateCommand::Update of n robots (desc: command_desc()): joy [JOY_ROWS][n] = joyCmdVx, Vy, Vz, RollRate, PitchRate, YawRate,
+        joycmdBodyHeight, joyCtrlState (an RC_* value) -> state_des [12][n] and the rows the other stages read: fe_in 0-5, fh_in 16-20, swing_vel_in
+        23-26, stance_cmd 0-6 (each optional).  cmd_state [CMD_STATE_ROWS][n] is the filter's memory; reset 1 starts every robot from zeros, a
+        stage-reset binding's mask does so per robot."""
+        self._chk(self._lib.qrgpu_command_update_batch(self._h, n, C.byref(desc), int(reset), _dp(joy), _dp(cmd_state), _dp(state_des), _dp(fe_in), _dp(fh_in),
+                                                       _dp(swing_vel_in), _dp(stance_cmd)))
+
+    def trot_inputs(self, n, est_in, est_out, rpy, gait_out, gait_state=None, fe_in=None, fh_in=None, swing_in=None, est_in_next=None):
+        """The getters between the trot's stages: fe_in rows 6-25 and 38-41, fh_in 21-45, swing_in 36-57 and rows 41-44 of est_in_next (usually
+        est_in itself) from est_in, est_out, rpy [3][n], gait_out [24][n] and gait_state (needed with fe_in).  Each output is optional."""
+        self._chk(self._lib.qrgpu_trot_inputs_batch(self._h, n, _dp(est_in), _dp(est_out), _dp(rpy), _dp(gait_out), _dp(gait_state), _dp(fe_in), _dp(fh_in),
+                                                    _dp(swing_in), _dp(est_in_next)))
+
+    def mpc_command(self, n, desc, tau, qdes, swing_in, gait_out, gait_state, cmd_mem, motor_cmd, reset=0):
+        """The motor command of the MPC mode (desc: mpc_command_desc()): motor_cmd [60][n] = p, Kp, d, Kd, tua from the tick's tau [12][n], the swing
+        targets qdes [24][n], rows 0-3 of swing_in, gait_out and gait_state.  cmd_mem [1][n] int32: the legs with a swing entry, bit per leg; reset
+        1 clears it for every robot, a stage-reset binding's mask per robot."""
+        self._chk(self._lib.qrgpu_mpc_command_batch(self._h, n, C.byref(desc), int(reset), _dp(tau), _dp(qdes), _dp(swing_in), _dp(gait_out), _dp(gait_state),
+                                                    _dp(cmd_mem), _dp(motor_cmd)))
 
     def mpc_frontend_batch(self, n, fe_in, fe_state, traj, gait, wbc_cmd=None, mpc_updated=None, num_horizon_l=2, dt_ctrl=0.002, dt_mpc=0.06):
         """SetupCommand + Run + UpdateMPC (without the solve) of n robots: qr_mpc_stance_leg_controller.cpp:158-382."""

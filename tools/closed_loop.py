@@ -8,6 +8,7 @@ inside the loop.
   python tools/closed_loop.py --body [--terrain stairs:0.04] [--push 30]              the same loop with knee and trunk contact and joint limits
   python tools/closed_loop.py --episodes [--max-ticks 400] [--terrain plane:0.2]      episode step -> plant -> tick: robots that fall start again
   python tools/closed_loop.py --estimator [--sensor-noise 0.02]                       the tick reads the estimator chain's state, not the plant's truth
+  python tools/closed_loop.py --trot [--cmd-vx 0.15] [--cmd-yaw 0.1] [--episodes] [--terrain ...]   the MPC trot, every stage on the device
 
 The robots are dropped from z = 0.30 onto joint PD at the stand pose (400 ticks of 1 ms), shoved by up to 0.3 m/s in x and y, and handed to
 MPC + WBC: qrgpu_plant_step_batch (include/qrgpu.h) writes the ground-truth mpc_state and fb_state the tick reads, and the tick -- the plain
@@ -36,7 +37,20 @@ stage-reset binding (mask = the step's done words, ticks = ep_state) restarts th
 --sensor-noise A adds the stage's noise (accelerometer 10 A m/s^2, gyro A rad/s, q 0.1 A rad, qd A rad/s).  How the standing batch fares on the
 estimate, and how far the estimate lies from the truth, is reported, not judged; the trot in this loop and stability under noise are not claimed.
 
+--trot (implies --estimator and --body) runs the reference's MPC trot (LocomotionMode::ADVANCED_TROT with MPC + WBC) closed on the device.  After the
+settle phase each tick queues, in the order of qrLocomotionController::Update / GetAction / qrFSMStateLocomotion::Run: [episode step,] plant, observe,
+ground, estimator, pack, qrgpu_command_update_batch (the operator's command --cmd-vx / --cmd-yaw in mode JOY_ADVANCED_TROT, uploaded once), gait (its
+contacts are rows 13-16 of est_in, no copy), qrgpu_trot_inputs_batch, swing update, footholds, swing targets, MPC front-end, tick,
+qrgpu_mpc_command_batch, whose output is the motor command the plant reads.  With --episodes the stage-reset binding restarts the command filter and the
+swing-command memory of a respawned robot with the other stages' memory, and the gait runs on the robot's own clock.  The reference runs either the MPC
+or the WBC on a tick (wbcData.allowAfterMPC); here the tick runs both every tick, and the front-end re-plans the trajectory on its own cadence.  The
+run logs on the device, per tick, the tick's status words and the Kd rows of the motor command (one device-to-device copy of 12 rows), and the true state
+100 ticks before the end; they are read once, after the loop.  Whether the batch trots, drifts or falls is reported, not judged.
+
   ticks_per_s   closed-loop control ticks per second: every robot advances one tick per (plant step + controller tick)
+  trot, cmd_vx, cmd_yaw, speed_along_command_mean (world x over the last 100 ticks, m/s, robots not respawned in them: speed_robots), yaw_rate_mean,
+                tick_flagged_share (share of ticks x robots whose tick status word carries a flag), swing_legs_commanded (legs x ticks x robots that
+                carried a swing command, warm-up included; _per_robot_tick: their mean number per robot and tick), swing_flags_seen (OR of QRGPU_SW_*)
   in_band       share of the robots that end inside the stand band: |z - 0.27| <= 0.01, |x|, |y| <= 0.03, |roll|, |pitch| <= 0.03
   fallen        (--body) robots that raised PL_TRUNK_CONTACT or PL_KNEE_CONTACT at any tick of the loop, warm-up included
   nonfinite     robots whose state left the finite numbers
@@ -88,9 +102,15 @@ def main():
     ap.add_argument("--spawn-spread", type=float, default=0.05, metavar="M", help="(--episodes) spacing of the 3 x 3 grid of spawn points, metres")
     ap.add_argument("--estimator", action="store_true", help="the tick reads the estimator chain's state (plant sensor rows -> observe -> ground -> estimator -> pack), not the plant's truth")
     ap.add_argument("--sensor-noise", type=float, default=0.0, metavar="A", help="(--estimator) sensor noise: acc 10 A m/s^2, gyro A rad/s, q 0.1 A rad, qd A rad/s")
+    ap.add_argument("--trot", action="store_true", help="the MPC trot closed on the device: command, gait, data flow, swing, front-end, tick, MPC command (implies --estimator --body)")
+    ap.add_argument("--cmd-vx", type=float, default=0.0, metavar="V", help="(--trot) joyCmdVx, m/s")
+    ap.add_argument("--cmd-yaw", type=float, default=0.0, metavar="W", help="(--trot) joyCmdYawRate, rad/s")
     ap.add_argument("--profile", action="store_true", help="the run a profiler traces: fewer ticks, nothing else changed")
     a = ap.parse_args()
-    a.body = a.body or a.episodes
+    if (a.cmd_vx != 0.0 or a.cmd_yaw != 0.0) and not a.trot:
+        ap.error("--cmd-vx / --cmd-yaw need --trot")
+    a.estimator = a.estimator or a.trot
+    a.body = a.body or a.episodes or a.trot
     if a.sensor_noise != 0.0 and not a.estimator:
         ap.error("--sensor-noise needs --estimator")
     pkg = _load_pkg()
@@ -145,6 +165,20 @@ def main():
                  stamp=ctx.alloc((n,), np.uint32), gst=ctx.alloc((13, n), np.float64), est_state=ctx.alloc((nd, n), np.float64).zero(),
                  est_out=ctx.alloc((42, n)).zero(), mpc_est=ctx.alloc((28, n)), fb_est=ctx.alloc((37, n)))
 
+    if a.trot:          # the trot's stages: their memory, the arrays they hand one another, the operator's command (uploaded once)
+        q, W = pkg.qrgpu, pkg.workload
+        cdesc, mdesc, sdesc = pkg.command_desc(), pkg.mpc_command_desc(), pkg.swing_mode_desc(q.MODE_ADVANCED_TROT, terrain=0)
+        gcfg, fcfg = W.gait_cfg(), W.foothold_cfg("a1")
+        joy = np.zeros((q.JOY_ROWS, n), np.float32); joy[0] = a.cmd_vx; joy[5] = a.cmd_yaw; joy[6] = cdesc.body_height; joy[7] = q.RC_JOY_ADVANCED_TROT
+        swing_in = np.zeros((58, n), np.float32)
+        swing_in[8:12] = np.float32(gcfg[0]) / np.float32(gcfg[4]) - np.float32(gcfg[0])       # swingDuration = stanceDuration / dutyFactor - stanceDuration
+        d.update(joy=ctx.alloc((q.JOY_ROWS, n)).upload(joy), cmd_state=ctx.alloc((q.CMD_STATE_ROWS, n)), state_des=ctx.alloc((12, n)),
+                 fe_in=ctx.alloc((64, n)).zero(), fe_state=ctx.alloc((8, n)), fh_in=ctx.alloc((46, n)).zero(), swing_in=ctx.alloc((58, n)).upload(swing_in),
+                 gait_state=ctx.alloc((52, n)), gait_out=ctx.alloc((24, n)), swing_state=ctx.alloc((q.SWING_STATE_FLOATS, n)),
+                 swing_flags=ctx.alloc((n,), np.int32), qdes=ctx.alloc((24, n)).zero(), tau=ctx.alloc((12, n)), cmd_mem=ctx.alloc((1, n), np.int32),
+                 updated=ctx.alloc((n,), np.int32), tick_log=ctx.alloc((ticks + 20, n), np.int32).zero(), kd_log=ctx.alloc((ticks + 20, 12, n)),
+                 fb_then=ctx.alloc_pinned((37, n)))
+
     def plant(par, **out):
         if a.body:
             ctx.plant_step_body_batch(n, par, tdesc, d["height"], d["fb"], d["cmd"], base_push=d["push"], terrain_out=d["tout"], body_out=d["bout"], **out)
@@ -167,8 +201,12 @@ def main():
     ctx.set_warm_start(True)
     params = pkg.plant_params(dt=0.002, substeps=a.substeps)
     tau = d["cmd"].row(48)
+    if a.trot:          # MPCStanceLegController::Reset on the settled robot: yawDesTrue, posDesiredinWorld from the pose at hand, the counter at 0
+        fst = np.zeros((8, n), np.float32)
+        fst[3] = np.arctan2(2 * (fb[0] * fb[3] + fb[1] * fb[2]), 1 - 2 * (fb[2] ** 2 + fb[3] ** 2)); fst[4:7] = fb[4:7]
+        d["fe_state"].upload(fst)
 
-    done = [0]
+    done, total = [0], [20 + ticks]
     if a.episodes:      # episode 0 is the state at hand: its spawn rows written here, not drawn
         stats = np.zeros((pkg.qrgpu.EPISODE_STATS_ROWS, n), np.float32); stats[0:3] = fb[4:7]; stats[8] = 0.30
         d["ep_stats"].upload(stats)
@@ -191,7 +229,24 @@ def main():
                 ctx.estimator_update_batch(n, ecfg, d["est_in"], d["stamp"], d["est_state"], d["est_out"])
                 ctx.pack_state_batch(n, com, d["est_in"], d["est_out"], d["rpy"], d["mpc_est"], d["fb_est"])
             done[0] += 1
-            if a.estimator:
+            if a.trot:                        # qrLocomotionController::Update / GetAction, qrFSMStateLocomotion::Run, in the reference's order
+                k = done[0] - 1
+                t = float(np.float32(k) * np.float32(0.002))                   # (under --episodes the gait runs on the binding's per-robot clock)
+                ctx.command_update(n, cdesc, d["joy"], d["cmd_state"], state_des=d["state_des"], fe_in=d["fe_in"], fh_in=d["fh_in"], reset=int(first))
+                ctx.gait_update_batch(n, gcfg, t, d["est_in"].row(13), d["gait_state"], d["gait_out"], d["fe_in"], reset=first)
+                ctx.trot_inputs(n, d["est_in"], d["est_out"], d["rpy"], d["gait_out"], gait_state=d["gait_state"], fe_in=d["fe_in"], fh_in=d["fh_in"],
+                                swing_in=d["swing_in"], est_in_next=d["est_in"])
+                ctx.swing_update_batch(n, sdesc, d["est_in"], d["est_out"], d["gait_out"], d["swing_state"], d["swing_flags"], gait_state=d["gait_state"],
+                                       swing_in=d["swing_in"], fe_in=d["fe_in"], reset=2 if first else 0)
+                ctx.footholds_batch(n, fcfg, d["fh_in"], d["swing_in"], gait_state=d["gait_state"], gait_out=d["gait_out"])
+                ctx.swing_targets_batch(n, ecfg, d["swing_in"], wbc_cmd=d["wcmd"], foot_target_world=d["fe_in"].row(26), qdes=d["qdes"])
+                ctx.mpc_frontend_batch(n, d["fe_in"], d["fe_state"], d["traj"], d["gait"], d["wcmd"], d["updated"])
+                ctx.tick_batch(n, d["mpc_est"], d["traj"], d["gait"], d["fb_est"], d["wcmd"], d["prev"], d["force"], d["tau"], d["tick_log"].row(k))
+                ctx.mpc_command(n, mdesc, d["tau"], d["qdes"], d["swing_in"], d["gait_out"], d["gait_state"], d["cmd_mem"], d["cmd"], reset=int(first))
+                ctx.copy_rows(d["kd_log"].row(k), d["cmd"].row(36), 12 * n)    # the report's log: Kd of this tick's command (a swing command carries the motor's)
+                if k == total[0] - 101:
+                    d["fb"].copy_to_pinned(d["fb_then"])                       # the truth 100 ticks before the end, for the mean speed
+            elif a.estimator:
                 ctx.tick_batch(n, d["mpc_est"], d["traj"], d["gait"], d["fb_est"], d["wcmd"], d["prev"], d["force"], tau, d["tick_status"])
             else:
                 ctx.tick_batch(n, d["mpc"], d["traj"], d["gait"], d["fb"], d["wcmd"], d["prev"], d["force"], tau, d["tick_status"])
@@ -205,7 +260,8 @@ def main():
     fb = d["fb"].download()
     rp = _rpy(fb[0:4].T)
     ok = (np.abs(fb[6] - HEIGHT) <= 0.01) & (np.abs(fb[4:6]).max(0) <= 0.03) & (np.abs(rp).max(1) <= 0.03)
-    tick_flags = pkg.status_flags(d["tick_status"].download())
+    tick_log = d["tick_log"].download() if a.trot else None
+    tick_flags = pkg.status_flags(tick_log[-1] if a.trot else d["tick_status"].download())
     log = d["status_log"].download() if a.body else None
     plant_flags = log[-1] if a.body else d["plant_status"].download()
     res = dict(metric="closed_loop_ticks_per_s", value=ticks / sec, robot_ticks_per_s=n * ticks / sec, ms_per_tick=1e3 * sec / ticks, robots=n, ticks=ticks,
@@ -244,6 +300,23 @@ def main():
         res.update(episodes=True, max_ticks=a.max_ticks, episodes_finished=int(st[4].sum() + st[5].sum()), episodes_failed=int(st[4].sum()),
                    episodes_timed_out=int(st[5].sum()), by_reason={nm: int(((dl >> k) & 1).sum()) for k, nm in enumerate(names)},
                    mean_episode_ticks=float(np.mean(lengths)) if lengths else None, alive_at_end=float(alive.mean()))
+    if a.trot:        # what the trot did: reported, not judged
+        kd = d["kd_log"].download()[:, 0::3]                              # [tick][leg][robot]: the abad's Kd, the motor's own on a swing command
+        swing = kd != np.float32(mdesc.stance_kd)
+        res.update(trot=True, cmd_vx=a.cmd_vx, cmd_yaw=a.cmd_yaw, tick_flagged_share=float((pkg.status_flags(tick_log) != 0).mean()),
+                   swing_legs_commanded=int(swing.sum()), swing_legs_commanded_per_robot_tick=float(swing.sum(1).mean()),
+                   swing_flags_seen=int(np.bitwise_or.reduce(d["swing_flags"].download())))
+        if ticks >= 81:   # mean base speed along the command over the last 100 ticks, from the plant's truth; robots respawned in that window left out
+            then = d["fb_then"].array
+            calm = np.isfinite(fb).all(0) & np.isfinite(then).all(0)
+            if a.episodes:
+                calm &= (d["done_log"].download()[total[0] - 100:total[0]] & pkg.qrgpu.EP_REASONS).max(0) == 0
+            c = np.array([a.cmd_vx, 0.0]) if a.cmd_vx != 0.0 else np.array([1.0, 0.0])
+            v = ((fb[4:6] - then[4:6]) / (100 * 0.002) * (c / np.linalg.norm(c))[:, None]).sum(0)
+            res.update(speed_along_command_mean=float(v[calm].mean()) if calm.any() else None, speed_robots=int(calm.sum()),
+                       yaw_rate_mean=float(((np.arctan2(2 * (fb[0] * fb[3] + fb[1] * fb[2]), 1 - 2 * (fb[2] ** 2 + fb[3] ** 2)) -
+                                             np.arctan2(2 * (then[0] * then[3] + then[1] * then[2]), 1 - 2 * (then[2] ** 2 + then[3] ** 2)))[calm] / 0.2).mean())
+                       if calm.any() else None)
     print(json.dumps(res))
     ctx.close()
 
