@@ -36,6 +36,8 @@
  *   qrgpu_stance_tick_batch <- TorqueStanceLegController::GetAction (:480-545) + that merge: front-end, force-balance QP, motor commands
  *   qrgpu_tick_batch       <- one MPC solve + one WBC tick per robot, WBC fed with that MPC's Fr_des
  *                             (QS/fsm/qr_fsm_state_locomotion.cpp:130-158 without the MPC/WBC time-slicing)
+ *   qrgpu_tick_cadence_batch <- the same state WITH the time-slicing: per robot the MPC on the ticks that re-plan, the held force through the
+ *                             current Jacobian and the WBC on every other tick (wbcData.allowAfterMPC), from a device mask
  *   qrgpu_set_torque_epilogue <- the motor-command tail of that state: abad compensation (:141-151) and the +-23 N m clip
  *                             (QS/fsm/qr_safety_checker.cpp:48-66)
  *   qrgpu_comm_* / qrgpu_allgather_tau <- no reference equivalent (the reference runs one robot per process): the all-gather of torques
@@ -302,6 +304,25 @@ int qrgpu_wbc_run_batch(qrgpu_ctx *ctx, int n, const int *d_type_id, const float
 int qrgpu_tick_batch(qrgpu_ctx *ctx, int n, const int *d_type_id, const float *d_mpc_state,
                      const float *d_traj, const float *d_gait, const float *d_fb_state,
                      const float *d_wbc_cmd, float *d_prev_ori, float *d_force, float *d_tau, float *d_qdes, int *d_status);
+/* The tick on the reference's cadence: per robot EITHER the MPC OR the WBC (wbcData.allowAfterMPC; qr_mpc_stance_leg_controller.cpp:337-382,
+ * :129-156, :305-333; qr_fsm_state_locomotion.cpp:130-158), chosen by a device mask -- d_mpc_updated [n], the array qrgpu_mpc_frontend_batch
+ * writes; any non-zero word means the robot is due.  d_force [12][n] and d_hold [12][n] are MEMORY: the caller's, required, carried from call to
+ * call.  d_force is the world-frame f of the robot's last solve (what qrgpu_tick_batch writes; the WBC's Fr_des on held ticks), d_hold the
+ * base-frame f_ff = -R^T f with R taken at that solve.  NULL for d_mpc_updated, d_force or d_hold: QRGPU_ERR_BAD_ARG, nothing is launched.
+ *   due robot:   the MPC solve as in qrgpu_mpc_solve_batch.  d_force and d_hold are rewritten; d_tau = J^T f_ff on all legs with the context's torque
+ *                epilogue on every motor, as qrgpu_mpc_solve_batch applies it; d_status is the solve's word.  The WBC does not touch the robot: its
+ *                d_prev_ori column and d_qdes rows stay as they were.
+ *   held robot:  no solve: d_force, d_hold, the warm-start words and the cost word are untouched.  d_tau = J(q_now)^T d_hold on all legs, then the
+ *                WBC as in qrgpu_tick_batch: Fr_des from d_force, stance legs overwritten, the epilogue after the merge; d_qdes (may be NULL) is
+ *                written.  d_status is the WBC's bits over an MPC part of 0 with iteration count 0 -- that count is how a held tick reads; there
+ *                is no status bit for it.
+ * Always the serial form on the context's stream, whatever qrgpu_set_tick_pipeline and qrgpu_set_tick_overlap say; no wait, poll or gate of its
+ * own, and nothing is read back to the host: which robots are due is known on the device alone (qrgpu_set_stage_reset gives every robot its own
+ * clock).  qrgpu_tick_batch remains the tick of the pipelined and overlapped forms. */
+int qrgpu_tick_cadence_batch(qrgpu_ctx *ctx, int n, const int *d_type_id, const int *d_mpc_updated,
+                             const float *d_mpc_state, const float *d_traj, const float *d_gait, const float *d_fb_state,
+                             const float *d_wbc_cmd, float *d_prev_ori, float *d_force, float *d_hold,
+                             float *d_tau, float *d_qdes, int *d_status);
 
 /* Motor-command tail of the locomotion state (K14), off by default -- the single-robot drop-in keeps the FSM doing it:
  *   QRGPU_EPILOGUE_HIP_COMP  the +-0.9 N m abad compensation of qrFSMStateLocomotion::Run (QS/fsm/qr_fsm_state_locomotion.cpp:141-151:

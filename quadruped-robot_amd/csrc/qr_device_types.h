@@ -145,6 +145,9 @@ struct MpcIO {
     float *dbgH, *dbgG, *g_force_wbc;
     int force_stride;
     long long *dbgT;
+    // Cadenced tick (qrgpu_tick_cadence_batch): [n], a robot whose word is zero is not solved by any launch of the call -- nothing of it is read or
+    // written, its warm-start and cost words included.  Null: every robot.
+    const int *due;
 };
 
 // Force-balance QP: ComputeContactForce's arguments that do not change per tick, per type.
@@ -245,6 +248,9 @@ struct WbcPipe {
     // the robots whose solves the main pass has started by then.  One launch behind one gate starts when the main pass's LAST workgroup has: at 8192
     // robots that is 1.2 ms into a 1.65 ms tick, and 0.34 ms of WBC trail the last solve.
     int slot_base;
+    // Cadenced tick (qrgpu_tick_cadence_batch, serial form only): [n], a robot whose word is non-zero -- it was solved this tick -- is left before
+    // anything of it is read or written.  Null: every robot.
+    const int *skip;
 };
 
 // WBC per-type constants (device buffer): BuildDynamicModel (QS/robots/qr_robot_a1_sim.cpp:176-343)

@@ -149,4 +149,13 @@ __global__ void qr_trot_inputs_kernel(int n, const float *g_est_in, const float 
 __global__ void qr_mpc_command_kernel(int n, qrgpu_mpc_command_desc D, int reset, StageResetArgs R, const float *g_tau, const float *g_qdes, const float *g_sw,
                                       const float *g_gait_out, const float *g_gait_state, int *g_mem, float *g_cmd);
 
+// qr_cadence_kernel.hip: one lane per robot; between the MPC and the WBC launch of the cadenced tick: the kept base-frame force of the robots just
+// solved, the torques and the status word of the others.  The leg geometry per type is the MPC launch's (MpcType).
+struct CadenceLegs {
+    float hip_l[QRGPU_MAX_TYPES], upper_l[QRGPU_MAX_TYPES], lower_l[QRGPU_MAX_TYPES];
+    int type_ready;       // bit t: type t was set up
+};
+__global__ void qr_cadence_kernel(int n, CadenceLegs L, const int *g_type, const int *g_due, const float *g_mpc_state, const float *g_fb_state, const float *g_force,
+                                  float *g_hold, float *g_tau, int *g_status);
+
 }  // namespace qrgpu

@@ -1728,6 +1728,14 @@ __device__ __forceinline__ void mpc_solve_robot(const MpcLaunch &P, const MpcIO 
 #undef QR_SYNC
 #undef QR_IDLE
 
+// Cadenced tick (MpcIO::due): a robot that is not due this tick is solved by no launch of the call -- nothing of it is read or written, its outputs,
+// its warm-start words and its cost word keep what its last solve left.  Asked at every site where a workgroup picks its robot, in front of the solve
+// and behind every counter the workgroup bumps (started, main_started, planned_done, main_done, the queue heads: a gate waits on them); not inside
+// mpc_solve_robot.  The half-CU list kernel of the overlapped ticks carries no test (64 bytes of scratch per lane with it, in either place:
+// profiles/cadence_isa_compare.txt); every other instantiation keeps its scratch and its occupancy.  The word is
+// the same for the whole workgroup: read through one lane, the branch is a scalar one whichever way the caller came by the robot's index.
+__device__ __forceinline__ bool mpc_is_due(const MpcIO &io, int rid) { return !io.due || __builtin_amdgcn_readfirstlane(io.due[rid]) != 0; }
+
 // Launch wrappers (one inlined copy of the solve each).
 //   LIST = false, main pass: workgroup b solves the robot of slot xcd_robot_index(b) (through the longest-first order when there is one);
 //   LIST = true:  workgroups 0-7 first sort the next call's dispatch order, then workgroup b re-solves entries b, b + grid, b + 2 grid ...
@@ -1793,7 +1801,10 @@ void qr_mpc_kernel(MpcLaunch P, MpcIO io)
         cnt = cnt < P.n ? cnt : P.n;
         if (P.plan_only) return;                 // (overlapped tick at h > 11: the tick's planned launch empties the rescue list, MpcLaunch::main_done)
         for (int e = blockIdx.x; e < cnt; e += gridDim.x) {
-            mpc_solve_robot<MAXB, BIG, NTHR, false, H16>(P, io, ld_xt(list + e, P.solved != nullptr), smem);
+            const int rid = ld_xt(list + e, P.solved != nullptr);
+            // (the half-CU list kernel -- MINW = 2 -- runs in overlapped ticks only, which a cadenced tick never is: it carries no mask test, and
+            //  keeps the register allocation it had)
+            if (MINW == 2 || mpc_is_due(io, rid)) mpc_solve_robot<MAXB, BIG, NTHR, false, H16>(P, io, rid, smem);
             __syncthreads();                           // every wave is out of the solve before the LDS is carved again
         }
         if (QR_P_TL && threadIdx.x == 0 && P.rescue_mode == 1) atomicMax(QR_P_TL + QR_TL_TICKS + (P.done_epoch & 63u) * 8 + 6, wall_clock64());
@@ -1878,7 +1889,7 @@ void qr_mpc_kernel(MpcLaunch P, MpcIO io)
                         const int rid = *sNext;
                         __syncthreads();
                         if (rid < 0) break;
-                        mpc_solve_robot<MAXB, BIG, NTHR, true>(P, io, rid, smem);
+                        if (mpc_is_due(io, rid)) mpc_solve_robot<MAXB, BIG, NTHR, true>(P, io, rid, smem);
                         __syncthreads();
                     }
                     tell_done();
@@ -1887,7 +1898,8 @@ void qr_mpc_kernel(MpcLaunch P, MpcIO io)
                 if (P.planned_stride) {
                     for (int e = blockIdx.x; e < cnt; e += gridDim.x) {
                         if (threadIdx.x == 0) QR_TRACE(ld_xt(P.pre_list + e, P.solved != nullptr), 8);
-                        mpc_solve_robot<MAXB, BIG, NTHR, true>(P, io, ld_xt(P.pre_list + e, P.solved != nullptr), smem);
+                        const int rid = ld_xt(P.pre_list + e, P.solved != nullptr);
+                        if (mpc_is_due(io, rid)) mpc_solve_robot<MAXB, BIG, NTHR, true>(P, io, rid, smem);
                         __syncthreads();
                     }
                     if (P.main_done && P.rescue_taken && P.rescue_list) {
@@ -1908,7 +1920,8 @@ void qr_mpc_kernel(MpcLaunch P, MpcIO io)
                 __syncthreads();                       // (every wave's hand-over stores are out before wave 0 can tell anybody)
             }
             if ((int)blockIdx.x >= cnt) { tell_done(); return; }
-            mpc_solve_robot<MAXB, BIG, NTHR, false, H16>(P, io, ld_xt(P.pre_list + blockIdx.x, P.solved != nullptr), smem);
+            const int rid = ld_xt(P.pre_list + blockIdx.x, P.solved != nullptr);
+            if (mpc_is_due(io, rid)) mpc_solve_robot<MAXB, BIG, NTHR, false, H16>(P, io, rid, smem);
             tell_done();                               // (wave 0 is the last to return from the solve and the one that stored its results)
             return;
         }
@@ -1922,9 +1935,9 @@ void qr_mpc_kernel(MpcLaunch P, MpcIO io)
             const int rid = P.order ? ld_xt(P.order + slot, P.main_done != nullptr) : slot;       // same XCD chunk either way (the order permutes inside a chunk)
             // solved by the planned list launch, beside this one -- unless that launch's gate gave up waiting for this one's stream (plan_abort)
             if (threadIdx.x == 0) QR_TRACE(rid, 1);
-            if (!(P.skip && ld_xt(P.skip + rid, P.main_done != nullptr) && !(P.plan_abort && *P.plan_abort == P.plan_epoch)))
-                mpc_solve_robot<MAXB, BIG, NTHR, false, H16>(P, io, rid, smem);
-            else if (threadIdx.x == 0) QR_TRACE(rid, 2);
+            if (!(P.skip && ld_xt(P.skip + rid, P.main_done != nullptr) && !(P.plan_abort && *P.plan_abort == P.plan_epoch))) {
+                if (mpc_is_due(io, rid)) mpc_solve_robot<MAXB, BIG, NTHR, false, H16>(P, io, rid, smem);
+            } else if (threadIdx.x == 0) QR_TRACE(rid, 2);
         }
         // (overlapped ticks at h > 11: the planned launch's workgroups take what this pass leaves on the rescue list -- thread 0 is the one that
         //  appends -- and go home when every workgroup of this launch has left: MpcLaunch::main_done)
@@ -1975,7 +1988,7 @@ void qr_mpc_persist_kernel(MpcLaunch P, MpcIO io)
         const int rid = *sNext;
         __syncthreads();
         if (rid < 0) return;
-        mpc_solve_robot<MAXB, BIG, NTHR, true>(P, io, rid, smem);
+        if (mpc_is_due(io, rid)) mpc_solve_robot<MAXB, BIG, NTHR, true>(P, io, rid, smem);
         __syncthreads();                               // every wave is out of the solve before the LDS is carved again
     }
 }

@@ -612,6 +612,8 @@ void qr_wbc_kernel(int n, const WbcConst *__restrict__ types, const int *__restr
     if (!pipe.second && gate_gave_up) { wbc_signal_done(pipe.finished, lane); return; }
     if (QW_P_TL && threadIdx.x == 0 && !pipe.second) atomicMin(QW_P_TL + QR_TL_TICKS + (pipe.epoch & 63u) * 8 + 3, wall_clock64());
     if (pipe.order && !pipe.second) rid = pipe.order[rid];        // (a permutation inside the XCD chunk: qr_mpc_kernel.hip, finish_order_chunk)
+    // (cadenced tick, serial form: a robot solved this tick commands its MPC torques; nothing of it is read or written here -- WbcPipe::skip)
+    if (pipe.skip && __builtin_amdgcn_readfirstlane(pipe.skip[rid]) != 0) return;
     if (QW_P_TLR && threadIdx.x == 0 && !pipe.second) QW_P_TLR[rid] = (int)wall_clock64();
     int tyid = type_id ? type_id[rid] : 0;
     const bool bad_type = resolve_type(tyid, type_ready);      // computed with the first valid type, flagged QRGPU_ST_BAD_TYPE

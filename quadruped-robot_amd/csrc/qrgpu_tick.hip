@@ -1,6 +1,7 @@
 // ============================================================================
 // libqrgpu.so host side: the fused tick (MPC launches + WBC launch) in its three forms -- serial, pipelined, overlapped --
-// and the switch, fence and counters of the overlapped form.  The MPC launches themselves: qrgpu_mpc.hip.
+// and the switch, fence and counters of the overlapped form; the cadenced tick (per robot the MPC or the WBC, always serial).  The MPC launches
+// themselves: qrgpu_mpc.hip.
 // ============================================================================
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -239,6 +240,40 @@ int qrgpu_tick_batch(qrgpu_ctx *c, int n, const int *d_type_id, const float *d_m
         c->ov_chain = true; c->ov_n = n; c->ov_epoch = epoch; c->ov_main_total = c->main_started_total; c->ov_prev_ori = (const void *)d_prev_ori; c->ov_lane_last = lane_id;
     }
     return QRGPU_OK;
+}
+
+// The tick on the reference's cadence (include/qrgpu.h): per robot either the MPC (d_mpc_updated[i] != 0) or the WBC.  Always the serial form, on
+// the context's stream: the MPC launches with the mask and the context's torque tail (only due robots are solved and write d_tau), the cadence
+// kernel (kept force of the due robots; torques and status word of the others), the WBC launch with the same mask as its skip list.  The pipelined
+// and overlapped forms rest on every robot's solve raising a flag and on gates that count workgroups: not for a tick in which most robots are
+// not solved.  Nothing is read back: which robots are due is known on the device alone.
+int qrgpu_tick_cadence_batch(qrgpu_ctx *c, int n, const int *d_type_id, const int *d_mpc_updated, const float *d_mpc_state, const float *d_traj,
+                             const float *d_gait, const float *d_fb_state, const float *d_wbc_cmd, float *d_prev_ori, float *d_force, float *d_hold,
+                             float *d_tau, float *d_qdes, int *d_status)
+{
+    if (!c || !d_mpc_updated || !d_force || !d_hold) return QRGPU_ERR_BAD_ARG;
+    if (!d_mpc_state || !d_traj || !d_gait || !d_fb_state || !d_wbc_cmd || !d_tau || !d_prev_ori) return QRGPU_ERR_BAD_ARG;
+    if (n <= 0 || n > c->max_batch) return QRGPU_ERR_BAD_ARG;
+    // (both launches' set-up rules before the first launch: a call that fails has launched nothing)
+    if (!(d_type_id ? (ready_mask(c->mpc_ready) != 0 && ready_mask(c->wbc_ready) != 0) : (c->mpc_ready[0] && c->wbc_ready[0]))) return QRGPU_ERR_NOT_SETUP;
+    HIPCHK(c, hipSetDevice(c->device));
+    c->last_tick_piped = false;
+    const TickArgs a{n, d_type_id, d_mpc_state, d_traj, d_gait, d_fb_state, d_wbc_cmd, d_prev_ori, d_force, d_tau, d_qdes, d_status};
+    MpcIO io = mpc_io(d_type_id, d_mpc_state, d_traj, d_gait, d_fb_state + (size_t)13 * n, d_force, d_tau, d_status);
+    io.due = d_mpc_updated;
+    MpcOpts mo;
+    mo.epilogue = c->epilogue;
+    int rc = launch_mpc(c, n, io, mo);
+    if (rc) return rc;
+    CadenceLegs L{};
+    for (int t = 0; t < QRGPU_MAX_TYPES; ++t) { L.hip_l[t] = c->mpc.type[t].hip_l; L.upper_l[t] = c->mpc.type[t].upper_l; L.lower_l[t] = c->mpc.type[t].lower_l; }
+    L.type_ready = ready_mask(c->mpc_ready);
+    hipLaunchKernelGGL(qr_cadence_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, n, L, d_type_id, d_mpc_updated, d_mpc_state, d_fb_state, (const float *)d_force, d_hold,
+                       d_tau, d_status);
+    HIPCHK(c, hipGetLastError());
+    WbcOpts o = tick_wbc_opts(c, a, d_force);
+    o.pipe.skip = d_mpc_updated;
+    return launch_wbc(c, n, d_type_id, d_fb_state, d_wbc_cmd, d_prev_ori, d_tau, d_qdes, d_status, o);
 }
 
 }  // extern "C"

@@ -349,7 +349,7 @@ EXPORTS = ["qrgpu_model_desc_default", "qrgpu_create", "qrgpu_destroy", "qrgpu_s
            "qrgpu_episode_desc_default", "qrgpu_episode_step_batch", "qrgpu_set_stage_reset",
            "qrgpu_observe_desc_default", "qrgpu_observe_state_rows", "qrgpu_observe_batch",
            "qrgpu_command_desc_default", "qrgpu_command_update_batch", "qrgpu_trot_inputs_batch", "qrgpu_mpc_command_desc_default",
-           "qrgpu_mpc_command_batch"]
+           "qrgpu_mpc_command_batch", "qrgpu_tick_cadence_batch"]
 
 
 def load_library():
@@ -386,6 +386,8 @@ def load_library():
     lib.qrgpu_wbc_run_batch.argtypes = [vp, ip] + [vp] * 7
     lib.qrgpu_wbc_inspect_batch.argtypes = [vp, ip] + [vp] * 7
     lib.qrgpu_tick_batch.argtypes = [vp, ip] + [vp] * 11
+    if hasattr(lib, "qrgpu_tick_cadence_batch"):           # (an older build named by QRGPU_LIB for an A/B run has no cadenced tick)
+        lib.qrgpu_tick_cadence_batch.argtypes = [vp, ip] + [vp] * 13
     lib.qrgpu_set_tick_overlap.argtypes = [vp, ip]
     lib.qrgpu_tick_fence.argtypes = [vp]
     lib.qrgpu_tick_overlap_stats.argtypes = [vp, C.POINTER(ip), C.POINTER(ip)]
@@ -649,6 +651,13 @@ class Context:
         """qdes [24][n]: desiredJPos / desiredJVel of the kinematic projection (K12); None skips that projection."""
         self._chk(self._lib.qrgpu_tick_batch(self._h, n, _dp(type_id), _dp(mpc_state), _dp(traj), _dp(gait), _dp(fb_state),
                                              _dp(wbc_cmd), _dp(prev_ori), _dp(force), _dp(tau), _dp(qdes), _dp(status)))
+
+    def tick_cadence_batch(self, n, updated, mpc_state, traj, gait, fb_state, wbc_cmd, prev_ori, force, hold, tau, status=None, qdes=None, type_id=None):
+        """The tick on the reference's cadence: robots whose word of `updated` [n] (int32, what mpc_frontend_batch writes) is non-zero are solved and
+        command their MPC torques, the others command the held base-frame force through the current Jacobian and run the WBC.  force and hold
+        [12][n] are memory carried from call to call (include/qrgpu.h).  Always the serial form on the context's stream."""
+        self._chk(self._lib.qrgpu_tick_cadence_batch(self._h, n, _dp(type_id), _dp(updated), _dp(mpc_state), _dp(traj), _dp(gait), _dp(fb_state),
+                                                     _dp(wbc_cmd), _dp(prev_ori), _dp(force), _dp(hold), _dp(tau), _dp(qdes), _dp(status)))
 
     def set_tick_pipeline(self, on=True):
         """WBC launch of a tick beside its MPC launches (default) or behind them."""

@@ -9,6 +9,7 @@ inside the loop.
   python tools/closed_loop.py --episodes [--max-ticks 400] [--terrain plane:0.2]      episode step -> plant -> tick: robots that fall start again
   python tools/closed_loop.py --estimator [--sensor-noise 0.02]                       the tick reads the estimator chain's state, not the plant's truth
   python tools/closed_loop.py --trot [--cmd-vx 0.15] [--cmd-yaw 0.1] [--episodes] [--terrain ...]   the MPC trot, every stage on the device
+  python tools/closed_loop.py --trot --cadence [...]                                  the same with the tick on the reference's cadence: MPC or WBC per robot
 
 The robots are dropped from z = 0.30 onto joint PD at the stand pose (400 ticks of 1 ms), shoved by up to 0.3 m/s in x and y, and handed to
 MPC + WBC: qrgpu_plant_step_batch (include/qrgpu.h) writes the ground-truth mpc_state and fb_state the tick reads, and the tick -- the plain
@@ -43,7 +44,10 @@ ground, estimator, pack, qrgpu_command_update_batch (the operator's command --cm
 contacts are rows 13-16 of est_in, no copy), qrgpu_trot_inputs_batch, swing update, footholds, swing targets, MPC front-end, tick,
 qrgpu_mpc_command_batch, whose output is the motor command the plant reads.  With --episodes the stage-reset binding restarts the command filter and the
 swing-command memory of a respawned robot with the other stages' memory, and the gait runs on the robot's own clock.  The reference runs either the MPC
-or the WBC on a tick (wbcData.allowAfterMPC); here the tick runs both every tick, and the front-end re-plans the trajectory on its own cadence.  The
+or the WBC on a tick (wbcData.allowAfterMPC); the plain --trot tick runs both every tick, and the front-end re-plans the trajectory on its own cadence.
+--cadence (needs --trot) runs the reference's tick instead: qrgpu_tick_cadence_batch with the `updated` array the front-end fills -- a robot that
+re-plans is solved and commands J^T f_ff, every other robot commands its held f_ff through the current Jacobian and runs the WBC on the held Fr_des.
+The mask never leaves the device; its mean over the timed ticks is logged there and read once, after the loop (mpc_due_share).  The
 run logs on the device, per tick, the tick's status words and the Kd rows of the motor command (one device-to-device copy of 12 rows), and the true state
 100 ticks before the end; they are read once, after the loop.  Whether the batch trots, drifts or falls is reported, not judged.
 
@@ -51,6 +55,7 @@ run logs on the device, per tick, the tick's status words and the Kd rows of the
   trot, cmd_vx, cmd_yaw, speed_along_command_mean (world x over the last 100 ticks, m/s, robots not respawned in them: speed_robots), yaw_rate_mean,
                 tick_flagged_share (share of ticks x robots whose tick status word carries a flag), swing_legs_commanded (legs x ticks x robots that
                 carried a swing command, warm-up included; _per_robot_tick: their mean number per robot and tick), swing_flags_seen (OR of QRGPU_SW_*)
+  cadence, mpc_due_share   (--cadence) true; the share of robots x timed ticks that were solved (1 / the front-end's period once the first 50 ticks are over)
   in_band       share of the robots that end inside the stand band: |z - 0.27| <= 0.01, |x|, |y| <= 0.03, |roll|, |pitch| <= 0.03
   fallen        (--body) robots that raised PL_TRUNK_CONTACT or PL_KNEE_CONTACT at any tick of the loop, warm-up included
   nonfinite     robots whose state left the finite numbers
@@ -105,10 +110,13 @@ def main():
     ap.add_argument("--trot", action="store_true", help="the MPC trot closed on the device: command, gait, data flow, swing, front-end, tick, MPC command (implies --estimator --body)")
     ap.add_argument("--cmd-vx", type=float, default=0.0, metavar="V", help="(--trot) joyCmdVx, m/s")
     ap.add_argument("--cmd-yaw", type=float, default=0.0, metavar="W", help="(--trot) joyCmdYawRate, rad/s")
+    ap.add_argument("--cadence", action="store_true", help="(--trot) the tick on the reference's cadence: per robot the MPC or the WBC, from the front-end's mask (qrgpu_tick_cadence_batch)")
     ap.add_argument("--profile", action="store_true", help="the run a profiler traces: fewer ticks, nothing else changed")
     a = ap.parse_args()
     if (a.cmd_vx != 0.0 or a.cmd_yaw != 0.0) and not a.trot:
         ap.error("--cmd-vx / --cmd-yaw need --trot")
+    if a.cadence and not a.trot:
+        ap.error("--cadence needs --trot")
     a.estimator = a.estimator or a.trot
     a.body = a.body or a.episodes or a.trot
     if a.sensor_noise != 0.0 and not a.estimator:
@@ -178,6 +186,9 @@ def main():
                  swing_flags=ctx.alloc((n,), np.int32), qdes=ctx.alloc((24, n)).zero(), tau=ctx.alloc((12, n)), cmd_mem=ctx.alloc((1, n), np.int32),
                  updated=ctx.alloc((n,), np.int32), tick_log=ctx.alloc((ticks + 20, n), np.int32).zero(), kd_log=ctx.alloc((ticks + 20, 12, n)),
                  fb_then=ctx.alloc_pinned((37, n)))
+        if a.cadence:   # the kept base-frame force (the force array is the other half of the memory), and every tick's mask
+            d.update(hold=ctx.alloc((12, n)).zero(), due_log=ctx.alloc((ticks + 20, n), np.int32).zero())
+            d["force"].zero()
 
     def plant(par, **out):
         if a.body:
@@ -241,7 +252,12 @@ def main():
                 ctx.footholds_batch(n, fcfg, d["fh_in"], d["swing_in"], gait_state=d["gait_state"], gait_out=d["gait_out"])
                 ctx.swing_targets_batch(n, ecfg, d["swing_in"], wbc_cmd=d["wcmd"], foot_target_world=d["fe_in"].row(26), qdes=d["qdes"])
                 ctx.mpc_frontend_batch(n, d["fe_in"], d["fe_state"], d["traj"], d["gait"], d["wcmd"], d["updated"])
-                ctx.tick_batch(n, d["mpc_est"], d["traj"], d["gait"], d["fb_est"], d["wcmd"], d["prev"], d["force"], d["tau"], d["tick_log"].row(k))
+                if a.cadence:
+                    ctx.tick_cadence_batch(n, d["updated"], d["mpc_est"], d["traj"], d["gait"], d["fb_est"], d["wcmd"], d["prev"], d["force"], d["hold"], d["tau"],
+                                           d["tick_log"].row(k))
+                    ctx.copy_rows(d["due_log"].row(k), d["updated"], n)        # the report's log: who was solved this tick
+                else:
+                    ctx.tick_batch(n, d["mpc_est"], d["traj"], d["gait"], d["fb_est"], d["wcmd"], d["prev"], d["force"], d["tau"], d["tick_log"].row(k))
                 ctx.mpc_command(n, mdesc, d["tau"], d["qdes"], d["swing_in"], d["gait_out"], d["gait_state"], d["cmd_mem"], d["cmd"], reset=int(first))
                 ctx.copy_rows(d["kd_log"].row(k), d["cmd"].row(36), 12 * n)    # the report's log: Kd of this tick's command (a swing command carries the motor's)
                 if k == total[0] - 101:
@@ -306,6 +322,8 @@ def main():
         res.update(trot=True, cmd_vx=a.cmd_vx, cmd_yaw=a.cmd_yaw, tick_flagged_share=float((pkg.status_flags(tick_log) != 0).mean()),
                    swing_legs_commanded=int(swing.sum()), swing_legs_commanded_per_robot_tick=float(swing.sum(1).mean()),
                    swing_flags_seen=int(np.bitwise_or.reduce(d["swing_flags"].download())))
+        if a.cadence:
+            res.update(cadence=True, mpc_due_share=float((d["due_log"].download()[20:20 + ticks] != 0).mean()))
         if ticks >= 81:   # mean base speed along the command over the last 100 ticks, from the plant's truth; robots respawned in that window left out
             then = d["fb_then"].array
             calm = np.isfinite(fb).all(0) & np.isfinite(then).all(0)
