@@ -1132,6 +1132,133 @@ void qrgpu_mpc_command_desc_default(qrgpu_mpc_command_desc *d);
 int  qrgpu_mpc_command_batch(qrgpu_ctx *ctx, int n, const qrgpu_mpc_command_desc *desc, int reset, const float *d_tau, const float *d_qdes,
                              const float *d_swing_in, const float *d_gait_out, const float *d_gait_state, int *d_cmd_mem, float *d_motor_cmd);
 
+/* ---- the control state machine: joystick, stand-up, transitions ---------------------------------------------------------------------------------
+ * What decides when a robot is in qrFSMStateLocomotion::Run, per robot and per tick, with no host decision: qrDesiredStateCommand::JoyCallback and the
+ * change-request block of Update (QS/controllers/qr_desired_state_command.cpp:66-161, :166-211), qrControlFSM::RunFSM over the states Passive, StandUp
+ * and Locomotion (QS/fsm/ *.cpp, with SwitchMode, StandLoop and SafetyPostCheck) and Action::StandUp / SitDown (QS/action/qr_action.cpp:31-96).  Three
+ * entry points, one launch each on the context's stream, one lane per robot; copies, compares, integer counters and float32 + - x / with contraction
+ * off.  They change no other call.  The tick of a robot's whole life cycle (tools/closed_loop.py --fsm):
+ *     episode step, qrgpu_fsm_update_batch, [plant,] observe ... qrgpu_command_update_batch, qrgpu_fsm_zero_command_batch, the locomotion chain ...
+ *     qrgpu_mpc_command_batch (or qrgpu_stance_command_batch), qrgpu_fsm_command_batch.
+ *
+ * qrgpu_fsm_update_batch: everything qrRobotRunner::Update does before the locomotion chain.  Per robot, in this order:
+ *   1. reset -- the scalar, or (d_done[r] & bits) != 0 -- writes the d_fsm_state column as constructed; what it held is not read: joyCtrlState =
+ *      desc->initial_ctrl_state, prevJoyCtrlState JOY_STAND, movementMode 0, bodyUp 0, joyCtrlOnRequest 1, no request; the FSM in STAND_UP after its
+ *      OnEnter (standUp 1, isUp 1, fsmMode K_STAND_UP), operating mode NORMAL; the locomotion state's checks on, the others' off; no command sent yet.
+ *   2. JoyCallback, if a message arrived: d_joy_msg [QRGPU_JOY_MSG_ROWS][n] (may be NULL): row 0 != 0 "a message arrived this tick", rows 1-5 buttons
+ *      [0] A, [1] B, [2] X, [3] Y, [5] RB (pressed: == 1), rows 6-8 axes [0], [3], [4], row 9 != 0 sets the gaitSwitch member (:166-169; read whatever row 0
+ *      says).  Or from the device script d_script [QRGPU_FSM_SCRIPT_ROWS][n_script] (may be NULL): row 0 a tick count, row 1 a button mask
+ *      (QRGPU_JOY_BTN_*), rows 2-4 axes [0], [3], [4]: a robot whose d_ticks[r] (row 0 of d_ep_state) equals an entry's tick receives that entry
+ *      (the first such entry).  A row-0 message of d_joy_msg wins over the script.  The axes are scaled by desc->max_velx, max_vely, max_yawrate.
+ *   3. unless an action is in progress: the gaitSwitch test and the change-request block of Update, and the zeros its JOY_STAND and else branches
+ *      assign to the joyCmd members (:213-243);
+ *   4. the head of RunFSM: a request becomes fsmMode (:72-94);
+ *   5. CheckTransition of the current state and the operating-mode logic (:96-119), up to the decision of what runs this tick.
+ *   d_joy [QRGPU_JOY_ROWS][n]  as qrgpu_command_update_batch reads it: rows 0-5 the joyCmd members (in HARD_CODE desc->hard_code_v, hard_code_w), 6
+ *                      desc->body_height, 7 joyCtrlState.
+ *   d_plan [n]         QRGPU_FSM_PLAN_* bits: exactly one of RUN (qrFSMStateLocomotion::Run), PHASE1 (SwitchMode / StandLoop: locomotion Update +
+ *                      GetAction with the command zeroed), PHASE2 (SwitchMode's stand blend), ACTION (one tick of StandUp / SitDown), HOLD
+ *                      (qrFSMStateStandUp::Run's command), PASSIVE (zeros), REPEAT (the command of the previous tick once more: see below); and the
+ *                      flags DONE (transitionData.done: OnExit and OnEnter follow), ACTION_FIRST, ACTION_END.
+ *   d_stage_mask [n] (may be NULL) = (d_done[r] & bits) | QRGPU_FSM_ENTERED where the robot's FSM ran qrFSMStateLocomotion::OnEnter with a state other
+ *                      than HARD_CODE at the end of the previous tick (:88-124): bound with qrgpu_set_stage_reset (bits = the caller's |
+ *                      QRGPU_FSM_ENTERED) it gives this tick's stages quadruped->Reset(), locomotionController->Reset() and stateEstimators->Reset().
+ * qrgpu_fsm_zero_command_batch: stateDes.segment(6, 6) = 0 and UpdateControllerParams(..., 0, 0) of SwitchMode and StandLoop (:289-290, :329-330),
+ *   after qrgpu_command_update_batch: for the robots whose plan has PHASE1, +0 into the copies of stateDes 6-11: d_state_des rows 6-11, d_fe_in 3-5,
+ *   d_fh_in 16-19, d_swing_vel_in 23-26, d_stance_cmd 1-6.  Each array may be NULL; no other row, no other robot is touched.  Those are all the rows
+ *   the existing kernels read desiredSpeed and desiredTwistingSpeed from; desired_speed / desired_twisting_speed of qrgpu_stance_desc are one value
+ *   for the batch (user_parameters.yaml's, zero by default) and cannot be zeroed per robot.
+ * qrgpu_fsm_command_batch: the rest of RunFSM, after the locomotion chain's motor command.  Reads d_plan, d_est_in (contacts 13-16, motor angles
+ *   17-28) and d_motor_cmd_loco (what qrgpu_mpc_command_batch or qrgpu_stance_command_batch wrote; may be d_motor_cmd itself: a lane loads its column
+ *   before its first store).  Writes every robot's d_motor_cmd [QRGPU_MOTOR_CMD_ROWS][n] column:
+ *     RUN, PHASE1   the locomotion column passed through
+ *     PHASE2        {stand ratio + (1 - ratio) q, Kp, 0, Kd, 0}, ratio = max(0.45f, (iter - T) / float(T))
+ *     ACTION        {blend target + (1 - blend) q_before, Kp, 0, Kd, 0} (POSITION_MODE, qr_robot_a1_sim.cpp:676-684); blend = t / time; StandUp sends the
+ *                   target itself once blend >= 1 (:48, :69); q_before is read from d_est_in at the action's first tick and kept in the state
+ *     HOLD          {motorAngles, Kp, 0, Kd, 0}: the stand-up angles while isUp, else the sit-down angles
+ *     PASSIVE       zeros
+ *     REPEAT        the column this call wrote at the previous tick (kept in the state)
+ *   then advances iter (with the N == 4 -> iter = T shortcuts), ends SwitchMode / StandLoop, runs OnExit and OnEnter after DONE and restores NORMAL, and
+ *   clips the tua rows to +-desc->tau_clip while the current state's checkForceFeedForward is on (qr_safety_checker.cpp:48-66; idempotent on top of
+ *   QRGPU_EPILOGUE_CLIP).  The reference's quirk is kept: Transition() to PASSIVE turns the locomotion state's checks off for good (:250).
+ *   d_fsm_out [QRGPU_FSM_OUT_ROWS][n] (may be NULL), after the tick: 0 state name (FSM_StateName: PASSIVE 1, STAND_UP 4, LOCOMOTION 7), 1 operating mode
+ *   (NORMAL 0, TRANSITIONING 1), 2 fsmMode, 3 joyCtrlState, 4 the locomotion state's iter, 5-7 checkSafeOrientation, checkPDesFoot,
+ *   checkForceFeedForward of the current state, 8 the gait OnEnter chose last (QRGPU_FSM_GAIT_*; 0: none yet), 9 the mode (LocomotionMode; -1: none yet),
+ *   10 action in progress (1 StandUp, -1 SitDown, 0).
+ * d_fsm_state [QRGPU_FSM_STATE_ROWS][n] float32, the machine's memory, every integer held exactly (csrc/qr_fsm.h lists the rows).  The first call on
+ *   new arrays is a reset.
+ *
+ * Unrolling, and what is OURS:
+ *   - A blocking action becomes one ACTION tick per call.  Its loop variable t is kept in the state and advanced by t += time_step in float32 from a
+ *     start time of 0 (the reference's wall-clock start is not reproducible).  The action ends at the first update call that finds t >= total
+ *     (stand_up_total; sit_down_time): that call plans HOLD | ACTION_END, and the command call does what Run() does after the action.
+ *   - While an action is in progress (that last call included) the runner is blocked: JoyCallback still runs; steps 3, 4 and 5 do not.
+ *   - At most one joystick message per robot per tick.
+ *   - fsmMode values that lead to statesList.invalid (BALANCE_STAND, VISION, RECOVERY_STAND, JOINT_PD) cannot arise from the joystick and are not
+ *     supported: a state that meets one stays as it is.
+ *   - PHASE1 passes the chain's command through as it comes: the batch tick cannot drop hip compensation and WBC for single robots.
+ *   - REPEAT: where the reference sends a command kept from the tick before -- the tick that ends SwitchMode / StandLoop (transitionData.legCommand is
+ *     not written, :276-283, :318-325), StandUp -> LOCOMOTION and LOCOMOTION -> STAND_UP (legCommand = data.legCmd) -- it is the column of the previous
+ *     tick.  An empty legCommand (the transitions to and from PASSIVE, transitionData.Zero()) is written as zeros.
+ *   - Gait and mode per robot are REPORTED in d_fsm_out; a gait call still takes one desc for the batch.
+ * QRGPU_ERR_BAD_ARG (nothing launched, outputs untouched; qrgpu_last_error names the argument): a NULL required array or desc; n < 1, n > max_batch;
+ *   a reset other than 0 or 1; stand_up_time, stand_up_total, sit_down_time, time_step, a transition duration or tau_clip not finite or not > 0;
+ *   transition_ticks < 1; initial_ctrl_state outside 0..7; n_script < 0 or > QRGPU_FSM_SCRIPT_MAX, n_script > 0 without d_script, a script without
+ *   d_ticks; d_done with bits == 0. */
+#define QRGPU_JOY_MSG_ROWS      10
+#define QRGPU_FSM_SCRIPT_ROWS   5
+#define QRGPU_FSM_SCRIPT_MAX    64
+#define QRGPU_FSM_STATE_ROWS    106
+#define QRGPU_FSM_OUT_ROWS      11
+#define QRGPU_FSM_ENTERED       0x00010000  /* in d_stage_mask: outside QRGPU_EP_REASONS and QRGPU_EP_BAD_FIELD */
+#define QRGPU_JOY_BTN_A         0x1         /* buttons[0] */
+#define QRGPU_JOY_BTN_B         0x2         /* buttons[1] */
+#define QRGPU_JOY_BTN_X         0x4         /* buttons[2] */
+#define QRGPU_JOY_BTN_Y         0x8         /* buttons[3] */
+#define QRGPU_JOY_BTN_RB        0x10        /* buttons[5] */
+#define QRGPU_JOY_GAIT_SWITCH   0x20        /* the gaitSwitch member, not a button */
+#define QRGPU_FSM_PLAN_RUN      0x1
+#define QRGPU_FSM_PLAN_PHASE1   0x2
+#define QRGPU_FSM_PLAN_PHASE2   0x4
+#define QRGPU_FSM_PLAN_ACTION   0x8
+#define QRGPU_FSM_PLAN_HOLD     0x10
+#define QRGPU_FSM_PLAN_PASSIVE  0x20
+#define QRGPU_FSM_PLAN_REPEAT   0x40
+#define QRGPU_FSM_PLAN_DONE         0x100
+#define QRGPU_FSM_PLAN_ACTION_FIRST 0x200
+#define QRGPU_FSM_PLAN_ACTION_END   0x400
+#define QRGPU_FSM_GAIT_TROT          1
+#define QRGPU_FSM_GAIT_ADVANCED_TROT 2
+#define QRGPU_FSM_GAIT_WALK          3
+#define QRGPU_FSM_GAIT_STAND         4
+struct qrgpu_fsm_desc {
+    float stand_up_angles[12];        /* robot->standUpMotorAngles; a1_sim: (0, acos(0.28 / 2 / 0.2), -2 x that) per leg, in float (qr_robot_a1_sim.cpp:114-119) */
+    float sit_down_angles[12];        /* robot->sitDownMotorAngles; a1_sim: (-0.167136, 0.934969, -2.54468) per leg */
+    float kp[12], kd[12];             /* robot->motorKps / motorKds; a1_sim: 100 / (1, 2, 2) per leg */
+    float stand_up_time;              /* qr_fsm_state_standup.cpp:62: 2 */
+    float stand_up_total;             /* :62: 3 */
+    float sit_down_time;              /* :66: 1.5 */
+    float time_step;                  /* 1 / controlFrequency: 0.001 */
+    int   transition_ticks;           /* T: every literal 1000 of SwitchMode, StandLoop and Transition */
+    float gait_transition_duration;   /* qr_fsm_state_locomotion.cpp:176: 2 */
+    float stand_transition_duration;  /* :181: 1 */
+    float tau_clip;                   /* qr_safety_checker.cpp:57-60: 23 */
+    float body_height;                /* robot->bodyHeight: 0.28 */
+    int   initial_ctrl_state;         /* RC_MODE the command is constructed with (qr_desired_state_command.cpp:46): BODY_UP 5 */
+    float hard_code_v[3], hard_code_w[3];                /* vDesInBodyFrame, wDesInBodyFrame: zeros */
+    float max_velx, max_vely, max_yawrate;               /* the axes' scales, qr_desired_state_command.hpp:312, :322, :332: 0.2, 0.1, 0.2 */
+};
+typedef struct qrgpu_fsm_desc qrgpu_fsm_desc;
+void qrgpu_fsm_desc_default(qrgpu_fsm_desc *d);
+int  qrgpu_fsm_update_batch(qrgpu_ctx *ctx, int n, const qrgpu_fsm_desc *desc, int reset, const float *d_joy_msg /* may be NULL */,
+                            const float *d_script /* [QRGPU_FSM_SCRIPT_ROWS][n_script], may be NULL */, int n_script, const int *d_ticks /* [n] */,
+                            const int *d_done /* [n], may be NULL */, unsigned bits, float *d_fsm_state, float *d_joy, int *d_plan,
+                            int *d_stage_mask /* may be NULL */);
+int  qrgpu_fsm_zero_command_batch(qrgpu_ctx *ctx, int n, const int *d_plan, float *d_state_des, float *d_fe_in, float *d_fh_in,
+                                  float *d_swing_vel_in, float *d_stance_cmd);
+int  qrgpu_fsm_command_batch(qrgpu_ctx *ctx, int n, const qrgpu_fsm_desc *desc, const int *d_plan, const float *d_est_in,
+                             const float *d_motor_cmd_loco, float *d_fsm_state, float *d_motor_cmd, float *d_fsm_out /* may be NULL */);
+
 /* ---- multi-GPU: all-gather of the per-robot torques over RCCL / xGMI ----------------------------------------
  * One process per GPU, one context per process; rank r of N owns a contiguous shard of the robot population and there is no exchange
  * inside a tick.  The only collective of the path collects every rank's tau[12][n_local] on every rank:

@@ -158,4 +158,11 @@ struct CadenceLegs {
 __global__ void qr_cadence_kernel(int n, CadenceLegs L, const int *g_type, const int *g_due, const float *g_mpc_state, const float *g_fb_state, const float *g_force,
                                   float *g_hold, float *g_tau, int *g_status);
 
+// qr_fsm_kernel.hip: one lane per robot; the control state machine: what runs this tick, the zeroed command of a transition, the command sent
+__global__ void qr_fsm_update_kernel(int n, qrgpu_fsm_desc D, int reset, const float *g_msg, const float *g_script, int n_script, const int *g_ticks,
+                                     const int *g_done, unsigned bits, float *g_st, float *g_joy, int *g_plan, int *g_stage_mask);
+__global__ void qr_fsm_zero_kernel(int n, const int *g_plan, float *g_des, float *g_fe, float *g_fh, float *g_sv, float *g_sc);
+__global__ void qr_fsm_command_kernel(int n, qrgpu_fsm_desc D, const int *g_plan, const float *g_est_in, const float *g_loco, float *g_st, float *g_cmd,
+                                      float *g_out);
+
 }  // namespace qrgpu

@@ -313,6 +313,32 @@ def mpc_command_desc(**fields):
     return _set_fields(d, fields)
 
 
+JOY_MSG_ROWS, FSM_SCRIPT_ROWS, FSM_SCRIPT_MAX, FSM_STATE_ROWS, FSM_OUT_ROWS = 10, 5, 64, 106, 11
+FSM_ENTERED = 0x00010000                # in fsm_update's stage_mask: outside EP_REASONS and EP_BAD_FIELD
+JOY_BTN_A, JOY_BTN_B, JOY_BTN_X, JOY_BTN_Y, JOY_BTN_RB, JOY_GAIT_SWITCH = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20
+FSM_PLAN_RUN, FSM_PLAN_PHASE1, FSM_PLAN_PHASE2, FSM_PLAN_ACTION, FSM_PLAN_HOLD, FSM_PLAN_PASSIVE, FSM_PLAN_REPEAT = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20, 0x40
+FSM_PLAN_DONE, FSM_PLAN_ACTION_FIRST, FSM_PLAN_ACTION_END = 0x100, 0x200, 0x400
+FSM_PASSIVE, FSM_STAND_UP, FSM_LOCOMOTION = 1, 4, 7                       # FSM_StateName, row 0 of fsm_out
+FSM_GAIT_TROT, FSM_GAIT_ADVANCED_TROT, FSM_GAIT_WALK, FSM_GAIT_STAND = 1, 2, 3, 4
+
+
+class fsm_desc_struct(C.Structure):
+    _fields_ = [("stand_up_angles", C.c_float * 12), ("sit_down_angles", C.c_float * 12), ("kp", C.c_float * 12), ("kd", C.c_float * 12),
+                ("stand_up_time", C.c_float), ("stand_up_total", C.c_float), ("sit_down_time", C.c_float), ("time_step", C.c_float),
+                ("transition_ticks", C.c_int), ("gait_transition_duration", C.c_float), ("stand_transition_duration", C.c_float),
+                ("tau_clip", C.c_float), ("body_height", C.c_float), ("initial_ctrl_state", C.c_int), ("hard_code_v", C.c_float * 3),
+                ("hard_code_w", C.c_float * 3), ("max_velx", C.c_float), ("max_vely", C.c_float), ("max_yawrate", C.c_float)]
+
+
+def fsm_desc(**fields):
+    """qrgpu_fsm_desc: the control state machine's constants -- a1_sim's stand-up and sit-down angles and motor gains, stand-up 2 s of 3 s, sit-down
+    1.5 s, time step 0.001, transition_ticks 1000 with durations 2 (gait) and 1 (stand), torque clip 23, body height 0.28, constructed in BODY_UP --
+    with any field overridden (scalars or sequences by name)."""
+    d = fsm_desc_struct()
+    load_library().qrgpu_fsm_desc_default(C.byref(d))
+    return _set_fields(d, fields)
+
+
 EPILOGUE_HIP_COMP, EPILOGUE_CLIP = 1, 2
 COMM_ID_BYTES = 128
 
@@ -349,7 +375,8 @@ EXPORTS = ["qrgpu_model_desc_default", "qrgpu_create", "qrgpu_destroy", "qrgpu_s
            "qrgpu_episode_desc_default", "qrgpu_episode_step_batch", "qrgpu_set_stage_reset",
            "qrgpu_observe_desc_default", "qrgpu_observe_state_rows", "qrgpu_observe_batch",
            "qrgpu_command_desc_default", "qrgpu_command_update_batch", "qrgpu_trot_inputs_batch", "qrgpu_mpc_command_desc_default",
-           "qrgpu_mpc_command_batch", "qrgpu_tick_cadence_batch"]
+           "qrgpu_mpc_command_batch", "qrgpu_tick_cadence_batch",
+           "qrgpu_fsm_desc_default", "qrgpu_fsm_update_batch", "qrgpu_fsm_zero_command_batch", "qrgpu_fsm_command_batch"]
 
 
 def load_library():
@@ -446,6 +473,10 @@ def load_library():
     lib.qrgpu_trot_inputs_batch.argtypes = [vp, ip] + [vp] * 9
     lib.qrgpu_mpc_command_desc_default.argtypes = [C.POINTER(mpc_command_desc_struct)]; lib.qrgpu_mpc_command_desc_default.restype = None
     lib.qrgpu_mpc_command_batch.argtypes = [vp, ip, C.POINTER(mpc_command_desc_struct), ip] + [vp] * 7
+    lib.qrgpu_fsm_desc_default.argtypes = [C.POINTER(fsm_desc_struct)]; lib.qrgpu_fsm_desc_default.restype = None
+    lib.qrgpu_fsm_update_batch.argtypes = [vp, ip, C.POINTER(fsm_desc_struct), ip, vp, vp, ip, vp, vp, C.c_uint] + [vp] * 4
+    lib.qrgpu_fsm_zero_command_batch.argtypes = [vp, ip] + [vp] * 6
+    lib.qrgpu_fsm_command_batch.argtypes = [vp, ip, C.POINTER(fsm_desc_struct)] + [vp] * 6
     lib.qrgpu_vmc_force1.argtypes = [vp, ip, fp, fp, fp, fp, C.POINTER(ip)]
     lib.qrgpu_vmc_force_world1.argtypes = [vp, ip, fp, fp, fp, fp, fp, C.POINTER(ip)]
     lib.qrgpu_mpc_frontend_batch.argtypes = [vp, ip, ip, C.c_float, C.c_float] + [vp] * 6
@@ -932,6 +963,32 @@ class Context:
         1 clears it for every robot, a stage-reset binding's mask per robot."""
         self._chk(self._lib.qrgpu_mpc_command_batch(self._h, n, C.byref(desc), int(reset), _dp(tau), _dp(qdes), _dp(swing_in), _dp(gait_out), _dp(gait_state),
                                                     _dp(cmd_mem), _dp(motor_cmd)))
+
+    def fsm_state_rows(self):
+        """Rows of fsm_state, the control state machine's memory (float32; the first fsm_update on new arrays is a reset)."""
+        return FSM_STATE_ROWS
+
+    def fsm_update(self, n, desc, fsm_state, joy, plan, stage_mask=None, joy_msg=None, script=None, n_script=0, ticks=None, done=None, bits=EP_REASONS,
+                   reset=0):
+        """The head of a robot's tick (desc: fsm_desc()): JoyCallback from joy_msg [JOY_MSG_ROWS][n] (row 0: a message arrived; buttons A, B, X, Y, RB;
+        axes [0], [3], [4]; gaitSwitch) or from the device script [FSM_SCRIPT_ROWS][n_script] (tick, JOY_BTN_* mask, the three axes) keyed on ticks [n]
+        (row 0 of ep_state), the change-request block of Update, RunFSM up to the decision -> joy [JOY_ROWS][n] for command_update, plan [n] int32
+        (FSM_PLAN_* bits) and stage_mask [n] int32 = (done & bits) | FSM_ENTERED for set_stage_reset.  reset, or a robot with done & bits, starts
+        as constructed."""
+        self._chk(self._lib.qrgpu_fsm_update_batch(self._h, n, C.byref(desc), int(reset), _dp(joy_msg), _dp(script), int(n_script), _dp(ticks), _dp(done),
+                                                   int(bits) if done is not None else 0, _dp(fsm_state), _dp(joy), _dp(plan), _dp(stage_mask)))
+
+    def fsm_zero_command(self, n, plan, state_des=None, fe_in=None, fh_in=None, swing_vel_in=None, stance_cmd=None):
+        """stateDes.segment(6, 6) = 0 of SwitchMode / StandLoop for the robots whose plan has FSM_PLAN_PHASE1, after command_update: state_des rows 6-11,
+        fe_in 3-5, fh_in 16-19, swing_vel_in 23-26, stance_cmd 1-6 (each optional)."""
+        self._chk(self._lib.qrgpu_fsm_zero_command_batch(self._h, n, _dp(plan), _dp(state_des), _dp(fe_in), _dp(fh_in), _dp(swing_vel_in), _dp(stance_cmd)))
+
+    def fsm_command(self, n, desc, plan, est_in, motor_cmd_loco, fsm_state, motor_cmd, fsm_out=None):
+        """The rest of RunFSM: every robot's motor_cmd [60][n] column chosen by its plan (the locomotion column motor_cmd_loco passed through, the stand
+        blend, an action tick, the hold, zeros, or the previous tick's), iter, OnExit / OnEnter, the torque clip; fsm_out [FSM_OUT_ROWS][n] reports the
+        state.  motor_cmd_loco may be motor_cmd itself."""
+        self._chk(self._lib.qrgpu_fsm_command_batch(self._h, n, C.byref(desc), _dp(plan), _dp(est_in), _dp(motor_cmd_loco), _dp(fsm_state), _dp(motor_cmd),
+                                                    _dp(fsm_out)))
 
     def mpc_frontend_batch(self, n, fe_in, fe_state, traj, gait, wbc_cmd=None, mpc_updated=None, num_horizon_l=2, dt_ctrl=0.002, dt_mpc=0.06):
         """SetupCommand + Run + UpdateMPC (without the solve) of n robots: qr_mpc_stance_leg_controller.cpp:158-382."""

@@ -10,6 +10,7 @@ inside the loop.
   python tools/closed_loop.py --estimator [--sensor-noise 0.02]                       the tick reads the estimator chain's state, not the plant's truth
   python tools/closed_loop.py --trot [--cmd-vx 0.15] [--cmd-yaw 0.1] [--episodes] [--terrain ...]   the MPC trot, every stage on the device
   python tools/closed_loop.py --trot --cadence [...]                                  the same with the tick on the reference's cadence: MPC or WBC per robot
+  python tools/closed_loop.py --fsm [--ticks 3000] [--cmd-vx 0.15] [--fsm-speed 1]    a robot's whole life cycle: sit, stand up, MPC standing, trot, fall, again
 
 The robots are dropped from z = 0.30 onto joint PD at the stand pose (400 ticks of 1 ms), shoved by up to 0.3 m/s in x and y, and handed to
 MPC + WBC: qrgpu_plant_step_batch (include/qrgpu.h) writes the ground-truth mpc_state and fb_state the tick reads, and the tick -- the plain
@@ -51,6 +52,16 @@ The mask never leaves the device; its mean over the timed ticks is logged there 
 run logs on the device, per tick, the tick's status words and the Kd rows of the motor command (one device-to-device copy of 12 rows), and the true state
 100 ticks before the end; they are read once, after the loop.  Whether the batch trots, drifts or falls is reported, not judged.
 
+--fsm (implies --trot --episodes) puts the control state machine in charge of every robot: qrgpu_fsm_update_batch after the episode step (its joy rows
+feed qrgpu_command_update_batch, its stage mask -- the episode's reasons or QRGPU_FSM_ENTERED -- is the stage-reset binding's), qrgpu_fsm_zero_command_batch
+after the command update, qrgpu_fsm_command_batch after the MPC command, whose column it passes on, replaces or repeats.  The robots spawn at the
+sit-down angles, 0.14 above the ground; an episode ends by tilt, by a clearance under 0.05 m or by a non-finite state (a sitting robot rests on its
+trunk: trunk contact is no reason here).  A device script keyed on each robot's episode tick presses X once the stand-up is over (to JOY_STAND) and X
+again with --cmd-vx / --cmd-yaw on the axes (to JOY_ADVANCED_TROT): a respawned robot goes through the same sequence again.  time_step is the
+tick's 0.002 x --fsm-speed and transition_ticks 500 / --fsm-speed: at speed 1 the stand-up takes 1500 ticks and the script presses at ticks 1600 and 2400.
+
+  fsm, fsm_state_share (share of robots x timed ticks in PASSIVE, STAND_UP, LOCOMOTION), stood_up (robots that completed a stand-up), entered_locomotion,
+                fell_before_locomotion (robots whose first episode ended before they had entered locomotion): warm-up included, reported, not judged
   ticks_per_s   closed-loop control ticks per second: every robot advances one tick per (plant step + controller tick)
   trot, cmd_vx, cmd_yaw, speed_along_command_mean (world x over the last 100 ticks, m/s, robots not respawned in them: speed_robots), yaw_rate_mean,
                 tick_flagged_share (share of ticks x robots whose tick status word carries a flag), swing_legs_commanded (legs x ticks x robots that
@@ -111,8 +122,12 @@ def main():
     ap.add_argument("--cmd-vx", type=float, default=0.0, metavar="V", help="(--trot) joyCmdVx, m/s")
     ap.add_argument("--cmd-yaw", type=float, default=0.0, metavar="W", help="(--trot) joyCmdYawRate, rad/s")
     ap.add_argument("--cadence", action="store_true", help="(--trot) the tick on the reference's cadence: per robot the MPC or the WBC, from the front-end's mask (qrgpu_tick_cadence_batch)")
+    ap.add_argument("--fsm", action="store_true", help="the control state machine decides what every robot runs: sit, stand up, stand, trot (implies --trot --episodes)")
+    ap.add_argument("--fsm-speed", type=float, default=1.0, metavar="S", help="(--fsm) run the stand-up and the transitions S times faster")
     ap.add_argument("--profile", action="store_true", help="the run a profiler traces: fewer ticks, nothing else changed")
     a = ap.parse_args()
+    a.trot = a.trot or a.fsm
+    a.episodes = a.episodes or a.fsm
     if (a.cmd_vx != 0.0 or a.cmd_yaw != 0.0) and not a.trot:
         ap.error("--cmd-vx / --cmd-yaw need --trot")
     if a.cadence and not a.trot:
@@ -130,6 +145,9 @@ def main():
     ctx.wbc_setup_packed(0, pkg.model_desc("a1"))
     fb0 = np.zeros((37, n), np.float32); fb0[0] = 1.0; fb0[6] = 0.30; fb0[13:25] = STAND_POSE[:, None]
     cmd0 = np.zeros((60, n), np.float32); cmd0[0:12] = STAND_POSE[:, None]; cmd0[12:24] = 100.0; cmd0[36:48] = 2.0
+    if a.fsm:           # the robots start sitting
+        fdesc = pkg.fsm_desc(time_step=0.002 * a.fsm_speed, transition_ticks=max(1, int(round(500 / a.fsm_speed))))
+        fb0[6] = 0.14; fb0[13:25] = np.array(fdesc.sit_down_angles[:], np.float32)[:, None]; cmd0[0:12] = fb0[13:25]
     traj = np.zeros((h, 12, n), np.float32); traj[:, 5] = HEIGHT
     wcmd = np.zeros((67, n), np.float32); wcmd[2] = HEIGHT; wcmd[63:67] = 1.0
     d = dict(fb=ctx.alloc((37, n)).upload(fb0), cmd=ctx.alloc((60, n)).upload(cmd0), mpc=ctx.alloc((28, n)), out=ctx.alloc((pkg.qrgpu.PLANT_OUT_ROWS, n)),
@@ -158,7 +176,8 @@ def main():
         cx, cy = grid.x0 + 0.5 * (grid.nx - 1) * grid.cell, grid.y0 + 0.5 * (grid.ny - 1) * grid.cell
         gx, gy = np.meshgrid(cx + a.spawn_spread * np.arange(-1, 2), cy + a.spawn_spread * np.arange(-1, 2))
         table = np.zeros((4, 9), np.float32); table[0] = gx.ravel(); table[1] = gy.ravel()
-        edesc = pkg.episode_desc(max_ticks=a.max_ticks, seed=a.seed, align_to_slope=int(kind == "plane"), field_margin=0.2, v_jitter=0.3)
+        sitting = dict(q_spawn=fdesc.sit_down_angles[:], spawn_height=0.14, status_mask=q.PL_NONFINITE | q.PL_QUAT_ZERO, min_clearance=0.05) if a.fsm else {}
+        edesc = pkg.episode_desc(max_ticks=a.max_ticks, seed=a.seed, align_to_slope=int(kind == "plane"), field_margin=0.2, v_jitter=0.3, **sitting)
         d.update(table=ctx.alloc((4, 9)).upload(table), ep_state=ctx.alloc((q.EPISODE_STATE_ROWS, n), np.int32).zero(), ep_stats=ctx.alloc((q.EPISODE_STATS_ROWS, n)),
                  done_log=ctx.alloc((ticks + 20, n), np.int32).zero(), done_list=ctx.alloc((n,), np.int32), done_count=ctx.alloc((1,), np.int32))
 
@@ -189,6 +208,15 @@ def main():
         if a.cadence:   # the kept base-frame force (the force array is the other half of the memory), and every tick's mask
             d.update(hold=ctx.alloc((12, n)).zero(), due_log=ctx.alloc((ticks + 20, n), np.int32).zero())
             d["force"].zero()
+
+    if a.fsm:           # the machine's memory, what it hands the stages, its per-tick report, the script (X after the stand-up, X with the command)
+        q = pkg.qrgpu
+        up = int(np.ceil(fdesc.stand_up_total / fdesc.time_step))
+        first_press = up + max(4, int(100 / a.fsm_speed))
+        press = np.array([[first_press, q.JOY_BTN_X, 0.0, 0.0, 0.0],
+                          [first_press + max(20, int(800 / a.fsm_speed)), q.JOY_BTN_X, a.cmd_yaw / fdesc.max_yawrate, 0.0, a.cmd_vx / fdesc.max_velx]], np.float32).T.copy()
+        d.update(fsm_state=ctx.alloc((q.FSM_STATE_ROWS, n)), plan=ctx.alloc((n,), np.int32), stage_mask=ctx.alloc((n,), np.int32), script=ctx.alloc(press.shape).upload(press),
+                 fsm_log=ctx.alloc((ticks + 20, q.FSM_OUT_ROWS, n)).zero(), plan_log=ctx.alloc((ticks + 20, n), np.int32).zero())
 
     def plant(par, **out):
         if a.body:
@@ -228,7 +256,11 @@ def main():
                 ctx.episode_step_batch(n, edesc, d["fb"], d["table"], 9, d["ep_state"], d["ep_stats"], d["done_log"].row(done[0]), params=params, terrain=tdesc,
                                        height=d["height"], plant_status=d["status_log"].row(done[0] - 1) if done[0] else None, tick_status=None,
                                        prev_ori=d["prev"], motor_cmd=d["cmd"], done_list=d["done_list"], done_count=d["done_count"])
-            if a.estimator and a.episodes:    # the observe, ground and estimator stages restart a robot this episode step respawned
+            if a.fsm:                         # JoyCallback, the change request, RunFSM up to the decision: the joy rows, the plan, the stages' reset mask
+                ctx.fsm_update(n, fdesc, d["fsm_state"], d["joy"], d["plan"], stage_mask=d["stage_mask"], script=d["script"], n_script=2, ticks=d["ep_state"],
+                               done=d["done_log"].row(done[0]), bits=pkg.qrgpu.EP_REASONS, reset=int(done[0] == 0))
+                ctx.set_stage_reset(mask=d["stage_mask"], bits=pkg.qrgpu.EP_REASONS | pkg.qrgpu.FSM_ENTERED, ticks=d["ep_state"])
+            elif a.estimator and a.episodes:  # the observe, ground and estimator stages restart a robot this episode step respawned
                 ctx.set_stage_reset(mask=d["done_log"].row(done[0]), ticks=d["ep_state"])
             plant(params, plant_out=d["out"], mpc_state=d["mpc"], status=d["status_log"].row(done[0]) if a.body else d["plant_status"],
                   **(dict(est_in=d["est_in"]) if a.estimator else {}))
@@ -244,6 +276,8 @@ def main():
                 k = done[0] - 1
                 t = float(np.float32(k) * np.float32(0.002))                   # (under --episodes the gait runs on the binding's per-robot clock)
                 ctx.command_update(n, cdesc, d["joy"], d["cmd_state"], state_des=d["state_des"], fe_in=d["fe_in"], fh_in=d["fh_in"], reset=int(first))
+                if a.fsm:                     # SwitchMode / StandLoop: the robots in phase 1 run the chain on a zeroed command
+                    ctx.fsm_zero_command(n, d["plan"], state_des=d["state_des"], fe_in=d["fe_in"], fh_in=d["fh_in"])
                 ctx.gait_update_batch(n, gcfg, t, d["est_in"].row(13), d["gait_state"], d["gait_out"], d["fe_in"], reset=first)
                 ctx.trot_inputs(n, d["est_in"], d["est_out"], d["rpy"], d["gait_out"], gait_state=d["gait_state"], fe_in=d["fe_in"], fh_in=d["fh_in"],
                                 swing_in=d["swing_in"], est_in_next=d["est_in"])
@@ -259,6 +293,9 @@ def main():
                 else:
                     ctx.tick_batch(n, d["mpc_est"], d["traj"], d["gait"], d["fb_est"], d["wcmd"], d["prev"], d["force"], d["tau"], d["tick_log"].row(k))
                 ctx.mpc_command(n, mdesc, d["tau"], d["qdes"], d["swing_in"], d["gait_out"], d["gait_state"], d["cmd_mem"], d["cmd"], reset=int(first))
+                if a.fsm:                     # the rest of RunFSM: the chain's column passed on, replaced by a stand-up, blend or hold, or repeated
+                    ctx.fsm_command(n, fdesc, d["plan"], d["est_in"], d["cmd"], d["fsm_state"], d["cmd"], fsm_out=d["fsm_log"].row(k))
+                    ctx.copy_rows(d["plan_log"].row(k), d["plan"], n, np.int32)
                 ctx.copy_rows(d["kd_log"].row(k), d["cmd"].row(36), 12 * n)    # the report's log: Kd of this tick's command (a swing command carries the motor's)
                 if k == total[0] - 101:
                     d["fb"].copy_to_pinned(d["fb_then"])                       # the truth 100 ticks before the end, for the mean speed
@@ -335,6 +372,19 @@ def main():
                        yaw_rate_mean=float(((np.arctan2(2 * (fb[0] * fb[3] + fb[1] * fb[2]), 1 - 2 * (fb[2] ** 2 + fb[3] ** 2)) -
                                              np.arctan2(2 * (then[0] * then[3] + then[1] * then[2]), 1 - 2 * (then[2] ** 2 + then[3] ** 2)))[calm] / 0.2).mean())
                        if calm.any() else None)
+    if a.fsm:         # where the machine took the robots: reported, not judged
+        q = pkg.qrgpu
+        state = d["fsm_log"].download()[:, 0]                             # [tick][robot]
+        plans, ends = d["plan_log"].download(), (d["done_log"].download() & q.EP_REASONS) != 0
+        ends[0] = False                                                   # (the first call's reset_all is no fall)
+        loco = state == q.FSM_LOCOMOTION
+        first_loco = np.where(loco.any(0), loco.argmax(0), state.shape[0])
+        first_end = np.where(ends.any(0), ends.argmax(0), state.shape[0])
+        timed = state[20:20 + ticks]
+        res.update(fsm=True, fsm_speed=a.fsm_speed, script_ticks=[int(x) for x in press[0]],
+                   fsm_state_share={nm: float((timed == v).mean()) for nm, v in (("passive", q.FSM_PASSIVE), ("stand_up", q.FSM_STAND_UP), ("locomotion", q.FSM_LOCOMOTION))},
+                   stood_up=int(((plans & q.FSM_PLAN_ACTION_END) != 0).any(0).sum()), entered_locomotion=int(loco.any(0).sum()),
+                   fell_before_locomotion=int((first_end < first_loco).sum()))
     print(json.dumps(res))
     ctx.close()
 
