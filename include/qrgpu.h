@@ -1200,7 +1200,8 @@ int  qrgpu_mpc_command_batch(qrgpu_ctx *ctx, int n, const qrgpu_mpc_command_desc
  *   - REPEAT: where the reference sends a command kept from the tick before -- the tick that ends SwitchMode / StandLoop (transitionData.legCommand is
  *     not written, :276-283, :318-325), StandUp -> LOCOMOTION and LOCOMOTION -> STAND_UP (legCommand = data.legCmd) -- it is the column of the previous
  *     tick.  An empty legCommand (the transitions to and from PASSIVE, transitionData.Zero()) is written as zeros.
- *   - Gait and mode per robot are REPORTED in d_fsm_out; a gait call still takes one desc for the batch.
+ *   - Gait and mode per robot are REPORTED in d_fsm_out.  qrgpu_gait_select_update_batch (below) acts on the gait; the MODE stays one per batch: the MPC
+ *     chain, the force-balance chain and the walk chain (with qrWalkGaitGenerator for the robots in JOY_WALK) are not chosen per robot.
  * QRGPU_ERR_BAD_ARG (nothing launched, outputs untouched; qrgpu_last_error names the argument): a NULL required array or desc; n < 1, n > max_batch;
  *   a reset other than 0 or 1; stand_up_time, stand_up_total, sit_down_time, time_step, a transition duration or tau_clip not finite or not > 0;
  *   transition_ticks < 1; initial_ctrl_state outside 0..7; n_script < 0 or > QRGPU_FSM_SCRIPT_MAX, n_script > 0 without d_script, a script without
@@ -1258,6 +1259,56 @@ int  qrgpu_fsm_zero_command_batch(qrgpu_ctx *ctx, int n, const int *d_plan, floa
                                   float *d_swing_vel_in, float *d_stance_cmd);
 int  qrgpu_fsm_command_batch(qrgpu_ctx *ctx, int n, const qrgpu_fsm_desc *desc, const int *d_plan, const float *d_est_in,
                              const float *d_motor_cmd_loco, float *d_fsm_state, float *d_motor_cmd, float *d_fsm_out /* may be NULL */);
+
+/* ---- the gait per robot: a table entry latched at reset, a clock that counts from OnEnter -----------------------------------------------------------
+ * qrFSMStateLocomotion::OnEnter sets gaitGenerator->gait and calls locomotionController->Reset(); qrOpenLoopGaitGenerator::Reset
+ * (QS/gait/qr_openloop_gait_generator.cpp:77-123) re-reads that gait's block of openloop_gait_generator.yaml, and qrLocomotionController::Reset
+ * (QS/controllers/qr_locomotion_controller.cpp:56-66) restarts timeSinceReset.  Two entry points, one launch each on the context's stream, one lane per
+ * robot; they change no other call.  The tick of tools/closed_loop.py --fsm-gait:
+ *     episode step, qrgpu_fsm_update_batch, qrgpu_stage_clock_batch, qrgpu_set_stage_reset, plant, observe ... qrgpu_gait_select_update_batch ...
+ *
+ * qrgpu_gait_select_update_batch: qrgpu_gait_update_batch with the parameters of robot r taken from table[k_r], k_r chosen by the robot.
+ *   table [n_gaits] (host; copied to the device when it differs from the table of the previous call), 1 <= n_gaits <= QRGPU_MAX_GAITS.
+ *   d_gait_sel [n] float32: the integer index of robot r's gait in table; with the state machine row 44 of d_fsm_state (d_fsm_state + 44 * n), whose
+ *     values are QRGPU_FSM_GAIT_*: 0 "none yet" is the gait the generator is constructed with.  It is read ONLY WHERE ROBOT r IS RESET AT THIS CALL -- the
+ *     reference re-reads the parameters in Reset and nowhere else: changing `gait` between resets does nothing.  The index in force is kept in row 48 of
+ *     d_gait_state and written back at every call; a call without a reset uses row 48, and a row 48 that does not hold an integer in [0, n_gaits) is
+ *     read as 0.  A selection that is NaN, not an integer or outside [0, n_gaits) selects entry 0 and raises QRGPU_GAIT_BAD_SEL in d_gait_flags[r]
+ *     (may be NULL).  That word is written at every call, 0 or the bit, never OR-ed; it is 0 where the selection was not read.
+ *   Reset and clock are qrgpu_gait_update_batch's, per robot, whether or not a binding is set: the scalar `reset` (0, QRGPU_GAIT_RESET_CONSTRUCT,
+ *     QRGPU_GAIT_RESET_LIVE) if it is non-zero; otherwise the bound level of qrgpu_set_stage_reset where (d_mask[r] & bits) != 0; otherwise none.  The
+ *     clock is (float)d_ticks[r] * tick_dt of the binding when it has d_ticks, else current_time.
+ *   A LIVE reset with a new entry is the reference's: the entry's initial_leg_state into the four leg-state vectors; resetTime, lastTime,
+ *     normalizedPhase, contactStartPhase = 0; gaitCycle, cumDt, firstSwing, firstStance, swingTimeRemaining, phaseInFullCycle and allowSwitchLegState
+ *     survive from the old gait (swingTimeRemaining keeps its last value for as long as the new gait commands no swing).  fullCyclePeriod,
+ *     swingDuration, dutyFactor, contactDetectionPhaseThreshold, waitTime and the advanced-trot hold are the entry's from that call on.
+ *   Rows 0-47 of d_gait_state, d_gait_out [24][n] (may be NULL) and rows 42-61 of d_fe_in (may be NULL) are written as qrgpu_gait_update_batch writes
+ *     them, dutyFactor (46-49) of the robot's entry.  d_swing_in (may be NULL): rows 8-11 = swingDuration of the entry in force,
+ *     stance_duration / duty_factor - stance_duration in float32 in that order, at every call; no other row of it.  Rows 49-51 of d_gait_state stay
+ *     spare and are not written.
+ *   QRGPU_ERR_BAD_ARG (nothing launched, outputs untouched; qrgpu_last_error names the argument): wherever qrgpu_gait_update_batch returns it; n_gaits
+ *     < 1 or > QRGPU_MAX_GAITS; a NULL table or d_gait_sel; an entry with a duty factor <= 0.001 or a stance duration <= 0 (USERDEFINED_SWING legs are
+ *     not supported).
+ * qrgpu_gait_table_default: the five entries QRGPU_FSM_GAIT_* index, from config/a1_sim/openloop_gait_generator.yaml: [0] and [2] advanced_trot (each
+ *   equal to qrgpu_gait_desc_default byte for byte), [1] trot (0.3, 0.6, phases (0.5, 0, 0, 0.5), threshold 0.5), [3] walk (7.5, 0.75, phases
+ *   (0.5, 0, 0.75, 0.25), threshold 0.1: the walk block's parameters in the OPEN-LOOP generator, as OnEnter does it), [4] stand (0.3, duty 1, phases 0,
+ *   threshold 0.1); advanced_trot = 0 in [1], [3], [4]; every entry starts its legs in STANCE and has qrgpu_gait_desc_default's wait_time.
+ *
+ * qrgpu_stage_clock_batch: where (d_mask[r] & bits) != 0, d_origin[r] = d_ticks[r]; then d_local[r] = d_ticks[r] - d_origin[r], in integers.  d_origin
+ *   [n] is the clock's memory: at the first call on a new one every robot is masked, or it is zeroed.  With d_mask = the state machine's d_stage_mask,
+ *   bits = QRGPU_EP_REASONS | QRGPU_FSM_ENTERED, d_ticks = row 0 of d_ep_state and d_local given to qrgpu_set_stage_reset as its d_ticks, every stage
+ *   that reads the binding's clock -- the gait, the walk gait, the stance update and the stance tick -- counts from the robot's last OnEnter or spawn:
+ *   resetTime = robot->GetTimeSinceReset().  No stage kernel changes for it.
+ *   QRGPU_ERR_BAD_ARG: a NULL array, bits == 0, n < 1, n > max_batch. */
+#define QRGPU_MAX_GAITS    8
+#define QRGPU_GAIT_BAD_SEL 0x1
+void qrgpu_gait_table_default(qrgpu_gait_desc table[5]);
+int  qrgpu_gait_select_update_batch(qrgpu_ctx *ctx, int n, const qrgpu_gait_desc *table /* host, [n_gaits] */, int n_gaits,
+                                    const float *d_gait_sel /* [n] */, float current_time, int robot_stop, int reset, const float *d_contact,
+                                    float *d_gait_state, float *d_gait_out, float *d_fe_in, float *d_swing_in /* may be NULL */,
+                                    int *d_gait_flags /* [n], may be NULL */);
+int  qrgpu_stage_clock_batch(qrgpu_ctx *ctx, int n, const int *d_mask, unsigned bits, const int *d_ticks, int *d_origin /* [n], memory */,
+                             int *d_local /* [n] */);
 
 /* ---- multi-GPU: all-gather of the per-robot torques over RCCL / xGMI ----------------------------------------
  * One process per GPU, one context per process; rank r of N owns a contiguous shard of the robot population and there is no exchange

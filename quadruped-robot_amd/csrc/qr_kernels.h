@@ -165,4 +165,10 @@ __global__ void qr_fsm_zero_kernel(int n, const int *g_plan, float *g_des, float
 __global__ void qr_fsm_command_kernel(int n, qrgpu_fsm_desc D, const int *g_plan, const float *g_est_in, const float *g_loco, float *g_st, float *g_cmd,
                                       float *g_out);
 
+// qr_gait_select_kernel.hip: one lane per robot; the open-loop gait generator on the table entry each robot latched at its last reset (the table in
+// device memory, indexed per lane), and the clock that counts from where a mask last said
+__global__ void qr_gait_select_kernel(int n, const qrgpu_gait_desc *g_table, int n_gaits, const float *g_sel, float currentTime, int stop, int fresh,
+                                      const float *g_contact, float *st, float *g_out, float *g_fe, float *g_sw, int *g_flags, StageResetArgs SR);
+__global__ void qr_stage_clock_kernel(int n, const int *g_mask, unsigned bits, const int *g_ticks, int *g_origin, int *g_local);
+
 }  // namespace qrgpu

@@ -101,6 +101,11 @@ struct qrgpu_ctx {
     // the stage kernels' per-robot reset and clock (qrgpu_set_stage_reset): while on, the stage entry points launch the _pr kernels
     qrgpu_stage_reset stage_reset{};
     bool stage_reset_on = false;
+    // the gait table of qrgpu_gait_select_update_batch: a device copy the kernel's lanes index themselves, allocated at the first call and uploaded
+    // when the caller's table differs from the one last uploaded
+    qrgpu_gait_desc gait_table_host[QRGPU_MAX_GAITS] = {};
+    qrgpu_gait_desc *d_gait_table = nullptr;
+    int gait_table_n = 0;
     // scratch for the single-robot calls and the fused tick
     // Staging of the single-robot calls.  Default: ONE block of pinned, mapped host memory that the kernels read and write in place (zero
     // copy: d_* are the device-side addresses of h_*), so a call is "fill h_in1, one launch, wait, read h_out1" with no copy command on the

@@ -26,6 +26,7 @@ ST_FLAG_MASK, ST_BAD_TYPE = 0xff0000ff, 0x01000000
 ST_MPC_MAXITER, ST_MPC_INFEAS, ST_MPC_OVERFLOW, ST_MPC_NOTSPD = 0x1, 0x2, 0x4, 0x8
 ST_WBC_MAXITER, ST_WBC_INFEAS = 0x10, 0x20
 GAIT_RESET_CONSTRUCT, GAIT_RESET_LIVE = 1, 2          # qrgpu_gait_update_batch's reset (include/qrgpu.h)
+MAX_GAITS, GAIT_BAD_SEL = 8, 0x1                      # qrgpu_gait_select_update_batch: the table's capacity, the bit of gait_flags
 FB_DEBUG_FLOATS = 324 + 18 + 18 + 216 + 12 + 12 + 12
 
 
@@ -376,7 +377,8 @@ EXPORTS = ["qrgpu_model_desc_default", "qrgpu_create", "qrgpu_destroy", "qrgpu_s
            "qrgpu_observe_desc_default", "qrgpu_observe_state_rows", "qrgpu_observe_batch",
            "qrgpu_command_desc_default", "qrgpu_command_update_batch", "qrgpu_trot_inputs_batch", "qrgpu_mpc_command_desc_default",
            "qrgpu_mpc_command_batch", "qrgpu_tick_cadence_batch",
-           "qrgpu_fsm_desc_default", "qrgpu_fsm_update_batch", "qrgpu_fsm_zero_command_batch", "qrgpu_fsm_command_batch"]
+           "qrgpu_fsm_desc_default", "qrgpu_fsm_update_batch", "qrgpu_fsm_zero_command_batch", "qrgpu_fsm_command_batch",
+           "qrgpu_gait_table_default", "qrgpu_gait_select_update_batch", "qrgpu_stage_clock_batch"]
 
 
 def load_library():
@@ -477,6 +479,9 @@ def load_library():
     lib.qrgpu_fsm_update_batch.argtypes = [vp, ip, C.POINTER(fsm_desc_struct), ip, vp, vp, ip, vp, vp, C.c_uint] + [vp] * 4
     lib.qrgpu_fsm_zero_command_batch.argtypes = [vp, ip] + [vp] * 6
     lib.qrgpu_fsm_command_batch.argtypes = [vp, ip, C.POINTER(fsm_desc_struct)] + [vp] * 6
+    lib.qrgpu_gait_table_default.argtypes = [C.POINTER(gait_desc_struct)]; lib.qrgpu_gait_table_default.restype = None
+    lib.qrgpu_gait_select_update_batch.argtypes = [vp, ip, C.POINTER(gait_desc_struct), ip, vp, C.c_float, ip, ip] + [vp] * 6
+    lib.qrgpu_stage_clock_batch.argtypes = [vp, ip, vp, C.c_uint, vp, vp, vp]
     lib.qrgpu_vmc_force1.argtypes = [vp, ip, fp, fp, fp, fp, C.POINTER(ip)]
     lib.qrgpu_vmc_force_world1.argtypes = [vp, ip, fp, fp, fp, fp, fp, C.POINTER(ip)]
     lib.qrgpu_mpc_frontend_batch.argtypes = [vp, ip, ip, C.c_float, C.c_float] + [vp] * 6
@@ -499,6 +504,22 @@ def load_library():
     lib.qrgpu_mark_elapsed_ms.argtypes = [vp, ip, ip, C.POINTER(C.c_double)]
     _LIB = lib
     return lib
+
+
+def _fill_gait_desc(d, cfg19):
+    for l in range(4):
+        d.stance_duration[l] = float(cfg19[l]); d.duty_factor[l] = float(cfg19[4 + l]); d.initial_leg_phase[l] = float(cfg19[8 + l])
+        d.initial_leg_state[l] = int(cfg19[12 + l])
+    d.contact_detection_phase_threshold = float(cfg19[16]); d.wait_time = float(cfg19[17]); d.advanced_trot = int(cfg19[18])
+
+
+def gait_table_default():
+    """qrgpu_gait_table_default: the five entries the FSM_GAIT_* values index ([0] the gait the generator is constructed with, trot, advanced_trot,
+    walk, stand) as [5][19] float32 rows in workload.gait_cfg()'s layout."""
+    d = (gait_desc_struct * 5)()
+    load_library().qrgpu_gait_table_default(d)
+    return np.array([[*e.stance_duration, *e.duty_factor, *e.initial_leg_phase, *e.initial_leg_state, e.contact_detection_phase_threshold, e.wait_time,
+                      e.advanced_trot] for e in d], np.float32)
 
 
 def _dp(x):
@@ -766,13 +787,34 @@ class Context:
         reset: True / GAIT_RESET_CONSTRUCT (1) = start from a generator as constructed, GAIT_RESET_LIVE (2) = Reset(0) on the running generator --
         the other way round from walk_gait_update_batch / swing_update_batch (include/qrgpu.h); any other value is refused."""
         d = gait_desc_struct()
-        cfg19 = np.asarray(cfg19, np.float32)
-        for l in range(4):
-            d.stance_duration[l] = float(cfg19[l]); d.duty_factor[l] = float(cfg19[4 + l]); d.initial_leg_phase[l] = float(cfg19[8 + l])
-            d.initial_leg_state[l] = int(cfg19[12 + l])
-        d.contact_detection_phase_threshold = float(cfg19[16]); d.wait_time = float(cfg19[17]); d.advanced_trot = int(cfg19[18])
+        _fill_gait_desc(d, np.asarray(cfg19, np.float32))
         self._chk(self._lib.qrgpu_gait_update_batch(self._h, n, C.byref(d), float(current_time), int(bool(stop)), int(reset), _dp(contact),
                                                     _dp(gait_state), _dp(gait_out), _dp(fe_in)))
+
+    def gait_select_update_batch(self, n, table, sel, current_time, contact, gait_state, gait_out=None, fe_in=None, swing_in=None, flags=None, stop=False,
+                                 reset=0):
+        """gait_update_batch with the gait per robot: table = a list of the 19-float rows workload.gait_cfg() makes (workload.gait_table(): [5][19]; at
+        most MAX_GAITS), sel [n] float32 on the device = each robot's index in it (row 44 of fsm_state: fsm_state.row(44)), read only where the robot
+        is reset at this call -- reset (0, GAIT_RESET_CONSTRUCT, GAIT_RESET_LIVE) if non-zero, else the level of set_stage_reset where its mask says --
+        and kept in row 48 of gait_state.  A bad selection runs entry 0 and sets GAIT_BAD_SEL in flags [n] int32.  swing_in: rows 8-11 receive the
+        swingDuration of the gait in force."""
+        key = np.asarray(table, np.float32).tobytes()
+        if getattr(self, "_gait_table", (None,))[0] != key:             # a loop passes the same table every tick: its structs are made once
+            rows = [np.asarray(r, np.float32) for r in table]
+            d = (gait_desc_struct * max(len(rows), 1))()
+            for e, r in zip(d, rows):
+                _fill_gait_desc(e, r)
+            self._gait_table = (key, d, len(rows))
+        _, d, count = self._gait_table
+        self._chk(self._lib.qrgpu_gait_select_update_batch(self._h, n, d, count, _dp(sel), float(current_time), int(bool(stop)), int(reset), _dp(contact),
+                                                           _dp(gait_state), _dp(gait_out), _dp(fe_in), _dp(swing_in), _dp(flags)))
+
+    def stage_clock(self, n, mask, bits, ticks, origin, local):
+        """The stage clock that restarts where the mask says: origin[r] = ticks[r] where (mask[r] & bits) != 0, then local[r] = ticks[r] - origin[r]
+        (all [n] int32 on the device; origin is the clock's memory: zeroed, or every robot masked at the first call).  With mask = fsm_update's
+        stage_mask, bits = EP_REASONS | FSM_ENTERED, ticks = row 0 of ep_state and local given to set_stage_reset as its ticks, the stages' clock counts
+        from the robot's last OnEnter or spawn."""
+        self._chk(self._lib.qrgpu_stage_clock_batch(self._h, n, _dp(mask), int(bits), _dp(ticks), _dp(origin), _dp(local)))
 
     def walk_gait_update_batch(self, n, cfg26, current_time, contact, walk_state, walk_out=None, ratio=None, vmc_in=None, stop=False, reset=0):
         """qrWalkGaitGenerator::Update of n robots + the walk branch of UpdateFRatio (qr_walk_gait_generator.cpp:202-288,

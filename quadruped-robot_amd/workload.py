@@ -533,6 +533,17 @@ def gait_cfg(stance_duration=0.5, duty_factor=0.6, initial_leg_phase=(0.5, 0.0, 
                      wait_time, 1.0 if advanced_trot else 0.0], dtype=f32)
 
 
+def gait_table():
+    """The five default rows of the gait table Context.gait_select_update_batch takes, indexed by the FSM_GAIT_* values
+    (config/a1_sim/openloop_gait_generator.yaml): [0] the gait the generator is constructed with and [2] advanced_trot, [1] trot, [3] the walk block in
+    the open-loop generator, [4] stand."""
+    return np.stack([gait_cfg(), gait_cfg(stance_duration=0.3, advanced_trot=False), gait_cfg(),
+                     gait_cfg(stance_duration=7.5, duty_factor=0.75, initial_leg_phase=(0.5, 0.0, 0.75, 0.25), contact_detection_phase_threshold=0.1,
+                              advanced_trot=False),
+                     gait_cfg(stance_duration=0.3, duty_factor=1.0, initial_leg_phase=(0.0, 0.0, 0.0, 0.0), contact_detection_phase_threshold=0.1,
+                              advanced_trot=False)])
+
+
 def walk_cfg(stance_duration=7.5, duty_factor=0.75, initial_leg_phase=(0.5, 0.0, 0.75, 0.25), initial_leg_state=(1, 1, 1, 1),
              contact_detection_phase_threshold=0.1, state_switch=(7, 6, 8, 5), state_ratio=(0.2, 0.3, 0.3, 0.2)):
     """Packed walk gait parameters (config/a1_sim/openloop_gait_generator.yaml, gait "walk"; SubLegState: load_force 5, unload_force 6,

@@ -11,6 +11,7 @@ inside the loop.
   python tools/closed_loop.py --trot [--cmd-vx 0.15] [--cmd-yaw 0.1] [--episodes] [--terrain ...]   the MPC trot, every stage on the device
   python tools/closed_loop.py --trot --cadence [...]                                  the same with the tick on the reference's cadence: MPC or WBC per robot
   python tools/closed_loop.py --fsm [--ticks 3000] [--cmd-vx 0.15] [--fsm-speed 1]    a robot's whole life cycle: sit, stand up, MPC standing, trot, fall, again
+  python tools/closed_loop.py --fsm --fsm-gait [...]                                  the same with every robot on the gait its state machine chose
 
 The robots are dropped from z = 0.30 onto joint PD at the stand pose (400 ticks of 1 ms), shoved by up to 0.3 m/s in x and y, and handed to
 MPC + WBC: qrgpu_plant_step_batch (include/qrgpu.h) writes the ground-truth mpc_state and fb_state the tick reads, and the tick -- the plain
@@ -59,9 +60,16 @@ sit-down angles, 0.14 above the ground; an episode ends by tilt, by a clearance 
 trunk: trunk contact is no reason here).  A device script keyed on each robot's episode tick presses X once the stand-up is over (to JOY_STAND) and X
 again with --cmd-vx / --cmd-yaw on the axes (to JOY_ADVANCED_TROT): a respawned robot goes through the same sequence again.  time_step is the
 tick's 0.002 x --fsm-speed and transition_ticks 500 / --fsm-speed: at speed 1 the stand-up takes 1500 ticks and the script presses at ticks 1600 and 2400.
+--fsm-gait (implies --fsm) lets the gait follow the machine: the gait call becomes qrgpu_gait_select_update_batch on row 44 of fsm_state over the default
+gait table, with swing_in given (rows 8-11: the swingDuration of each robot's gait), and the binding's clock comes from qrgpu_stage_clock_batch, so it
+counts from the robot's last OnEnter or spawn.  Without the flag the launches and the output are what they were.
 
   fsm, fsm_state_share (share of robots x timed ticks in PASSIVE, STAND_UP, LOCOMOTION), stood_up (robots that completed a stand-up), entered_locomotion,
                 fell_before_locomotion (robots whose first episode ended before they had entered locomotion): warm-up included, reported, not judged
+  fsm_gait, gait_share (--fsm-gait; share of robots x timed ticks on each entry of the gait table: none_yet, trot, advanced_trot, walk, stand, from
+                row 48 of gait_state), standing_robot_ticks (robots x ticks in LOCOMOTION under JOY_STAND, the "MPC standing" phase, warm-up included),
+                standing_swing_legs_commanded (legs that carried a swing command in them) beside standing_swing_legs_nominal_without (the legs the one
+                advanced_trot desc of --fsm schedules to swing in the same robot-ticks, on its clock from the spawn, holds ignored): reported, not judged
   ticks_per_s   closed-loop control ticks per second: every robot advances one tick per (plant step + controller tick)
   trot, cmd_vx, cmd_yaw, speed_along_command_mean (world x over the last 100 ticks, m/s, robots not respawned in them: speed_robots), yaw_rate_mean,
                 tick_flagged_share (share of ticks x robots whose tick status word carries a flag), swing_legs_commanded (legs x ticks x robots that
@@ -124,8 +132,10 @@ def main():
     ap.add_argument("--cadence", action="store_true", help="(--trot) the tick on the reference's cadence: per robot the MPC or the WBC, from the front-end's mask (qrgpu_tick_cadence_batch)")
     ap.add_argument("--fsm", action="store_true", help="the control state machine decides what every robot runs: sit, stand up, stand, trot (implies --trot --episodes)")
     ap.add_argument("--fsm-speed", type=float, default=1.0, metavar="S", help="(--fsm) run the stand-up and the transitions S times faster")
+    ap.add_argument("--fsm-gait", action="store_true", help="(implies --fsm) every robot on the gait its state machine chose, the stages' clock counted from its last OnEnter or spawn")
     ap.add_argument("--profile", action="store_true", help="the run a profiler traces: fewer ticks, nothing else changed")
     a = ap.parse_args()
+    a.fsm = a.fsm or a.fsm_gait
     a.trot = a.trot or a.fsm
     a.episodes = a.episodes or a.fsm
     if (a.cmd_vx != 0.0 or a.cmd_yaw != 0.0) and not a.trot:
@@ -217,6 +227,10 @@ def main():
                           [first_press + max(20, int(800 / a.fsm_speed)), q.JOY_BTN_X, a.cmd_yaw / fdesc.max_yawrate, 0.0, a.cmd_vx / fdesc.max_velx]], np.float32).T.copy()
         d.update(fsm_state=ctx.alloc((q.FSM_STATE_ROWS, n)), plan=ctx.alloc((n,), np.int32), stage_mask=ctx.alloc((n,), np.int32), script=ctx.alloc(press.shape).upload(press),
                  fsm_log=ctx.alloc((ticks + 20, q.FSM_OUT_ROWS, n)).zero(), plan_log=ctx.alloc((ticks + 20, n), np.int32).zero())
+    if a.fsm_gait:      # the gait table, the clock's memory and its output, the flags, every tick's index in force (row 48 of gait_state)
+        gtable = pkg.workload.gait_table()
+        d.update(clock_origin=ctx.alloc((n,), np.int32).zero(), clock_local=ctx.alloc((n,), np.int32).zero(), gait_flags=ctx.alloc((n,), np.int32),
+                 gait_log=ctx.alloc((ticks + 20, n)).zero())
 
     def plant(par, **out):
         if a.body:
@@ -259,7 +273,11 @@ def main():
             if a.fsm:                         # JoyCallback, the change request, RunFSM up to the decision: the joy rows, the plan, the stages' reset mask
                 ctx.fsm_update(n, fdesc, d["fsm_state"], d["joy"], d["plan"], stage_mask=d["stage_mask"], script=d["script"], n_script=2, ticks=d["ep_state"],
                                done=d["done_log"].row(done[0]), bits=pkg.qrgpu.EP_REASONS, reset=int(done[0] == 0))
-                ctx.set_stage_reset(mask=d["stage_mask"], bits=pkg.qrgpu.EP_REASONS | pkg.qrgpu.FSM_ENTERED, ticks=d["ep_state"])
+                if a.fsm_gait:                # the stages' clock counts from the robot's last OnEnter or spawn, not from the spawn alone
+                    ctx.stage_clock(n, d["stage_mask"], pkg.qrgpu.EP_REASONS | pkg.qrgpu.FSM_ENTERED, d["ep_state"], d["clock_origin"], d["clock_local"])
+                    ctx.set_stage_reset(mask=d["stage_mask"], bits=pkg.qrgpu.EP_REASONS | pkg.qrgpu.FSM_ENTERED, ticks=d["clock_local"])
+                else:
+                    ctx.set_stage_reset(mask=d["stage_mask"], bits=pkg.qrgpu.EP_REASONS | pkg.qrgpu.FSM_ENTERED, ticks=d["ep_state"])
             elif a.estimator and a.episodes:  # the observe, ground and estimator stages restart a robot this episode step respawned
                 ctx.set_stage_reset(mask=d["done_log"].row(done[0]), ticks=d["ep_state"])
             plant(params, plant_out=d["out"], mpc_state=d["mpc"], status=d["status_log"].row(done[0]) if a.body else d["plant_status"],
@@ -278,7 +296,12 @@ def main():
                 ctx.command_update(n, cdesc, d["joy"], d["cmd_state"], state_des=d["state_des"], fe_in=d["fe_in"], fh_in=d["fh_in"], reset=int(first))
                 if a.fsm:                     # SwitchMode / StandLoop: the robots in phase 1 run the chain on a zeroed command
                     ctx.fsm_zero_command(n, d["plan"], state_des=d["state_des"], fe_in=d["fe_in"], fh_in=d["fh_in"])
-                ctx.gait_update_batch(n, gcfg, t, d["est_in"].row(13), d["gait_state"], d["gait_out"], d["fe_in"], reset=first)
+                if a.fsm_gait:                # the gait OnEnter chose (row 44 of fsm_state), latched at the robot's reset; its swingDuration into swing_in
+                    ctx.gait_select_update_batch(n, gtable, d["fsm_state"].row(44), t, d["est_in"].row(13), d["gait_state"], d["gait_out"], d["fe_in"],
+                                                 swing_in=d["swing_in"], flags=d["gait_flags"], reset=int(first))
+                    ctx.copy_rows(d["gait_log"].row(k), d["gait_state"].row(48), n)
+                else:
+                    ctx.gait_update_batch(n, gcfg, t, d["est_in"].row(13), d["gait_state"], d["gait_out"], d["fe_in"], reset=first)
                 ctx.trot_inputs(n, d["est_in"], d["est_out"], d["rpy"], d["gait_out"], gait_state=d["gait_state"], fe_in=d["fe_in"], fh_in=d["fh_in"],
                                 swing_in=d["swing_in"], est_in_next=d["est_in"])
                 ctx.swing_update_batch(n, sdesc, d["est_in"], d["est_out"], d["gait_out"], d["swing_state"], d["swing_flags"], gait_state=d["gait_state"],
@@ -385,6 +408,20 @@ def main():
                    fsm_state_share={nm: float((timed == v).mean()) for nm, v in (("passive", q.FSM_PASSIVE), ("stand_up", q.FSM_STAND_UP), ("locomotion", q.FSM_LOCOMOTION))},
                    stood_up=int(((plans & q.FSM_PLAN_ACTION_END) != 0).any(0).sum()), entered_locomotion=int(loco.any(0).sum()),
                    fell_before_locomotion=int((first_end < first_loco).sum()))
+    if a.fsm_gait:    # which gait the robots ran, and what the stand gait does to the "MPC standing" phase: reported, not judged
+        names = ("none_yet", "trot", "advanced_trot", "walk", "stand")
+        index = d["gait_log"].download()[20:20 + ticks]                    # [tick][robot]: row 48 of gait_state
+        log = d["fsm_log"].download()
+        standing = (log[:, 0] == q.FSM_LOCOMOTION) & (log[:, 3] == q.RC_JOY_STAND)      # [tick][robot], warm-up included as swing_legs_commanded is
+        # the same robot-ticks under the one batch-wide desc of --fsm: the legs advanced_trot's nominal schedule swings on the clock from the spawn
+        dl = (d["done_log"].download() & q.EP_REASONS) != 0
+        at = np.arange(dl.shape[0])[:, None]
+        tsr = ((at - np.maximum.accumulate(np.where(dl, at, 0), axis=0)).astype(np.float32) * np.float32(0.002)).astype(np.float64)
+        full = float(gcfg[0]) / float(gcfg[4])
+        nominal = np.stack([np.fmod(float(gcfg[8 + l]) * full + tsr, full) / full >= float(gcfg[4]) for l in range(4)], axis=1)
+        res.update(fsm_gait=True, gait_share={nm: float((index == e).mean()) for e, nm in enumerate(names)}, standing_robot_ticks=int(standing.sum()),
+                   standing_swing_legs_commanded=int((swing & standing[:, None, :]).sum()),
+                   standing_swing_legs_nominal_without=int((nominal & standing[:, None, :]).sum()), gait_flags_seen=int(np.bitwise_or.reduce(d["gait_flags"].download())))
     print(json.dumps(res))
     ctx.close()
 
