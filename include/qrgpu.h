@@ -34,6 +34,9 @@
  *   qrgpu_stance_command_batch <- the motor-command tail of TorqueStanceLegController::GetAction (:503-541) + qrLocomotionController::GetAction's
  *                             merge with the swing command   QS/controllers/qr_locomotion_controller.cpp:128-147
  *   qrgpu_stance_tick_batch <- TorqueStanceLegController::GetAction (:480-545) + that merge: front-end, force-balance QP, motor commands
+ *   qrgpu_velocity_inputs_batch <- the reads of the velocity mode's controllers between those stages (the force-balance trot, JOY_TROT): swingFootIds,
+ *                             the inputs of qrRaibertSwingLegController::GetAction's VELOCITY case and the keys of swingJointAnglesVelocities with the
+ *                             command loop's flag   QS/controllers/qr_swing_leg_controller.cpp:100, 218-229, 256-276, 294, 306, 408-424, 446-448
  *   qrgpu_tick_batch       <- one MPC solve + one WBC tick per robot, WBC fed with that MPC's Fr_des
  *                             (QS/fsm/qr_fsm_state_locomotion.cpp:130-158 without the MPC/WBC time-slicing)
  *   qrgpu_tick_cadence_batch <- the same state WITH the time-slicing: per robot the MPC on the ticks that re-plan, the held force through the
@@ -1070,7 +1073,9 @@ int  qrgpu_observe_batch(qrgpu_ctx *ctx, int n, const qrgpu_observe_desc *desc, 
  *                      clip(filteredOmega[1] * dt, pitch); (2) is joycmdBodyHeight, times the double 0.85 where stateDes(6) < -0.01; the JOY_STAND and
  *                      else branches zero the filter state as well as the output; the filter is state * float(1.0 - filterFactor) + cmd * filterFactor.
  *   the rows the existing kernels read, no other row of those arrays touched: d_fe_in 0-5 (stateDes 2, 3, 4, 6, 7, 11), d_fh_in 16-20 (6, 7, 8, 11, 2),
- *                      d_swing_vel_in 23-26 (6, 7, 8, 11), d_stance_cmd 0-6 (2, 6, 7, 8, 9, 10, 11).  Each of the five outputs may be NULL. */
+ *                      d_swing_vel_in 23-26 (6, 7, 8, 11), d_stance_cmd 0-6 (2, 6, 7, 8, 9, 10, 11).  Each of the five outputs may be NULL.
+ *   Rows 23-26 of d_swing_vel_in are not where qrgpu_swing_velocity_batch reads these values (yaw rate 23, desiredSpeed 24-26, desiredTwistingSpeed 27):
+ *   the chain of the velocity mode passes d_swing_vel_in = NULL here and lets qrgpu_velocity_inputs_batch, which runs later, write rows 23-27. */
 #define QRGPU_JOY_ROWS 8
 #define QRGPU_CMD_STATE_ROWS 6
 struct qrgpu_command_desc {
@@ -1131,6 +1136,37 @@ typedef struct qrgpu_mpc_command_desc qrgpu_mpc_command_desc;
 void qrgpu_mpc_command_desc_default(qrgpu_mpc_command_desc *d);
 int  qrgpu_mpc_command_batch(qrgpu_ctx *ctx, int n, const qrgpu_mpc_command_desc *desc, int reset, const float *d_tau, const float *d_qdes,
                              const float *d_swing_in, const float *d_gait_out, const float *d_gait_state, int *d_cmd_mem, float *d_motor_cmd);
+
+/* qrgpu_velocity_inputs_batch: the data-flow stage of the velocity mode -- the force-balance trot, LocomotionMode::VELOCITY_LOCOMOTION with
+ * TorqueStanceLegController and the VELOCITY case of the swing controller (JOY_TROT: qr_fsm_state_locomotion.cpp:98-101,
+ * qr_stance_leg_controller_interface.cpp:85-93).  What qrgpu_trot_inputs_batch and the memory of qrgpu_mpc_command_batch are to the MPC trot: the reads
+ * the controllers make on qrRobot, qrStateDataFlow, the estimator and the gait generator between the stages, and the keys of
+ * swingJointAnglesVelocities.  One launch on the context's stream, one lane per robot, workgroups of 64; copies, compares and integer bit operations.
+ * The order of a tick: command update (d_swing_vel_in NULL), gait, this call, swing update (mode VELOCITY, given d_swing_vel_in: rows 8-19),
+ * qrgpu_swing_velocity_batch, qrgpu_stance_tick_batch (mode VELOCITY, d_swing_q and d_swing_flag as below).
+ * Reads d_est_in (quat_wxyz 6-9, yaw rate 12, motor angles 17-28), d_est_out (rows 6-8: stateEstimator->GetEstimatedVelocity(), which
+ * qr_robot_velocity_estimator.cpp:126-131 leaves in the base frame -- the estimator kernel's baseVelocityInBaseFrame), d_ground_out (baseRInControlFrame
+ * 22-30; read on terrain >= 2 alone, may be NULL below), d_gait_out [24][n] (normalizedPhase 4-7, desiredLegState 8-11, legState 12-15), d_gait_state
+ * (allowSwitchLegState 20-23), d_state_des [12][n] of qrgpu_command_update_batch.  terrain: the TerrainType, 0..4 (PLANE, PLUM_PILES, STAIRS, SLOPE, ROUGH).
+ * Writes, each of the four arrays may be NULL, no other row touched:
+ *   d_swing_vel_in  0-3 the leg is in swingFootIds: not ((legState STANCE and allowSwitchLegState) or legState EARLY_CONTACT), 1 or 0
+ *               (qr_swing_leg_controller.cpp:218-229); 4-7 normalizedPhase; 20-22 the estimated velocity; 23 GetBaseRollPitchYawRate()(2); 24-27 stateDes 6,
+ *               7, 8, 11 -- the rows qr_swing_velocity_kernel reads, whatever qrgpu_command_update_batch or qrgpu_fsm_zero_command_batch put into rows
+ *               23-26 before this call; 28-36 dR and 37-40 the quaternion of robotBaseR: the identity and (1, 0, 0, 0) on terrain < 2 (:271-276), else
+ *               baseRInControlFrame and quat_wxyz; 41-52 motor angles.  Rows 8-19 (phaseSwitchFootLocalPos) are qrgpu_swing_update_batch's.
+ *   d_est_in_next   rows 41-44: desiredLegState of this tick's gait, as qrgpu_trot_inputs_batch writes them.  Usually d_est_in itself: the rows written are
+ *               not among the rows read, and a lane loads every row it reads before its first store.  No other two arrays may overlap.
+ *   d_cmd_mem [1][n] int  bit l: leg l has an entry in swingJointAnglesVelocities.  reset 1 clears it for every robot (Reset(), :100), a stage-reset
+ *               binding's mask per robot when the scalar is 0; then every leg of swingFootIds is added (GetAction, :408-424).  Required with d_swing_flag.
+ *   d_swing_flag [4][n]  1 or 0: leg l has an entry and desiredLegState[l] == SWING (the VELOCITY case of the command loop, :446-448): the d_swing_flag of
+ *               qrgpu_stance_command_batch / qrgpu_stance_tick_batch.
+ * The values of the map are not kept by this call: they are rows 24-47 of qrgpu_swing_velocity_batch's d_out, which that kernel writes for the flagged
+ * legs alone, so the array keeps a leg's last targets as the map does; d_swing_q of qrgpu_stance_command_batch is that d_out + 24 * n.
+ * QRGPU_ERR_BAD_ARG, nothing launched, qrgpu_last_error naming the argument: n, terrain outside 0..4, reset other than 0 or 1, a NULL d_est_in, d_est_out,
+ * d_gait_out, d_gait_state or d_state_des, a NULL d_ground_out on terrain >= 2, d_swing_flag without d_cmd_mem. */
+int  qrgpu_velocity_inputs_batch(qrgpu_ctx *ctx, int n, int terrain, int reset, const float *d_est_in, const float *d_est_out, const float *d_ground_out,
+                                 const float *d_gait_out, const float *d_gait_state, const float *d_state_des, float *d_swing_vel_in, float *d_est_in_next,
+                                 int *d_cmd_mem, float *d_swing_flag);
 
 /* ---- the control state machine: joystick, stand-up, transitions ---------------------------------------------------------------------------------
  * What decides when a robot is in qrFSMStateLocomotion::Run, per robot and per tick, with no host decision: qrDesiredStateCommand::JoyCallback and the

@@ -171,4 +171,9 @@ __global__ void qr_gait_select_kernel(int n, const qrgpu_gait_desc *g_table, int
                                       const float *g_contact, float *st, float *g_out, float *g_fe, float *g_sw, int *g_flags, StageResetArgs SR);
 __global__ void qr_stage_clock_kernel(int n, const int *g_mask, unsigned bits, const int *g_ticks, int *g_origin, int *g_local);
 
+// qr_velocity_flow_kernel.hip: one lane per robot; the getters between the stages of the force-balance trot, the entries of its swing command
+__global__ void qr_velocity_flow_kernel(int n, int terrain, int reset, StageResetArgs R, const float *g_est_in, const float *g_est_out, const float *g_ground,
+                                        const float *g_gait_out, const float *g_gait_state, const float *g_des, float *g_sv, float *g_est_w, int *g_mem,
+                                        float *g_flag);
+
 }  // namespace qrgpu

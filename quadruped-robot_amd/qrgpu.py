@@ -378,7 +378,7 @@ EXPORTS = ["qrgpu_model_desc_default", "qrgpu_create", "qrgpu_destroy", "qrgpu_s
            "qrgpu_command_desc_default", "qrgpu_command_update_batch", "qrgpu_trot_inputs_batch", "qrgpu_mpc_command_desc_default",
            "qrgpu_mpc_command_batch", "qrgpu_tick_cadence_batch",
            "qrgpu_fsm_desc_default", "qrgpu_fsm_update_batch", "qrgpu_fsm_zero_command_batch", "qrgpu_fsm_command_batch",
-           "qrgpu_gait_table_default", "qrgpu_gait_select_update_batch", "qrgpu_stage_clock_batch"]
+           "qrgpu_gait_table_default", "qrgpu_gait_select_update_batch", "qrgpu_stage_clock_batch", "qrgpu_velocity_inputs_batch"]
 
 
 def load_library():
@@ -482,6 +482,8 @@ def load_library():
     lib.qrgpu_gait_table_default.argtypes = [C.POINTER(gait_desc_struct)]; lib.qrgpu_gait_table_default.restype = None
     lib.qrgpu_gait_select_update_batch.argtypes = [vp, ip, C.POINTER(gait_desc_struct), ip, vp, C.c_float, ip, ip] + [vp] * 6
     lib.qrgpu_stage_clock_batch.argtypes = [vp, ip, vp, C.c_uint, vp, vp, vp]
+    if hasattr(lib, "qrgpu_velocity_inputs_batch"):        # (an older build named by QRGPU_LIB for an A/B run has no force-balance trot chain)
+        lib.qrgpu_velocity_inputs_batch.argtypes = [vp, ip, ip, ip] + [vp] * 10
     lib.qrgpu_vmc_force1.argtypes = [vp, ip, fp, fp, fp, fp, C.POINTER(ip)]
     lib.qrgpu_vmc_force_world1.argtypes = [vp, ip, fp, fp, fp, fp, fp, C.POINTER(ip)]
     lib.qrgpu_mpc_frontend_batch.argtypes = [vp, ip, ip, C.c_float, C.c_float] + [vp] * 6
@@ -1005,6 +1007,15 @@ class Context:
         1 clears it for every robot, a stage-reset binding's mask per robot."""
         self._chk(self._lib.qrgpu_mpc_command_batch(self._h, n, C.byref(desc), int(reset), _dp(tau), _dp(qdes), _dp(swing_in), _dp(gait_out), _dp(gait_state),
                                                     _dp(cmd_mem), _dp(motor_cmd)))
+
+    def velocity_inputs(self, n, est_in, est_out, gait_out, gait_state, state_des, ground_out=None, swing_vel_in=None, est_in_next=None, cmd_mem=None,
+                        swing_flag=None, terrain=0, reset=0):
+        """The getters between the stages of the force-balance trot (mode VELOCITY): swing_vel_in rows 0-7 and 20-52 (rows 8-19 are
+        swing_update_batch's), rows 41-44 of est_in_next (usually est_in itself), cmd_mem [1][n] int32 (the legs with a swing entry, bit per leg; reset
+        1 clears it for every robot, a stage-reset binding's mask per robot) and swing_flag [4][n] for stance_tick_batch, whose swing_q is row 24 of
+        swing_velocity_batch's output.  ground_out is read on terrain >= 2 alone.  Each output is optional; swing_flag needs cmd_mem."""
+        self._chk(self._lib.qrgpu_velocity_inputs_batch(self._h, n, int(terrain), int(reset), _dp(est_in), _dp(est_out), _dp(ground_out), _dp(gait_out),
+                                                        _dp(gait_state), _dp(state_des), _dp(swing_vel_in), _dp(est_in_next), _dp(cmd_mem), _dp(swing_flag)))
 
     def fsm_state_rows(self):
         """Rows of fsm_state, the control state machine's memory (float32; the first fsm_update on new arrays is a reset)."""

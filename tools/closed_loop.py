@@ -12,6 +12,7 @@ inside the loop.
   python tools/closed_loop.py --trot --cadence [...]                                  the same with the tick on the reference's cadence: MPC or WBC per robot
   python tools/closed_loop.py --fsm [--ticks 3000] [--cmd-vx 0.15] [--fsm-speed 1]    a robot's whole life cycle: sit, stand up, MPC standing, trot, fall, again
   python tools/closed_loop.py --fsm --fsm-gait [...]                                  the same with every robot on the gait its state machine chose
+  python tools/closed_loop.py --fb-trot [--cmd-vx 0.15] [--cmd-yaw 0.1] [--episodes] [--terrain ...]   the force-balance trot, every stage on the device
 
 The robots are dropped from z = 0.30 onto joint PD at the stand pose (400 ticks of 1 ms), shoved by up to 0.3 m/s in x and y, and handed to
 MPC + WBC: qrgpu_plant_step_batch (include/qrgpu.h) writes the ground-truth mpc_state and fb_state the tick reads, and the tick -- the plain
@@ -64,6 +65,18 @@ tick's 0.002 x --fsm-speed and transition_ticks 500 / --fsm-speed: at speed 1 th
 gait table, with swing_in given (rows 8-11: the swingDuration of each robot's gait), and the binding's clock comes from qrgpu_stage_clock_batch, so it
 counts from the robot's last OnEnter or spawn.  Without the flag the launches and the output are what they were.
 
+--fb-trot (implies --estimator and --body; not with --trot, --cadence or --fsm) runs the reference's force-balance trot -- JOY_TROT:
+LocomotionMode::VELOCITY_LOCOMOTION with TorqueStanceLegController and the velocity case of the swing controller -- closed on the device.  Per tick, with
+no host copy: [episode step,] plant, observe, ground (its output kept: the stance stage reads it), estimator, qrgpu_command_update_batch (--cmd-vx /
+--cmd-yaw in mode JOY_TROT, uploaded once; it writes stateDes and rows 0-6 of stance_cmd, swing_vel_in / fe_in / fh_in not given), gait (the `trot` entry
+of qrgpu_gait_table_default), qrgpu_velocity_inputs_batch, swing update (mode VELOCITY: the lift-off rows of swing_vel_in), qrgpu_swing_velocity_batch (the
+entry's stance duration), qrgpu_stance_tick_batch (mode VELOCITY; swing_q = row 24 of the swing-velocity output, swing_flag from the inputs stage), whose
+motor command the plant reads.  Rows 7-27 of stance_cmd (the walk pose plan's and the position mode's, which VELOCITY does not read) hold the stand pose
+and zeros, uploaded once.  --terrain picks the TerrainType the stages get: flat and gap PLANE, stairs STAIRS, plane SLOPE, rough ROUGH.  With --episodes
+the stage-reset binding also clears the swing-command entries of a respawned robot.  Whether the batch trots, drifts or falls is reported, not judged.
+
+  fb_trot, cmd_vx, cmd_yaw, speed_along_command_mean / speed_robots (as --trot), swing_legs_commanded (legs x ticks x robots whose swing flag was set,
+                warm-up included; _per_robot_tick), vmc_flagged_share (share of ticks x robots whose force-balance QP status word carries a flag)
   fsm, fsm_state_share (share of robots x timed ticks in PASSIVE, STAND_UP, LOCOMOTION), stood_up (robots that completed a stand-up), entered_locomotion,
                 fell_before_locomotion (robots whose first episode ended before they had entered locomotion): warm-up included, reported, not judged
   fsm_gait, gait_share (--fsm-gait; share of robots x timed ticks on each entry of the gait table: none_yet, trot, advanced_trot, walk, stand, from
@@ -133,17 +146,20 @@ def main():
     ap.add_argument("--fsm", action="store_true", help="the control state machine decides what every robot runs: sit, stand up, stand, trot (implies --trot --episodes)")
     ap.add_argument("--fsm-speed", type=float, default=1.0, metavar="S", help="(--fsm) run the stand-up and the transitions S times faster")
     ap.add_argument("--fsm-gait", action="store_true", help="(implies --fsm) every robot on the gait its state machine chose, the stages' clock counted from its last OnEnter or spawn")
+    ap.add_argument("--fb-trot", action="store_true", help="the force-balance trot (JOY_TROT, mode VELOCITY) closed on the device: command, gait, velocity inputs, swing, stance tick (implies --estimator --body)")
     ap.add_argument("--profile", action="store_true", help="the run a profiler traces: fewer ticks, nothing else changed")
     a = ap.parse_args()
     a.fsm = a.fsm or a.fsm_gait
+    if a.fb_trot and (a.trot or a.cadence or a.fsm):
+        ap.error("--fb-trot excludes --trot, --cadence and --fsm")
     a.trot = a.trot or a.fsm
     a.episodes = a.episodes or a.fsm
-    if (a.cmd_vx != 0.0 or a.cmd_yaw != 0.0) and not a.trot:
-        ap.error("--cmd-vx / --cmd-yaw need --trot")
+    if (a.cmd_vx != 0.0 or a.cmd_yaw != 0.0) and not (a.trot or a.fb_trot):
+        ap.error("--cmd-vx / --cmd-yaw need --trot or --fb-trot")
     if a.cadence and not a.trot:
         ap.error("--cadence needs --trot")
-    a.estimator = a.estimator or a.trot
-    a.body = a.body or a.episodes or a.trot
+    a.estimator = a.estimator or a.trot or a.fb_trot
+    a.body = a.body or a.episodes or a.trot or a.fb_trot
     if a.sensor_noise != 0.0 and not a.estimator:
         ap.error("--sensor-noise needs --estimator")
     pkg = _load_pkg()
@@ -219,6 +235,23 @@ def main():
             d.update(hold=ctx.alloc((12, n)).zero(), due_log=ctx.alloc((ticks + 20, n), np.int32).zero())
             d["force"].zero()
 
+    if a.fb_trot:       # the force-balance trot's stages: their memory, the arrays they hand one another, the operator's command (uploaded once)
+        q, W = pkg.qrgpu, pkg.workload
+        ttype = dict(flat=0, gap=0, stairs=2, plane=3, rough=4)[kind]                   # TerrainType: PLANE, STAIRS, SLOPE, ROUGH
+        cdesc, sdesc, stdesc = pkg.command_desc(), pkg.swing_mode_desc(q.MODE_VELOCITY, terrain=ttype), pkg.stance_desc(q.MODE_VELOCITY, terrain=ttype)
+        gcfg = pkg.gait_table_default()[q.FSM_GAIT_TROT]                              # advanced_trot 0
+        svcfg = W.swing_velocity_cfg("a1", stance_duration=float(gcfg[0]))
+        ctx.vmc_setup_packed(0, W.vmc_cfg("a1"), pkg.model_desc("a1")[:3])
+        joy = np.zeros((q.JOY_ROWS, n), np.float32); joy[0] = a.cmd_vx; joy[5] = a.cmd_yaw; joy[6] = cdesc.body_height; joy[7] = q.RC_JOY_TROT
+        scmd = np.zeros((28, n), np.float32); scmd[9] = HEIGHT; scmd[15] = HEIGHT          # rows 7-27: not read in VELOCITY
+        d.update(joy=ctx.alloc((q.JOY_ROWS, n)).upload(joy), cmd_state=ctx.alloc((q.CMD_STATE_ROWS, n)), state_des=ctx.alloc((12, n)),
+                 stance_cmd=ctx.alloc((28, n)).upload(scmd), gout=ctx.alloc((32, n)), gait_state=ctx.alloc((52, n)), gait_out=ctx.alloc((24, n)),
+                 swing_state=ctx.alloc((q.SWING_STATE_FLOATS, n)), swing_flags=ctx.alloc((n,), np.int32), sv=ctx.alloc((53, n)).zero(),
+                 sv_out=ctx.alloc((48, n)).zero(), cmd_mem=ctx.alloc((1, n), np.int32).zero(), swing_flag=ctx.alloc((4, n)).zero(),
+                 stance_state=ctx.alloc((q.STANCE_STATE_FLOATS, n)), vmc_in=ctx.alloc((37, n)), ratio=ctx.alloc((8, n)), stance_out=ctx.alloc((33, n)),
+                 tau=ctx.alloc((12, n)), vmc_log=ctx.alloc((ticks + 20, n), np.int32).zero(), flag_log=ctx.alloc((ticks + 20, 4, n)).zero(),
+                 fb_then=ctx.alloc_pinned((37, n)))
+
     if a.fsm:           # the machine's memory, what it hands the stages, its per-tick report, the script (X after the stand-up, X with the command)
         q = pkg.qrgpu
         up = int(np.ceil(fdesc.stand_up_total / fdesc.time_step))
@@ -286,10 +319,28 @@ def main():
                 first = done[0] == 0
                 ctx.observe_batch(n, odesc, d["est_in"], d["obs"], d["est_in"], d["rpy"], ground_in=d["gin"], tick=d["stamp"], est_out_prev=d["est_out"],
                                   reset=first, step=done[0])
-                ctx.ground_update_batch(n, d["gin"], d["gst"], None, d["est_in"], reset=first)
+                ctx.ground_update_batch(n, d["gin"], d["gst"], d["gout"] if a.fb_trot else None, d["est_in"], reset=first)
                 ctx.estimator_update_batch(n, ecfg, d["est_in"], d["stamp"], d["est_state"], d["est_out"])
-                ctx.pack_state_batch(n, com, d["est_in"], d["est_out"], d["rpy"], d["mpc_est"], d["fb_est"])
+                if not a.fb_trot:             # (the force-balance chain reads est_in / est_out themselves: packed once after the loop, for the report)
+                    ctx.pack_state_batch(n, com, d["est_in"], d["est_out"], d["rpy"], d["mpc_est"], d["fb_est"])
             done[0] += 1
+            if a.fb_trot:                     # qrLocomotionController::Update / GetAction of the velocity mode, in the reference's order
+                k = done[0] - 1
+                t = float(np.float32(k) * np.float32(0.002))                   # (under --episodes the gait and the stance stage run on the binding's clock)
+                ctx.command_update(n, cdesc, d["joy"], d["cmd_state"], state_des=d["state_des"], stance_cmd=d["stance_cmd"], reset=int(first))
+                ctx.gait_update_batch(n, gcfg, t, d["est_in"].row(13), d["gait_state"], d["gait_out"], reset=first)
+                ctx.velocity_inputs(n, d["est_in"], d["est_out"], d["gait_out"], d["gait_state"], d["state_des"], ground_out=d["gout"], swing_vel_in=d["sv"],
+                                    est_in_next=d["est_in"], cmd_mem=d["cmd_mem"], swing_flag=d["swing_flag"], terrain=ttype, reset=int(first))
+                ctx.swing_update_batch(n, sdesc, d["est_in"], d["est_out"], d["gait_out"], d["swing_state"], d["swing_flags"], swing_vel_in=d["sv"],
+                                       reset=2 if first else 0)
+                ctx.swing_velocity_batch(n, ecfg, svcfg, d["sv"], d["sv_out"])
+                ctx.stance_tick_batch(n, stdesc, d["est_in"], d["est_out"], d["gout"], d["rpy"], d["gait_out"], d["stance_cmd"], d["stance_state"], d["vmc_in"],
+                                      d["force"], d["tau"], d["cmd"], gait_state=d["gait_state"], ratio=d["ratio"], stance_out=d["stance_out"],
+                                      status=d["vmc_log"].row(k), swing_q=d["sv_out"].row(24), swing_flag=d["swing_flag"], current_time=t, reset=first)
+                ctx.copy_rows(d["flag_log"].row(k), d["swing_flag"], 4 * n)    # the report's log: the legs that carried a swing command this tick
+                if k == total[0] - 101:
+                    d["fb"].copy_to_pinned(d["fb_then"])                       # the truth 100 ticks before the end, for the mean speed
+                continue
             if a.trot:                        # qrLocomotionController::Update / GetAction, qrFSMStateLocomotion::Run, in the reference's order
                 k = done[0] - 1
                 t = float(np.float32(k) * np.float32(0.002))                   # (under --episodes the gait runs on the binding's per-robot clock)
@@ -333,11 +384,15 @@ def main():
     loop(ticks)
     ctx.sync()
     sec = time.perf_counter() - t0
+    if a.fb_trot:     # the estimate in the tick's layout, for the report below
+        ctx.pack_state_batch(n, com, d["est_in"], d["est_out"], d["rpy"], d["mpc_est"], d["fb_est"])
+        ctx.sync()
     fb = d["fb"].download()
     rp = _rpy(fb[0:4].T)
     ok = (np.abs(fb[6] - HEIGHT) <= 0.01) & (np.abs(fb[4:6]).max(0) <= 0.03) & (np.abs(rp).max(1) <= 0.03)
     tick_log = d["tick_log"].download() if a.trot else None
-    tick_flags = pkg.status_flags(tick_log[-1] if a.trot else d["tick_status"].download())
+    vmc_log = d["vmc_log"].download() if a.fb_trot else None
+    tick_flags = pkg.status_flags(tick_log[-1] if a.trot else vmc_log[-1] if a.fb_trot else d["tick_status"].download())
     log = d["status_log"].download() if a.body else None
     plant_flags = log[-1] if a.body else d["plant_status"].download()
     res = dict(metric="closed_loop_ticks_per_s", value=ticks / sec, robot_ticks_per_s=n * ticks / sec, ms_per_tick=1e3 * sec / ticks, robots=n, ticks=ticks,
@@ -384,6 +439,12 @@ def main():
                    swing_flags_seen=int(np.bitwise_or.reduce(d["swing_flags"].download())))
         if a.cadence:
             res.update(cadence=True, mpc_due_share=float((d["due_log"].download()[20:20 + ticks] != 0).mean()))
+    if a.fb_trot:     # what the force-balance trot did: reported, not judged
+        swing = d["flag_log"].download() != 0                             # [tick][leg][robot]
+        res.update(fb_trot=True, cmd_vx=a.cmd_vx, cmd_yaw=a.cmd_yaw, vmc_flagged_share=float((pkg.status_flags(vmc_log) != 0).mean()),
+                   swing_legs_commanded=int(swing.sum()), swing_legs_commanded_per_robot_tick=float(swing.sum(1).mean()),
+                   swing_flags_seen=int(np.bitwise_or.reduce(d["swing_flags"].download())))
+    if a.trot or a.fb_trot:
         if ticks >= 81:   # mean base speed along the command over the last 100 ticks, from the plant's truth; robots respawned in that window left out
             then = d["fb_then"].array
             calm = np.isfinite(fb).all(0) & np.isfinite(then).all(0)
