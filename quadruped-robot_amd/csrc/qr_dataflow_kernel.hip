@@ -18,20 +18,20 @@
 namespace qrgpu {
 
 // the robot's reset: the call's scalar, or its mask word under a binding; unbound, the lane reads a word of `own` (a column it loads anyway) instead
-__device__ __forceinline__ bool dataflow_reset(const StageResetArgs &R, int reset, const void *own, int i)
+__device__ __forceinline__ bool dataflow_reset(const StageResetArgs &SR, int reset, const void *own, int i)
 {
-    const unsigned *mp = R.mask ? (const unsigned *)R.mask + i : (const unsigned *)own + i;
-    const unsigned bits = R.mask ? R.bits : 0u;
+    const unsigned *mp = SR.mask ? (const unsigned *)SR.mask + i : (const unsigned *)own + i;
+    const unsigned bits = SR.mask ? SR.bits : 0u;
     return (reset != 0) | ((*mp & bits) != 0u);
 }
 
-__global__ void __launch_bounds__(64) qr_command_kernel(int n, qrgpu_command_desc D, int reset, StageResetArgs R, const float *__restrict__ g_joy,
+__global__ void __launch_bounds__(64) qr_command_kernel(int n, qrgpu_command_desc D, int reset, StageResetArgs SR, const float *__restrict__ g_joy,
                                                         float *__restrict__ g_st, float *__restrict__ g_des, float *__restrict__ g_fe, float *__restrict__ g_fh,
                                                         float *__restrict__ g_sv, float *__restrict__ g_sc)
 {
     const int i = (int)blockIdx.x * 64 + (int)threadIdx.x;
     if (i >= n) return;
-    const bool rst = dataflow_reset(R, reset, g_joy, i);
+    const bool rst = dataflow_reset(SR, reset, g_joy, i);
     dataflow::command_update(D, rst, (size_t)n, g_joy + i, g_st + i, g_des ? g_des + i : nullptr, g_fe ? g_fe + i : nullptr, g_fh ? g_fh + i : nullptr,
                              g_sv ? g_sv + i : nullptr, g_sc ? g_sc + i : nullptr);
 }
@@ -46,13 +46,13 @@ __global__ void __launch_bounds__(64) qr_trot_inputs_kernel(int n, const float *
                           g_fh ? g_fh + i : nullptr, g_sw ? g_sw + i : nullptr, g_est_w ? g_est_w + i : nullptr);
 }
 
-__global__ void __launch_bounds__(64) qr_mpc_command_kernel(int n, qrgpu_mpc_command_desc D, int reset, StageResetArgs R, const float *__restrict__ g_tau,
+__global__ void __launch_bounds__(64) qr_mpc_command_kernel(int n, qrgpu_mpc_command_desc D, int reset, StageResetArgs SR, const float *__restrict__ g_tau,
                                                             const float *__restrict__ g_qdes, const float *__restrict__ g_sw, const float *__restrict__ g_gait_out,
                                                             const float *__restrict__ g_gait_state, int *__restrict__ g_mem, float *__restrict__ g_cmd)
 {
     const int i = (int)blockIdx.x * 64 + (int)threadIdx.x;
     if (i >= n) return;
-    const bool rst = dataflow_reset(R, reset, g_tau, i);
+    const bool rst = dataflow_reset(SR, reset, g_tau, i);
     dataflow::mpc_command(D, rst, (size_t)n, g_tau + i, g_qdes + i, g_sw + i, g_gait_out + i, g_gait_state + i, g_mem + i, g_cmd + i);
 }
 

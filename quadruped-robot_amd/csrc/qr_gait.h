@@ -1,6 +1,6 @@
 // The open-loop gait generator with the gait chosen per robot, and the stage clock that restarts where a mask says: what qr_gait_select_kernel and
 // qr_stage_clock_kernel (qr_gait_select_kernel.hip) run per lane.  float32 + - x / with contraction off, exact fmodf, every operation in the order of
-// qr_gait_kernel (qr_estimator_stages.inc.h) and of tests/gait_ref.py.  Every function is __host__ __device__: the same text compiles for a CPU check
+// qr_gait_kernel (qr_estimator_kernel.hip) and of tests/gait_ref.py.  Every function is __host__ __device__: the same text compiles for a CPU check
 // against tests/gait_select_ref.py (tests/stubs/gait_select_host.hip).  include/qrgpu.h states the rules.
 //   qrOpenLoopGaitGenerator::Reset                  quadruped/src/gait/qr_openloop_gait_generator.cpp:77-123 (re-reads the block of `gait`)
 //   qrOpenLoopGaitGenerator::Update, Schedule       :126-207, :210-249 (legs with a non-zero duty factor)

@@ -45,46 +45,9 @@ __global__ void qr_wbc_kernel_dbg(int n, const WbcConst *types, const int *type_
                                   float *g_prev, float *g_tau, float *g_qdes, int *g_status, float *g_dbg, int merge_tau, int status_or, long long *dbgT,
                                   const float *g_fr, int type_ready, int epilogue, float *g_qp, WbcPipe pipe);
 
-// qr_frontend_kernel.hip, qr_vmc_kernel.hip
-__global__ void qr_frontend_kernel(int n, int horizon, int numHorizonL, float dt, float dtMPC, int period, const float *fin, float *fst,
-                                   float *g_traj, float *g_gait, float *g_cmd, int *g_updated);
-__global__ void qr_vmc_kernel(VmcLaunch P, const int *type_id, const float *g_in, const float *g_q, float *g_force, float *g_tau, int *g_status);
-
-// qr_estimator_kernel.hip
-__global__ void qr_estimator_kernel(int n, qrgpu_estimator_desc D, const float *g_in, const unsigned *g_tick, double *st, float *g_out);
-__global__ void qr_pack_state_kernel(int n, float c0, float c1, float c2, const float *g_in, const float *g_est, const float *g_rpy, float *g_mpc, float *g_fb);
-__global__ void qr_swing_kernel(int n, qrgpu_estimator_desc D, const float *g_in, float *g_cmd, float *g_tgt_world, float *g_qdes);
-__global__ void qr_gait_kernel(int n, qrgpu_gait_desc D, float currentTime, int stop, int fresh, const float *g_contact, float *st, float *g_out, float *g_fe);
-__global__ void qr_foothold_kernel(int n, qrgpu_foothold_desc D, const float *g_in, const float *g_gait_state, const float *g_gait_out, float *g_swing);
-__global__ void qr_ground_kernel(int n, int fresh, const float *g_in, double *g_st, float *g_out, float *g_est_in);
-__global__ void qr_walk_gait_kernel(int n, WalkDesc D, float currentTime, int stop, int fresh, const float *g_contact, float *st, float *g_out, float *g_ratio,
-                                    float *g_vmc_in);
-__global__ void qr_swing_velocity_kernel(int n, qrgpu_estimator_desc D, qrgpu_swing_velocity_desc V, const float *g_in, float *g_out);
-
-// qr_swing_modes_kernel.hip, qr_stance_kernel.hip, qr_pose_plan_kernel.hip
-__global__ void qr_swing_update_kernel(int n, qrgpu_swing_mode_desc M, int reset, int stop, const float *g_est_in, const float *g_est_out, const float *g_gait_out,
-                                       float *g_st, float *g_swing_in, float *g_swing_vel_in, float *g_fe_in, int *g_flags);
-__global__ void qr_swing_action_kernel(int n, qrgpu_swing_mode_desc M, qrgpu_estimator_desc D, int stop, const float *g_est_in, const float *g_est_out,
-                                       const float *g_gait_out, const float *g_gait_state, float *g_st, float *g_out, int *g_flags);
-__global__ void qr_stance_update_kernel(int n, qrgpu_stance_desc S, float current_time, int stop, int reset, const float *g_est_in, const float *g_est_out,
-                                        const float *g_ground, const float *g_rpy, const float *g_gait_out, const float *g_gait_state, const float *g_cmd,
-                                        float *g_st, float *g_vmc_in, float *g_ratio, float *g_out);
-__global__ void qr_stance_command_kernel(int n, qrgpu_stance_desc S, int stop, const float *g_vmc_in, const float *g_stance_out, const float *g_tau,
-                                         const float *g_swing_q, const float *g_swing_flag, float *g_cmd);
-__global__ void qr_pose_plan_kernel(int n, qrgpu_pose_plan_desc D, int event, const int *g_event, int reset, const float *g_est_in, const float *g_est_out,
-                                    const float *g_ground, const float *g_rpy, const float *g_walk, float *g_state, float *g_cmd, float *g_out, int *g_flags);
-
-// The per-robot forms of the eight stage kernels with memory (qrgpu_set_stage_reset): the same kernel text, compiled a second time with
-// QR_STAGE_PR 1 (the *.inc.h files beside the kernel files), which names it NAME_pr and gives it the binding as one more argument.  The binding's level
-// is already the stage's own number (the front-end takes the QRGPU_STAGE_RESET_* value itself).
-#define QR_STAGE_CAT_(a, b) a##b
-#define QR_STAGE_CAT(a, b) QR_STAGE_CAT_(a, b)
-#define QR_STAGE_K_0(name) name
-#define QR_STAGE_K_1(name) name##_pr
-#define QR_STAGE_PARAM_0
-#define QR_STAGE_PARAM_1 , StageResetArgs SR
-#define QR_STAGE_K(name) QR_STAGE_CAT(QR_STAGE_K_, QR_STAGE_PR)(name)
-#define QR_STAGE_PARAM QR_STAGE_CAT(QR_STAGE_PARAM_, QR_STAGE_PR)
+// The binding of qrgpu_set_stage_reset as a stage kernel takes it, always its last argument: robot i is reset at `level` -- already the stage's own
+// number; the front-end takes the QRGPU_STAGE_RESET_* value itself -- where mask[i] & bits, and its clock is ticks[i] * tick_dt.  A null mask resets
+// nobody and a null tick array leaves the call's scalar clock: that is every caller that has bound nothing.
 struct StageResetArgs {
     const int *mask;      // [n] or null
     unsigned bits;
@@ -93,28 +56,43 @@ struct StageResetArgs {
     float tick_dt;
 };
 // Robot i's mask word (0 without a mask) and clock (the call's scalar without a tick array): one row load each, issued with the first state loads.
-__device__ __forceinline__ bool stage_masked(const StageResetArgs &R, int i) { return R.mask && ((unsigned)R.mask[i] & R.bits) != 0u; }
-__device__ __forceinline__ float stage_time(const StageResetArgs &R, int i, float scalar)
+__device__ __forceinline__ bool stage_masked(const StageResetArgs &SR, int i) { return SR.mask && ((unsigned)SR.mask[i] & SR.bits) != 0u; }
+__device__ __forceinline__ float stage_time(const StageResetArgs &SR, int i, float scalar)
 {
 #pragma clang fp contract(off)
-    return R.ticks ? (float)R.ticks[i] * R.tick_dt : scalar;
+    return SR.ticks ? (float)SR.ticks[i] * SR.tick_dt : scalar;
 }
-__global__ void qr_frontend_kernel_pr(int n, int horizon, int numHorizonL, float dt, float dtMPC, int period, const float *fin, float *fst,
-                                      float *g_traj, float *g_gait, float *g_cmd, int *g_updated, StageResetArgs R);
-__global__ void qr_estimator_kernel_pr(int n, qrgpu_estimator_desc D, const float *g_in, const unsigned *g_tick, double *st, float *g_out, StageResetArgs R);
-__global__ void qr_gait_kernel_pr(int n, qrgpu_gait_desc D, float currentTime, int stop, int fresh, const float *g_contact, float *st, float *g_out, float *g_fe,
-                                  StageResetArgs R);
-__global__ void qr_ground_kernel_pr(int n, int fresh, const float *g_in, double *g_st, float *g_out, float *g_est_in, StageResetArgs R);
-__global__ void qr_walk_gait_kernel_pr(int n, WalkDesc D, float currentTime, int stop, int fresh, const float *g_contact, float *st, float *g_out, float *g_ratio,
-                                       float *g_vmc_in, StageResetArgs R);
-__global__ void qr_swing_update_kernel_pr(int n, qrgpu_swing_mode_desc M, int reset, int stop, const float *g_est_in, const float *g_est_out, const float *g_gait_out,
-                                          float *g_st, float *g_swing_in, float *g_swing_vel_in, float *g_fe_in, int *g_flags, StageResetArgs R);
-__global__ void qr_stance_update_kernel_pr(int n, qrgpu_stance_desc S, float current_time, int stop, int reset, const float *g_est_in, const float *g_est_out,
-                                           const float *g_ground, const float *g_rpy, const float *g_gait_out, const float *g_gait_state, const float *g_cmd,
-                                           float *g_st, float *g_vmc_in, float *g_ratio, float *g_out, StageResetArgs R);
-__global__ void qr_pose_plan_kernel_pr(int n, qrgpu_pose_plan_desc D, int event, const int *g_event, int reset, const float *g_est_in, const float *g_est_out,
-                                       const float *g_ground, const float *g_rpy, const float *g_walk, float *g_state, float *g_cmd, float *g_out, int *g_flags,
-                                       StageResetArgs R);
+
+// qr_frontend_kernel.hip, qr_vmc_kernel.hip
+__global__ void qr_frontend_kernel(int n, int horizon, int numHorizonL, float dt, float dtMPC, int period, const float *fin, float *fst,
+                                   float *g_traj, float *g_gait, float *g_cmd, int *g_updated, StageResetArgs SR);
+__global__ void qr_vmc_kernel(VmcLaunch P, const int *type_id, const float *g_in, const float *g_q, float *g_force, float *g_tau, int *g_status);
+
+// qr_estimator_kernel.hip
+__global__ void qr_estimator_kernel(int n, qrgpu_estimator_desc D, const float *g_in, const unsigned *g_tick, double *st, float *g_out, StageResetArgs SR);
+__global__ void qr_pack_state_kernel(int n, float c0, float c1, float c2, const float *g_in, const float *g_est, const float *g_rpy, float *g_mpc, float *g_fb);
+__global__ void qr_swing_kernel(int n, qrgpu_estimator_desc D, const float *g_in, float *g_cmd, float *g_tgt_world, float *g_qdes);
+__global__ void qr_gait_kernel(int n, qrgpu_gait_desc D, float currentTime, int stop, int fresh, const float *g_contact, float *st, float *g_out, float *g_fe,
+                               StageResetArgs SR);
+__global__ void qr_foothold_kernel(int n, qrgpu_foothold_desc D, const float *g_in, const float *g_gait_state, const float *g_gait_out, float *g_swing);
+__global__ void qr_ground_kernel(int n, int fresh, const float *g_in, double *g_st, float *g_out, float *g_est_in, StageResetArgs SR);
+__global__ void qr_walk_gait_kernel(int n, WalkDesc D, float currentTime, int stop, int fresh, const float *g_contact, float *st, float *g_out, float *g_ratio,
+                                    float *g_vmc_in, StageResetArgs SR);
+__global__ void qr_swing_velocity_kernel(int n, qrgpu_estimator_desc D, qrgpu_swing_velocity_desc V, const float *g_in, float *g_out);
+
+// qr_swing_modes_kernel.hip, qr_stance_kernel.hip, qr_pose_plan_kernel.hip
+__global__ void qr_swing_update_kernel(int n, qrgpu_swing_mode_desc M, int reset, int stop, const float *g_est_in, const float *g_est_out, const float *g_gait_out,
+                                       float *g_st, float *g_swing_in, float *g_swing_vel_in, float *g_fe_in, int *g_flags, StageResetArgs SR);
+__global__ void qr_swing_action_kernel(int n, qrgpu_swing_mode_desc M, qrgpu_estimator_desc D, int stop, const float *g_est_in, const float *g_est_out,
+                                       const float *g_gait_out, const float *g_gait_state, float *g_st, float *g_out, int *g_flags);
+__global__ void qr_stance_update_kernel(int n, qrgpu_stance_desc S, float current_time, int stop, int reset, const float *g_est_in, const float *g_est_out,
+                                        const float *g_ground, const float *g_rpy, const float *g_gait_out, const float *g_gait_state, const float *g_cmd,
+                                        float *g_st, float *g_vmc_in, float *g_ratio, float *g_out, StageResetArgs SR);
+__global__ void qr_stance_command_kernel(int n, qrgpu_stance_desc S, int stop, const float *g_vmc_in, const float *g_stance_out, const float *g_tau,
+                                         const float *g_swing_q, const float *g_swing_flag, float *g_cmd);
+__global__ void qr_pose_plan_kernel(int n, qrgpu_pose_plan_desc D, int event, const int *g_event, int reset, const float *g_est_in, const float *g_est_out,
+                                    const float *g_ground, const float *g_rpy, const float *g_walk, float *g_state, float *g_cmd, float *g_out, int *g_flags,
+                                    StageResetArgs SR);
 
 // qr_plant_kernel.hip: four lanes per robot, sixteen robots per workgroup of one wavefront
 __global__ void qr_fwd_dyn_kernel(int n, const WbcConst *types, const int *type_id, int type_ready, const float *g_state, const float *g_tau, const float *g_ff,
@@ -138,15 +116,15 @@ __global__ void qr_episode_kernel(int n, qrgpu_episode_desc D, double cos_tilt, 
                                   int *g_count);
 
 // qr_observe_kernel.hip: one lane per robot; ReceiveObservation's filters, yaw logic and quaternion, the inputs of the ground and estimator stages
-__global__ void qr_observe_kernel(int n, qrgpu_observe_desc D, int reset, unsigned step, StageResetArgs R, const float *g_raw, const float *g_prev, float *g_st,
+__global__ void qr_observe_kernel(int n, qrgpu_observe_desc D, int reset, unsigned step, StageResetArgs SR, const float *g_raw, const float *g_prev, float *g_st,
                                   float *g_est_in, float *g_rpy, float *g_ground_in, unsigned *g_tick);
 
 // qr_dataflow_kernel.hip: one lane per robot; the operator's command, the getters between the trot's stages, the motor command of the MPC mode
-__global__ void qr_command_kernel(int n, qrgpu_command_desc D, int reset, StageResetArgs R, const float *g_joy, float *g_st, float *g_des, float *g_fe, float *g_fh,
+__global__ void qr_command_kernel(int n, qrgpu_command_desc D, int reset, StageResetArgs SR, const float *g_joy, float *g_st, float *g_des, float *g_fe, float *g_fh,
                                   float *g_sv, float *g_sc);
 __global__ void qr_trot_inputs_kernel(int n, const float *g_est_in, const float *g_est_out, const float *g_rpy, const float *g_gait_out, const float *g_gait_state,
                                       float *g_fe, float *g_fh, float *g_sw, float *g_est_w);
-__global__ void qr_mpc_command_kernel(int n, qrgpu_mpc_command_desc D, int reset, StageResetArgs R, const float *g_tau, const float *g_qdes, const float *g_sw,
+__global__ void qr_mpc_command_kernel(int n, qrgpu_mpc_command_desc D, int reset, StageResetArgs SR, const float *g_tau, const float *g_qdes, const float *g_sw,
                                       const float *g_gait_out, const float *g_gait_state, int *g_mem, float *g_cmd);
 
 // qr_cadence_kernel.hip: one lane per robot; between the MPC and the WBC launch of the cadenced tick: the kept base-frame force of the robots just
@@ -172,7 +150,7 @@ __global__ void qr_gait_select_kernel(int n, const qrgpu_gait_desc *g_table, int
 __global__ void qr_stage_clock_kernel(int n, const int *g_mask, unsigned bits, const int *g_ticks, int *g_origin, int *g_local);
 
 // qr_velocity_flow_kernel.hip: one lane per robot; the getters between the stages of the force-balance trot, the entries of its swing command
-__global__ void qr_velocity_flow_kernel(int n, int terrain, int reset, StageResetArgs R, const float *g_est_in, const float *g_est_out, const float *g_ground,
+__global__ void qr_velocity_flow_kernel(int n, int terrain, int reset, StageResetArgs SR, const float *g_est_in, const float *g_est_out, const float *g_ground,
                                         const float *g_gait_out, const float *g_gait_state, const float *g_des, float *g_sv, float *g_est_w, int *g_mem,
                                         float *g_flag);
 

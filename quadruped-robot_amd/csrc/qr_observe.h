@@ -83,7 +83,7 @@ QR_HD void rpy_to_quat(const float rpy[3], float q[4])
     }
 }
 
-// FootPositionsInBaseFrame, one leg (qr_robot.cpp:127-146, :174-183; the formula of qr_estimator_stages.inc.h:24-34)
+// FootPositionsInBaseFrame, one leg (qr_robot.cpp:127-146, :174-183; the formula of qr_estimator_kernel, qr_estimator_kernel.hip)
 QR_HD void foot_position(const qrgpu_observe_desc &D, int leg, float t0, float t1, float t2, float p[3])
 {
 #pragma clang fp contract(off)

@@ -16,7 +16,7 @@
 
 namespace qrgpu {
 
-__global__ void __launch_bounds__(64) qr_observe_kernel(int n, qrgpu_observe_desc D, int reset, unsigned step, StageResetArgs R, const float *g_raw, const float *g_prev,
+__global__ void __launch_bounds__(64) qr_observe_kernel(int n, qrgpu_observe_desc D, int reset, unsigned step, StageResetArgs SR, const float *g_raw, const float *g_prev,
                                                         float *__restrict__ g_st, float *g_est_in, float *__restrict__ g_rpy, float *__restrict__ g_ground_in,
                                                         unsigned *__restrict__ g_tick)
 {
@@ -24,8 +24,8 @@ __global__ void __launch_bounds__(64) qr_observe_kernel(int n, qrgpu_observe_des
     if (i >= n) return;
     // the mask word's load is the first of the lane's loads, not a gate in front of them: no branch on the binding -- unbound, the lane reads a word of
     // its own raw column instead and holds it against bits 0
-    const unsigned *mp = R.mask ? (const unsigned *)R.mask + i : (const unsigned *)g_raw + i;
-    const unsigned bits = R.mask ? R.bits : 0u;
+    const unsigned *mp = SR.mask ? (const unsigned *)SR.mask + i : (const unsigned *)g_raw + i;
+    const unsigned bits = SR.mask ? SR.bits : 0u;
     const bool rst = (reset != 0) | ((*mp & bits) != 0u);
     observe::step(D, rst, (unsigned)i, step, (size_t)n, g_raw + i, g_prev ? g_prev + i : nullptr, g_st + i, g_est_in + i, g_rpy + i,
                   g_ground_in ? g_ground_in + i : nullptr, g_tick ? g_tick + i : nullptr);

@@ -7,7 +7,7 @@
 //   qrRaibertSwingLegController::GetAction    :256-258 (motor angles, yaw rate, estimated velocity), :271-276 (dR and robotBaseR on horizontal terrain),
 //                                             :294 (stateDes 6-8, 11), :306 (normalizedPhase), :408-424 (the map's entries), :446-448 (the VELOCITY flag)
 //   qrRobotVelocityEstimator::Update          quadruped/src/estimators/qr_robot_velocity_estimator.cpp:126-131: estimatedVelocity is left in the base
-//                                             frame, the value robot->baseVelocityInBaseFrame receives: rows 6-8 of est_out (qr_estimator_stages.inc.h)
+//                                             frame, the value robot->baseVelocityInBaseFrame receives: rows 6-8 of est_out (qr_estimator_kernel.hip)
 // The values of swingJointAnglesVelocities are not kept here: they are rows 24-47 of qrgpu_swing_velocity_batch's output, which that kernel writes for the
 // flagged legs alone, so the array keeps a leg's last targets as the map does (d_swing_q of qrgpu_stance_command_batch is that d_out + 24 * n).
 // Row k of an array lies at p[k * S]: the kernel passes the robot's column and S = n, a packed record has S = 1.

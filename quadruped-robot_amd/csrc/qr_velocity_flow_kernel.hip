@@ -15,7 +15,7 @@
 
 namespace qrgpu {
 
-__global__ void __launch_bounds__(64) qr_velocity_flow_kernel(int n, int terrain, int reset, StageResetArgs R, const float *g_est_in, const float *__restrict__ g_est_out,
+__global__ void __launch_bounds__(64) qr_velocity_flow_kernel(int n, int terrain, int reset, StageResetArgs SR, const float *g_est_in, const float *__restrict__ g_est_out,
                                                               const float *__restrict__ g_ground, const float *__restrict__ g_gait_out,
                                                               const float *__restrict__ g_gait_state, const float *__restrict__ g_des, float *__restrict__ g_sv,
                                                               float *g_est_w, int *__restrict__ g_mem, float *__restrict__ g_flag)
@@ -23,8 +23,8 @@ __global__ void __launch_bounds__(64) qr_velocity_flow_kernel(int n, int terrain
     const int i = (int)blockIdx.x * 64 + (int)threadIdx.x;
     if (i >= n) return;
     // the robot's reset: the call's scalar, or its mask word under a binding; unbound, the lane reads a word of a column it loads anyway
-    const unsigned *mp = R.mask ? (const unsigned *)R.mask + i : (const unsigned *)g_gait_out + i;
-    const unsigned bits = R.mask ? R.bits : 0u;
+    const unsigned *mp = SR.mask ? (const unsigned *)SR.mask + i : (const unsigned *)g_gait_out + i;
+    const unsigned bits = SR.mask ? SR.bits : 0u;
     const bool rst = (reset != 0) | ((*mp & bits) != 0u);
     velocity_flow::velocity_inputs(terrain, rst, (size_t)n, g_est_in + i, g_est_out + i, g_ground ? g_ground + i : nullptr, g_gait_out + i, g_gait_state + i,
                                    g_des + i, g_sv ? g_sv + i : nullptr, g_est_w ? g_est_w + i : nullptr, g_mem ? g_mem + i : nullptr,

@@ -98,9 +98,8 @@ struct qrgpu_ctx {
     qrgpu_plant_body_desc *d_body = nullptr;
     bool body_ready[QRGPU_MAX_TYPES] = {false, false, false, false};
     bool body_dirty = true;
-    // the stage kernels' per-robot reset and clock (qrgpu_set_stage_reset): while on, the stage entry points launch the _pr kernels
+    // the stage kernels' per-robot reset and clock (qrgpu_set_stage_reset); all zeros while nothing is bound
     qrgpu_stage_reset stage_reset{};
-    bool stage_reset_on = false;
     // the gait table of qrgpu_gait_select_update_batch: a device copy the kernel's lanes index themselves, allocated at the first call and uploaded
     // when the caller's table differs from the one last uploaded
     qrgpu_gait_desc gait_table_host[QRGPU_MAX_GAITS] = {};
@@ -268,6 +267,16 @@ inline int ready_mask(const bool *r) { int m = 0; for (int t = 0; t < QRGPU_MAX_
 
 // The check every batched entry point starts with.
 inline bool batch_ok(const qrgpu_ctx *c, int n) { return c && n > 0 && n <= c->max_batch; }
+
+// The binding of qrgpu_set_stage_reset as the stage kernels take it: the bound level in the stage's own numbers, the mask and the clock.  With
+// nothing bound c->stage_reset is all zeros, and both forms are the unbound struct: a null mask, a null tick array.
+inline StageResetArgs stage_args(const qrgpu_ctx *c, int construct, int live)
+{
+    const qrgpu_stage_reset &b = c->stage_reset;
+    return StageResetArgs{b.d_mask, b.bits, b.level == QRGPU_STAGE_RESET_CONSTRUCT ? construct : live, b.d_ticks, b.tick_dt};
+}
+// The mask alone, for the stages with one reset level and no clock.
+inline StageResetArgs stage_mask_args(const qrgpu_ctx *c) { return StageResetArgs{c->stage_reset.d_mask, c->stage_reset.bits, 1, nullptr, 0.f}; }
 
 // A device allocation that lives as long as the scope that made it: freed on every exit path, an early HIPCHK return included.
 struct DeviceScratch {

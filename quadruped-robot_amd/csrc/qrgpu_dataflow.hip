@@ -24,12 +24,6 @@ static int dataflow_launch(qrgpu_ctx *c, void (*kernel)(KArgs...), int n, Args..
     return QRGPU_OK;
 }
 
-// the binding as the kernels take it, always: a null mask is "unbound"; the clock is not read
-static StageResetArgs dataflow_binding(const qrgpu_ctx *c)
-{
-    return c->stage_reset_on ? StageResetArgs{c->stage_reset.d_mask, c->stage_reset.bits, 1, nullptr, 0.f} : StageResetArgs{nullptr, 0u, 1, nullptr, 0.f};
-}
-
 extern "C" {
 
 void qrgpu_command_desc_default(qrgpu_command_desc *d)
@@ -51,7 +45,7 @@ int qrgpu_command_update_batch(qrgpu_ctx *c, int n, const qrgpu_command_desc *de
     if (reset != 0 && reset != 1) return dataflow_bad(c, me, "reset");
     if (!d_joy) return dataflow_bad(c, me, "d_joy");
     if (!d_cmd_state) return dataflow_bad(c, me, "d_cmd_state");
-    return dataflow_launch(c, qr_command_kernel, n, *desc, reset, dataflow_binding(c), d_joy, d_cmd_state, d_state_des, d_fe_in, d_fh_in, d_swing_vel_in,
+    return dataflow_launch(c, qr_command_kernel, n, *desc, reset, stage_mask_args(c), d_joy, d_cmd_state, d_state_des, d_fe_in, d_fh_in, d_swing_vel_in,
                            d_stance_cmd);
 }
 
@@ -95,7 +89,7 @@ int qrgpu_mpc_command_batch(qrgpu_ctx *c, int n, const qrgpu_mpc_command_desc *d
     if (!d_gait_state) return dataflow_bad(c, me, "d_gait_state");
     if (!d_cmd_mem) return dataflow_bad(c, me, "d_cmd_mem");
     if (!d_motor_cmd) return dataflow_bad(c, me, "d_motor_cmd");
-    return dataflow_launch(c, qr_mpc_command_kernel, n, *desc, reset, dataflow_binding(c), d_tau, d_qdes, d_swing_in, d_gait_out, d_gait_state, d_cmd_mem,
+    return dataflow_launch(c, qr_mpc_command_kernel, n, *desc, reset, stage_mask_args(c), d_tau, d_qdes, d_swing_in, d_gait_out, d_gait_state, d_cmd_mem,
                            d_motor_cmd);
 }
 

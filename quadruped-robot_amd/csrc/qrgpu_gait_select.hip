@@ -67,13 +67,9 @@ int qrgpu_gait_select_update_batch(qrgpu_ctx *c, int n, const qrgpu_gait_desc *t
         HIPCHK(c, hipStreamSynchronize(c->stream));
         c->gait_table_n = n_gaits;
     }
-    // the per-robot form always: without a binding, no mask and the scalar clock
-    const qrgpu_stage_reset &b = c->stage_reset;
-    const StageResetArgs R = c->stage_reset_on
-        ? StageResetArgs{b.d_mask, b.bits, b.level == QRGPU_STAGE_RESET_CONSTRUCT ? QRGPU_GAIT_RESET_CONSTRUCT : QRGPU_GAIT_RESET_LIVE, b.d_ticks, b.tick_dt}
-        : StageResetArgs{nullptr, 0u, QRGPU_GAIT_RESET_CONSTRUCT, nullptr, 0.f};
     return gs_launch(c, qr_gait_select_kernel, n, (const qrgpu_gait_desc *)c->d_gait_table, n_gaits, d_gait_sel, current_time, robot_stop ? 1 : 0, reset, d_contact,
-                     d_gait_state, d_gait_out, d_fe_in, d_swing_in, d_gait_flags, R);
+                     d_gait_state, d_gait_out, d_fe_in, d_swing_in, d_gait_flags,
+                     stage_args(c, QRGPU_GAIT_RESET_CONSTRUCT, QRGPU_GAIT_RESET_LIVE));
 }
 
 int qrgpu_stage_clock_batch(qrgpu_ctx *c, int n, const int *d_mask, unsigned bits, const int *d_ticks, int *d_origin, int *d_local)

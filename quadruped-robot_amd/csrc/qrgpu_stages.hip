@@ -22,13 +22,6 @@ static int launch_stage(qrgpu_ctx *c, void (*kernel)(KArgs...), dim3 grid, dim3 
 // Robot i is thread i: workgroups of one wavefront.
 static dim3 per_robot(int n) { return dim3((n + 63) / 64); }
 
-// The binding of qrgpu_set_stage_reset as a _pr kernel takes it: the bound level in the stage's own numbers.
-static StageResetArgs stage_args(const qrgpu_ctx *c, int construct, int live)
-{
-    const qrgpu_stage_reset &b = c->stage_reset;
-    return StageResetArgs{b.d_mask, b.bits, b.level == QRGPU_STAGE_RESET_CONSTRUCT ? construct : live, b.d_ticks, b.tick_dt};
-}
-
 extern "C" {
 
 void qrgpu_estimator_desc_default(qrgpu_estimator_desc *d)
@@ -48,8 +41,7 @@ int qrgpu_estimator_update_batch(qrgpu_ctx *c, int n, const qrgpu_estimator_desc
 {
     if (!batch_ok(c, n) || !desc || !d_est_in || !d_tick || !d_est_state || !d_est_out) return QRGPU_ERR_BAD_ARG;
     if (desc->window <= 0 || desc->window > 4096) return QRGPU_ERR_BAD_ARG;
-    if (c->stage_reset_on) return launch_stage(c, qr_estimator_kernel_pr, per_robot(n), dim3(64), n, *desc, d_est_in, d_tick, d_est_state, d_est_out, stage_args(c, 1, 1));
-    return launch_stage(c, qr_estimator_kernel, per_robot(n), dim3(64), n, *desc, d_est_in, d_tick, d_est_state, d_est_out);
+    return launch_stage(c, qr_estimator_kernel, per_robot(n), dim3(64), n, *desc, d_est_in, d_tick, d_est_state, d_est_out, stage_args(c, 1, 1));
 }
 
 void qrgpu_gait_desc_default(qrgpu_gait_desc *d)
@@ -67,10 +59,8 @@ int qrgpu_gait_update_batch(qrgpu_ctx *c, int n, const qrgpu_gait_desc *desc, fl
     if (!batch_ok(c, n) || !desc || !d_contact || !d_gait_state) return QRGPU_ERR_BAD_ARG;
     if (reset != 0 && reset != QRGPU_GAIT_RESET_CONSTRUCT && reset != QRGPU_GAIT_RESET_LIVE) return QRGPU_ERR_BAD_ARG;
     for (int l = 0; l < 4; ++l) if (!(desc->duty_factor[l] > 0.001f) || !(desc->stance_duration[l] > 0.f)) return QRGPU_ERR_BAD_ARG;   // USERDEFINED_SWING legs are not built
-    if (c->stage_reset_on)
-        return launch_stage(c, qr_gait_kernel_pr, per_robot(n), dim3(64), n, *desc, current_time, robot_stop, reset, d_contact, d_gait_state, d_gait_out, d_fe_in,
-                            stage_args(c, QRGPU_GAIT_RESET_CONSTRUCT, QRGPU_GAIT_RESET_LIVE));
-    return launch_stage(c, qr_gait_kernel, per_robot(n), dim3(64), n, *desc, current_time, robot_stop, reset, d_contact, d_gait_state, d_gait_out, d_fe_in);
+    return launch_stage(c, qr_gait_kernel, per_robot(n), dim3(64), n, *desc, current_time, robot_stop, reset, d_contact, d_gait_state, d_gait_out, d_fe_in,
+                        stage_args(c, QRGPU_GAIT_RESET_CONSTRUCT, QRGPU_GAIT_RESET_LIVE));
 }
 
 void qrgpu_walk_gait_desc_default(qrgpu_walk_gait_desc *d)
@@ -119,17 +109,14 @@ int qrgpu_walk_gait_update_batch(qrgpu_ctx *c, int n, const qrgpu_walk_gait_desc
         }
     }
     D.contact_detection_phase_threshold = desc->contact_detection_phase_threshold;
-    if (c->stage_reset_on)
-        return launch_stage(c, qr_walk_gait_kernel_pr, per_robot(n), dim3(64), n, D, current_time, robot_stop, reset, d_contact, d_walk_state, d_walk_out, d_ratio, d_vmc_in,
-                            stage_args(c, 2, 1));
-    return launch_stage(c, qr_walk_gait_kernel, per_robot(n), dim3(64), n, D, current_time, robot_stop, reset, d_contact, d_walk_state, d_walk_out, d_ratio, d_vmc_in);
+    return launch_stage(c, qr_walk_gait_kernel, per_robot(n), dim3(64), n, D, current_time, robot_stop, reset, d_contact, d_walk_state, d_walk_out, d_ratio, d_vmc_in,
+                        stage_args(c, 2, 1));
 }
 
 int qrgpu_ground_update_batch(qrgpu_ctx *c, int n, int reset, const float *d_ground_in, double *d_ground_state, float *d_ground_out, float *d_est_in)
 {
     if (!batch_ok(c, n) || !d_ground_in || !d_ground_state) return QRGPU_ERR_BAD_ARG;
-    if (c->stage_reset_on) return launch_stage(c, qr_ground_kernel_pr, per_robot(n), dim3(64), n, reset, d_ground_in, d_ground_state, d_ground_out, d_est_in, stage_args(c, 1, 1));
-    return launch_stage(c, qr_ground_kernel, per_robot(n), dim3(64), n, reset, d_ground_in, d_ground_state, d_ground_out, d_est_in);
+    return launch_stage(c, qr_ground_kernel, per_robot(n), dim3(64), n, reset, d_ground_in, d_ground_state, d_ground_out, d_est_in, stage_args(c, 1, 1));
 }
 
 void qrgpu_foothold_desc_default(qrgpu_foothold_desc *d)
@@ -192,11 +179,8 @@ int qrgpu_swing_update_batch(qrgpu_ctx *c, int n, const qrgpu_swing_mode_desc *d
     qrgpu_swing_mode_desc M;
     if (!batch_ok(c, n) || !swing_mode_desc(desc, M) || reset < 0 || reset > 2) return QRGPU_ERR_BAD_ARG;
     if (!d_est_in || !d_est_out || !d_gait_out || !d_swing_state || !d_swing_flags) return QRGPU_ERR_BAD_ARG;
-    if (c->stage_reset_on)
-        return launch_stage(c, qr_swing_update_kernel_pr, per_robot(n), dim3(64), n, M, reset, robot_stop ? 1 : 0, d_est_in, d_est_out, d_gait_out, d_swing_state, d_swing_in,
-                            d_swing_vel_in, d_fe_in, d_swing_flags, stage_args(c, 2, 1));
     return launch_stage(c, qr_swing_update_kernel, per_robot(n), dim3(64), n, M, reset, robot_stop ? 1 : 0, d_est_in, d_est_out, d_gait_out, d_swing_state, d_swing_in,
-                        d_swing_vel_in, d_fe_in, d_swing_flags);
+                        d_swing_vel_in, d_fe_in, d_swing_flags, stage_args(c, 2, 1));
 }
 
 int qrgpu_swing_action_batch(qrgpu_ctx *c, int n, const qrgpu_swing_mode_desc *desc, const qrgpu_estimator_desc *geom, int robot_stop,
@@ -280,11 +264,8 @@ int qrgpu_stance_update_batch(qrgpu_ctx *c, int n, const qrgpu_stance_desc *desc
     qrgpu_stance_desc S;
     const int e = stance_update_check(c, n, desc, S, d_est_in, d_est_out, d_ground_out, d_rpy, d_gait_out, d_gait_state, d_stance_cmd, d_stance_state);
     if (e != QRGPU_OK) return e;
-    if (c->stage_reset_on)
-        return launch_stage(c, qr_stance_update_kernel_pr, per_robot(n), dim3(64), n, S, current_time, robot_stop ? 1 : 0, reset ? 1 : 0, d_est_in, d_est_out, d_ground_out,
-                            d_rpy, d_gait_out, d_gait_state, d_stance_cmd, d_stance_state, d_vmc_in, d_ratio, d_stance_out, stage_args(c, 1, 1));
     return launch_stage(c, qr_stance_update_kernel, per_robot(n), dim3(64), n, S, current_time, robot_stop ? 1 : 0, reset ? 1 : 0, d_est_in, d_est_out, d_ground_out,
-                        d_rpy, d_gait_out, d_gait_state, d_stance_cmd, d_stance_state, d_vmc_in, d_ratio, d_stance_out);
+                        d_rpy, d_gait_out, d_gait_state, d_stance_cmd, d_stance_state, d_vmc_in, d_ratio, d_stance_out, stage_args(c, 1, 1));
 }
 
 int qrgpu_stance_command_batch(qrgpu_ctx *c, int n, const qrgpu_stance_desc *desc, int robot_stop, const float *d_vmc_in, const float *d_stance_out,
@@ -333,13 +314,10 @@ int qrgpu_pose_plan_batch(qrgpu_ctx *c, int n, const qrgpu_pose_plan_desc *desc,
 {
     if (!batch_ok(c, n) || !desc || event < 0 || event > 3) return QRGPU_ERR_BAD_ARG;
     if (!d_est_in || !d_est_out || !d_ground_out || !d_rpy || !d_walk_out || !d_pose_state || !d_stance_cmd || !d_pose_flags) return QRGPU_ERR_BAD_ARG;
-    const bool masked = c->stage_reset_on && c->stage_reset.d_mask;                                     // a masked robot is reset also where nothing else happens
+    const bool masked = c->stage_reset.d_mask != nullptr;                                               // a masked robot is reset also where nothing else happens
     if (!d_event && event == 0 && !reset && !masked) return QRGPU_OK;                                   // nothing to do: no launch
-    if (c->stage_reset_on)
-        return launch_stage(c, qr_pose_plan_kernel_pr, dim3(8 * ((n + 7) / 8)), dim3(64), n, *desc, event, d_event, reset ? 1 : 0, d_est_in, d_est_out, d_ground_out, d_rpy,
-                            d_walk_out, d_pose_state, d_stance_cmd, d_pose_out, d_pose_flags, stage_args(c, 1, 1));
     return launch_stage(c, qr_pose_plan_kernel, dim3(8 * ((n + 7) / 8)), dim3(64), n, *desc, event, d_event, reset ? 1 : 0, d_est_in, d_est_out, d_ground_out, d_rpy,
-                        d_walk_out, d_pose_state, d_stance_cmd, d_pose_out, d_pose_flags);
+                        d_walk_out, d_pose_state, d_stance_cmd, d_pose_out, d_pose_flags, stage_args(c, 1, 1));
 }
 
 int qrgpu_mpc_frontend_batch(qrgpu_ctx *c, int n, int num_horizon_l, float dt_ctrl, float dt_mpc, const float *d_fe_in, float *d_fe_state,
@@ -352,11 +330,8 @@ int qrgpu_mpc_frontend_batch(qrgpu_ctx *c, int n, int num_horizon_l, float dt_ct
     const float iterations = roundf(dt_mpc / dt_ctrl);
     if (!(iterations >= 2.f && iterations <= 16777216.f)) return QRGPU_ERR_BAD_ARG;
     if (!c->mpc_ready[0]) return QRGPU_ERR_NOT_SETUP;
-    if (c->stage_reset_on)
-        return launch_stage(c, qr_frontend_kernel_pr, per_robot(n), dim3(64, c->mpc.horizon), n, c->mpc.horizon, num_horizon_l, dt_ctrl, dt_mpc, (int)iterations / 2,
-                            d_fe_in, d_fe_state, d_traj, d_gait, d_wbc_cmd, d_mpc_updated, stage_args(c, QRGPU_STAGE_RESET_CONSTRUCT, QRGPU_STAGE_RESET_LIVE));
     return launch_stage(c, qr_frontend_kernel, per_robot(n), dim3(64, c->mpc.horizon), n, c->mpc.horizon, num_horizon_l, dt_ctrl, dt_mpc, (int)iterations / 2,
-                        d_fe_in, d_fe_state, d_traj, d_gait, d_wbc_cmd, d_mpc_updated);
+                        d_fe_in, d_fe_state, d_traj, d_gait, d_wbc_cmd, d_mpc_updated, stage_args(c, QRGPU_STAGE_RESET_CONSTRUCT, QRGPU_STAGE_RESET_LIVE));
 }
 
 void qrgpu_plant_params_default(qrgpu_plant_params *p)
@@ -521,7 +496,7 @@ int qrgpu_episode_step_batch(qrgpu_ctx *c, int n, const qrgpu_episode_desc *desc
 int qrgpu_set_stage_reset(qrgpu_ctx *c, const qrgpu_stage_reset *r)
 {
     if (!c) return QRGPU_ERR_BAD_ARG;
-    if (!r) { c->stage_reset = qrgpu_stage_reset{}; c->stage_reset_on = false; return QRGPU_OK; }
+    if (!r) { c->stage_reset = qrgpu_stage_reset{}; return QRGPU_OK; }
     const char *what = nullptr;
     if (!r->d_mask && !r->d_ticks) what = "d_mask and d_ticks are both NULL";
     else if (r->d_mask && r->bits == 0u) what = "bits";
@@ -531,7 +506,6 @@ int qrgpu_set_stage_reset(qrgpu_ctx *c, const qrgpu_stage_reset *r)
     c->stage_reset = *r;
     if (!r->d_mask) { c->stage_reset.bits = 0u; c->stage_reset.level = QRGPU_STAGE_RESET_CONSTRUCT; }       // fields that are not read
     if (!r->d_ticks) c->stage_reset.tick_dt = 0.f;
-    c->stage_reset_on = true;
     return QRGPU_OK;
 }
 
@@ -573,10 +547,8 @@ int qrgpu_observe_batch(qrgpu_ctx *c, int n, const qrgpu_observe_desc *desc, int
         {"upper_l", desc->upper_l}, {"lower_l", desc->lower_l}};
     for (const auto &a : finite) if (!std::isfinite(a.v)) return observe_bad(c, a.name);
     for (int k = 0; k < 12; ++k) if (!std::isfinite(desc->hip_offset[k])) return observe_bad(c, "hip_offset");
-    // the binding as the kernel takes it, always: a null mask is "unbound"; the clock is not read
-    const StageResetArgs R = c->stage_reset_on ? StageResetArgs{c->stage_reset.d_mask, c->stage_reset.bits, 1, nullptr, 0.f} : StageResetArgs{nullptr, 0u, 1, nullptr, 0.f};
-    return launch_stage(c, qr_observe_kernel, per_robot(n), dim3(64), n, *desc, reset != 0 ? 1 : 0, step, R, d_raw, d_est_out_prev, d_obs_state, d_est_in, d_rpy,
-                        d_ground_in, d_tick);
+    return launch_stage(c, qr_observe_kernel, per_robot(n), dim3(64), n, *desc, reset != 0 ? 1 : 0, step, stage_mask_args(c), d_raw, d_est_out_prev, d_obs_state,
+                        d_est_in, d_rpy, d_ground_in, d_tick);
 }
 
 }  // extern "C"

@@ -30,12 +30,10 @@ int qrgpu_velocity_inputs_batch(qrgpu_ctx *c, int n, int terrain, int reset, con
     if (!d_gait_state) return velocity_flow_bad(c, "d_gait_state");
     if (!d_state_des) return velocity_flow_bad(c, "d_state_des");
     if (d_swing_flag && !d_cmd_mem) return velocity_flow_bad(c, "d_cmd_mem");                      // the flag is "has an entry and ..."
-    // the binding as the kernel takes it, always: a null mask is "unbound"; the clock is not read
-    const StageResetArgs R = c->stage_reset_on ? StageResetArgs{c->stage_reset.d_mask, c->stage_reset.bits, 1, nullptr, 0.f} : StageResetArgs{nullptr, 0u, 1, nullptr, 0.f};
     c->ov_chain = false;                                             // another launch of the context: the next overlapped tick is not chained
     HIPCHK(c, hipSetDevice(c->device));
-    hipLaunchKernelGGL(qr_velocity_flow_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, n, terrain, reset, R, d_est_in, d_est_out, d_ground_out, d_gait_out,
-                       d_gait_state, d_state_des, d_swing_vel_in, d_est_in_next, d_cmd_mem, d_swing_flag);
+    hipLaunchKernelGGL(qr_velocity_flow_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, n, terrain, reset, stage_mask_args(c), d_est_in, d_est_out, d_ground_out,
+                       d_gait_out, d_gait_state, d_state_des, d_swing_vel_in, d_est_in_next, d_cmd_mem, d_swing_flag);
     HIPCHK(c, hipGetLastError());
     return QRGPU_OK;
 }

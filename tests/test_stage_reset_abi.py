@@ -50,9 +50,11 @@ def test_library_exports_the_entry_point(pkg):
     assert hasattr(lib, "qrgpu_set_stage_reset")
     assert "qrgpu_set_stage_reset" in pkg.qrgpu.EXPORTS
     data = open(pkg._build.build(), "rb").read()
-    for k in (b"qr_ground_kernel_pr", b"qr_estimator_kernel_pr", b"qr_gait_kernel_pr", b"qr_walk_gait_kernel_pr", b"qr_swing_update_kernel_pr",
-              b"qr_stance_update_kernel_pr", b"qr_pose_plan_kernel_pr", b"qr_frontend_kernel_pr"):
+    # one kernel per stage, bound or not: the eight stage kernels are there, and none of them has a per-robot twin (suffix _pr) beside it
+    for k in (b"qr_ground_kernel", b"qr_estimator_kernel", b"qr_gait_kernel", b"qr_walk_gait_kernel", b"qr_swing_update_kernel",
+              b"qr_stance_update_kernel", b"qr_pose_plan_kernel", b"qr_frontend_kernel"):
         assert k in data, k
+        assert k + b"_pr" not in data, k
     # a NULL context is refused before anything is read
     f = pkg.load_library().qrgpu_set_stage_reset
     assert f(None, None) == 2 and f(None, C.byref(pkg.qrgpu.stage_reset(mask=8, level=1))) == 2

@@ -1,17 +1,20 @@
-"""Workload for the per-launch times of the eight per-robot stage kernels beside their unbound forms: ground, estimator, gait,
+"""Workload for the per-launch times of the eight stage kernels with memory, bound and unbound: ground, estimator, gait,
 walk gait, swing update (position mode), stance update (ADVANCED_TROT), pose plan and MPC front-end at 1024 robots, every tick all eight, the
-ticks alternating between a bound call (qrgpu_set_stage_reset: mask and tick arrays on the device) and an unbound one, meant to run under
+ticks alternating between an unbound call (even ticks) and a bound one (odd ticks; qrgpu_set_stage_reset: mask and tick arrays on the device),
+meant to run under
 
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -o zero   -- python tools/prof_stage_reset.py
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -o masked -- python tools/prof_stage_reset.py --all-masked
 
 Default: an all-zero mask and tick counts that follow the scalar clock, so the bound and the unbound ticks compute the same thing and the trace
-compares one kernel text compiled twice.  --all-masked: every robot is reset at every bound tick (the estimator's zeroing pass).  The inputs change
+compares one kernel with and without the two row loads of a binding.  --all-masked: every robot is reset at every bound tick (the estimator's zeroing pass).  The inputs change
 every third tick, so each input set, and each change of inputs (a ground fit fires on newly made contacts), meets both forms equally often.
 
     python tools/prof_stage_reset.py --summarise OUT/zero_kernel_trace.csv [OUT/masked_kernel_trace.csv]
 
-prints, per kernel and trace, calls, median, min and max of the launch durations as CSV (profiles/stage_reset_kernel_stats.csv)."""
+prints, per kernel and trace, calls, median, min and max of the launch durations as CSV (profiles/stage_one_text_kernel_stats.csv), the unbound
+and the bound ticks apart.  Both run the same kernel: every tick launches each kernel once, so in start order the k-th launch of a kernel belongs to
+tick k, and the odd ticks are the bound ones."""
 import csv
 import os
 import sys
@@ -96,22 +99,21 @@ def main(all_masked, n=1024, ticks=600):
 
 
 def summarise(paths):
-    """rocprofv3's kernel trace(s) -> CSV on stdout: one row per trace and stage kernel form"""
-    print('"Trace","Kernel","Calls","MedianNs","MinNs","MaxNs"')
+    """rocprofv3's kernel trace(s) -> CSV on stdout: per trace and stage kernel one row for its unbound ticks and one for its bound ticks"""
+    print('"Trace","Kernel","Ticks","Calls","MedianNs","MinNs","MaxNs"')
     for path in paths:
-        durations = {}
+        launches = {}
         with open(path, newline="") as f:
             for row in csv.DictReader(f):
-                name = row["Kernel_Name"]
-                m = [s for s in STAGES if ("qrgpu::" + s + "(") in name or ("qrgpu::" + s + "_pr(") in name]
+                m = [s for s in STAGES if ("qrgpu::" + s + "(") in row["Kernel_Name"]]
                 if m:
-                    key = m[0] + ("_pr" if (m[0] + "_pr(") in name else "")
-                    durations.setdefault(key, []).append(int(row["End_Timestamp"]) - int(row["Start_Timestamp"]))
+                    launches.setdefault(m[0], []).append((int(row["Start_Timestamp"]), int(row["End_Timestamp"]) - int(row["Start_Timestamp"])))
         tag = os.path.basename(path).replace("_kernel_trace.csv", "")
         for s in STAGES:
-            for key in (s, s + "_pr"):
-                d = np.array(durations.get(key, [0]))
-                print('"%s","%s",%d,%d,%d,%d' % (tag, key, len(durations.get(key, [])), int(np.median(d)), int(d.min()), int(d.max())))
+            in_order = [d for _, d in sorted(launches.get(s, []))]
+            for ticks, d in (("unbound", in_order[0::2]), ("bound", in_order[1::2])):
+                a = np.array(d or [0])
+                print('"%s","%s","%s",%d,%d,%d,%d' % (tag, s, ticks, len(d), int(np.median(a)), int(a.min()), int(a.max())))
 
 
 if __name__ == "__main__":

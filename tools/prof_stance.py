@@ -5,8 +5,8 @@ action for the walk and position modes -- meant to run under
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -o walk -- python tools/prof_stance.py walk
 
 once per mode (velocity, position, walk, advanced_trot), each in a run of its own.  --bound (after the mode) alternates the ticks between unbound
-calls and calls under qrgpu_set_stage_reset with an all-zero mask: one trace then holds the gait, swing update and stance update kernels and their
-per-robot forms (qr_*_kernel_pr) side by side."""
+calls and calls under qrgpu_set_stage_reset with an all-zero mask: one trace then holds the unbound and the bound launches of the gait, swing update and
+stance update kernels: each runs once a tick, so in start order its k-th launch belongs to tick k."""
 import os
 import sys
 
@@ -45,7 +45,7 @@ def main(name, n=1024, ticks=2000, bound=False):
     if bound:
         d_mask = ctx.alloc((n,), np.int32).upload(np.zeros(n, np.int32)); d_ticks = ctx.alloc((n,), np.int32)
     for k in range(ticks):
-        if bound:                                  # odd ticks: the per-robot kernels on an all-zero mask and the robots' own (equal) clocks
+        if bound:                                  # odd ticks: the kernels bound to an all-zero mask and the robots' own (equal) clocks
             d_ticks.upload(np.full(n, k, np.int32))    # (every tick, so that both kinds of tick start behind the same blocking copy)
             if k % 2:
                 ctx.set_stage_reset(mask=d_mask, ticks=d_ticks, tick_dt=0.002)

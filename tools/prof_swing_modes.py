@@ -5,7 +5,7 @@ at 1024 robots, gait generator -> swing update -> swing action, meant to run und
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -o position -- python tools/prof_swing_modes.py position
 
 --bound (after the mode) alternates the ticks between unbound calls and calls under qrgpu_set_stage_reset with an all-zero mask, so that one trace
-holds the gait and swing update kernels and their per-robot forms (qr_*_kernel_pr) side by side.
+holds the gait and swing update kernels' unbound and bound launches: each runs once a tick, so in start order its k-th launch belongs to tick k.
 
 The walk runs the shortened cycle (0.75 s stance); the position mode uses a1_sim's gaps, whose plan is made at the first leg-0 lift-off
 (the slowest update launch of the run)."""
@@ -43,7 +43,7 @@ def main(mode, n=1024, ticks=2000, bound=False):
     if bound:
         d_mask = ctx.alloc((n,), np.int32).upload(np.zeros(n, np.int32)); d_ticks = ctx.alloc((n,), np.int32)
     for k in range(ticks):
-        if bound:                                  # odd ticks: the per-robot kernels on an all-zero mask and the robots' own (equal) clocks
+        if bound:                                  # odd ticks: the kernels bound to an all-zero mask and the robots' own (equal) clocks
             d_ticks.upload(np.full(n, k, np.int32))    # (every tick, so that both kinds of tick start behind the same blocking copy)
             if k % 2:
                 ctx.set_stage_reset(mask=d_mask, ticks=d_ticks, tick_dt=0.002)
