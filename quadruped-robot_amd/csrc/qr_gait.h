@@ -1,7 +1,7 @@
-// The open-loop gait generator with the gait chosen per robot, and the stage clock that restarts where a mask says: what qr_gait_select_kernel and
-// qr_stage_clock_kernel (qr_gait_select_kernel.hip) run per lane.  float32 + - x / with contraction off, exact fmodf, every operation in the order of
-// qr_gait_kernel (qr_estimator_kernel.hip) and of tests/gait_ref.py.  Every function is __host__ __device__: the same text compiles for a CPU check
-// against tests/gait_select_ref.py (tests/stubs/gait_select_host.hip).  include/qrgpu.h states the rules.
+// The open-loop gait generator, written once, and the stage clock that restarts where a mask says: what qr_gait_kernel (one gait for the launch),
+// qr_gait_select_kernel (the gait chosen per robot) and qr_stage_clock_kernel (qr_gait_kernel.hip) run per lane.  float32 + - x / with contraction off,
+// exact fmodf, every operation in the order of tests/gait_ref.py.  Every function is __host__ __device__: the same text compiles for a CPU check against
+// tests/gait_ref.py and tests/gait_select_ref.py (tests/stubs/gait_select_host.hip).  include/qrgpu.h states the rules.
 //   qrOpenLoopGaitGenerator::Reset                  quadruped/src/gait/qr_openloop_gait_generator.cpp:77-123 (re-reads the block of `gait`)
 //   qrOpenLoopGaitGenerator::Update, Schedule       :126-207, :210-249 (legs with a non-zero duty factor)
 //   qrGaitGenerator::Reset, the members' initialisers   quadruped/include/quadruped/gait/qr_gait.h:76-87, :263-294
@@ -53,18 +53,6 @@ QR_HD void load(size_t S, const float *st, Generator &g)
         g.leg[l] = (int)st[(S_LEG + l) * S]; g.allow[l] = (int)st[(S_ALLOW + l) * S]; g.fsw[l] = (int)st[(S_FIRST_SWING + l) * S];
         g.fst[l] = (int)st[(S_FIRST_STANCE + l) * S]; g.phase[l] = st[(S_PHASE + l) * S]; g.nphase[l] = st[(S_NPHASE + l) * S];
         g.csp[l] = st[(S_CONTACT_START + l) * S]; g.srem[l] = st[(S_SWING_REMAINING + l) * S];
-    }
-}
-
-QR_HD void store(size_t S, const Generator &g, float current_time, float *st)
-{
-    st[S_RESET_TIME * S] = g.reset_time; st[S_LAST_TIME * S] = current_time; st[S_CUM_DT * S] = g.cum_dt; st[S_GAIT_CYCLE * S] = g.gait_cycle;
-#pragma unroll
-    for (int l = 0; l < 4; ++l) {
-        st[(S_CUR + l) * S] = (float)g.cur[l]; st[(S_LAST + l) * S] = (float)g.last[l]; st[(S_DESIRED + l) * S] = (float)g.desired[l];
-        st[(S_LEG + l) * S] = (float)g.leg[l]; st[(S_ALLOW + l) * S] = (float)g.allow[l]; st[(S_FIRST_SWING + l) * S] = (float)g.fsw[l];
-        st[(S_FIRST_STANCE + l) * S] = (float)g.fst[l]; st[(S_PHASE + l) * S] = g.phase[l]; st[(S_NPHASE + l) * S] = g.nphase[l];
-        st[(S_CONTACT_START + l) * S] = g.csp[l]; st[(S_SWING_REMAINING + l) * S] = g.srem[l];
     }
 }
 
@@ -144,10 +132,51 @@ QR_HD void update(const qrgpu_gait_desc &D, float current_time, int stop, const 
     }
 }
 
+// One robot's tick on the parameters of D and a loaded generator: Reset where the level says, Update, then everything the tick writes.  Row 1
+// (lastTime) receives the call's time.  st, out, fe, sw: the robot's columns (out, fe and sw may be null).  A leg's state rows are stored beside its
+// out / fe / sw rows, in one loop: a store pass over the whole generator in front of the output pass keeps every member live across both (183
+// against 139 VGPRs in qr_gait_select_kernel).
+QR_HD void tick(const qrgpu_gait_desc &D, int level, float current_time, int stop, size_t S, const float ct[4], Generator &g, float *st, float *out,
+                float *fe, float *sw)
+{
+    if (level) reset(D, level, g);
+    float swing_duration[4];
+    update(D, current_time, stop, ct, g, swing_duration);
+    st[S_RESET_TIME * S] = g.reset_time; st[S_LAST_TIME * S] = current_time; st[S_CUM_DT * S] = g.cum_dt; st[S_GAIT_CYCLE * S] = g.gait_cycle;
+#pragma unroll
+    for (int l = 0; l < 4; ++l) {
+        st[(S_CUR + l) * S] = (float)g.cur[l]; st[(S_LAST + l) * S] = (float)g.last[l]; st[(S_DESIRED + l) * S] = (float)g.desired[l];
+        st[(S_LEG + l) * S] = (float)g.leg[l]; st[(S_ALLOW + l) * S] = (float)g.allow[l]; st[(S_FIRST_SWING + l) * S] = (float)g.fsw[l];
+        st[(S_FIRST_STANCE + l) * S] = (float)g.fst[l]; st[(S_PHASE + l) * S] = g.phase[l]; st[(S_NPHASE + l) * S] = g.nphase[l];
+        st[(S_CONTACT_START + l) * S] = g.csp[l]; st[(S_SWING_REMAINING + l) * S] = g.srem[l];
+        if (out) {
+            out[(size_t)l * S] = g.phase[l]; out[(size_t)(4 + l) * S] = g.nphase[l]; out[(size_t)(8 + l) * S] = (float)g.desired[l];
+            out[(size_t)(12 + l) * S] = (float)g.leg[l]; out[(size_t)(16 + l) * S] = (float)g.cur[l]; out[(size_t)(20 + l) * S] = g.srem[l];
+        }
+        if (fe) {            // rows 42-61 of the MPC front-end's input
+            fe[(size_t)(42 + l) * S] = g.phase[l]; fe[(size_t)(46 + l) * S] = D.duty_factor[l]; fe[(size_t)(50 + l) * S] = g.nphase[l];
+            fe[(size_t)(54 + l) * S] = (float)g.desired[l]; fe[(size_t)(58 + l) * S] = (float)g.leg[l];
+        }
+        if (sw) sw[(size_t)(8 + l) * S] = swing_duration[l];      // swingDuration of the gait in force
+    }
+}
+
+// One robot's tick of qrgpu_gait_update_batch: one gait for the whole call.  level: the robot's reset level at this call; contact, st, out, fe: the
+// robot's columns (out and fe may be null).  Rows 48-51 of the state are neither read nor written, and swing_in is the caller's.  The state column and
+// the contacts are loaded before anything depends on the level; a reset then overrides what its level does not keep.
+QR_HD void fixed_update(const qrgpu_gait_desc &D, int level, float current_time, int stop, size_t S, const float *contact, float *st, float *out, float *fe)
+{
+    Generator g;
+    load(S, st, g);
+    float ct[4];
+#pragma unroll
+    for (int l = 0; l < 4; ++l) ct[l] = contact[(size_t)l * S];
+    tick(D, level, current_time, stop, S, ct, g, st, out, fe, nullptr);
+}
+
 // One robot's tick of qrgpu_gait_select_update_batch.  table [n_gaits] in memory the caller can read with an index of its own; sel: the robot's word of
 // d_gait_sel; level: the robot's reset level at this call (0, QRGPU_GAIT_RESET_CONSTRUCT, QRGPU_GAIT_RESET_LIVE); st, out, fe, sw: the robot's columns
-// (out, fe, sw and flag may be null).  The state column, the selection and the contacts are loaded before anything depends on the level; a reset then
-// overrides what its level does not keep.
+// (out, fe, sw and flag may be null).  The state column, the selection and the contacts are loaded before anything depends on the level.
 QR_HD void select_update(const qrgpu_gait_desc *table, int n_gaits, float sel, int level, float current_time, int stop, size_t S, const float *contact,
                          float *st, float *out, float *fe, float *sw, int *flag)
 {
@@ -160,23 +189,8 @@ QR_HD void select_update(const qrgpu_gait_desc *table, int n_gaits, float sel, i
     int idx = kept < 0 ? 0 : kept, bad = 0;
     if (level) { idx = chosen < 0 ? 0 : chosen; bad = chosen < 0 ? QRGPU_GAIT_BAD_SEL : 0; }      // the selection counts at a reset and nowhere else
     const qrgpu_gait_desc D = table[idx];
-    if (level) reset(D, level, g);
-    float swing_duration[4];
-    update(D, current_time, stop, ct, g, swing_duration);
-    store(S, g, current_time, st);
+    tick(D, level, current_time, stop, S, ct, g, st, out, fe, sw);
     st[S_INDEX * S] = (float)idx;
-#pragma unroll
-    for (int l = 0; l < 4; ++l) {
-        if (out) {
-            out[(size_t)l * S] = g.phase[l]; out[(size_t)(4 + l) * S] = g.nphase[l]; out[(size_t)(8 + l) * S] = (float)g.desired[l];
-            out[(size_t)(12 + l) * S] = (float)g.leg[l]; out[(size_t)(16 + l) * S] = (float)g.cur[l]; out[(size_t)(20 + l) * S] = g.srem[l];
-        }
-        if (fe) {            // rows 42-61 of the MPC front-end's input
-            fe[(size_t)(42 + l) * S] = g.phase[l]; fe[(size_t)(46 + l) * S] = D.duty_factor[l]; fe[(size_t)(50 + l) * S] = g.nphase[l];
-            fe[(size_t)(54 + l) * S] = (float)g.desired[l]; fe[(size_t)(58 + l) * S] = (float)g.leg[l];
-        }
-        if (sw) sw[(size_t)(8 + l) * S] = swing_duration[l];      // swingDuration of the gait in force
-    }
     if (flag) *flag = bad;
 }
 

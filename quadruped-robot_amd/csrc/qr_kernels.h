@@ -72,8 +72,6 @@ __global__ void qr_vmc_kernel(VmcLaunch P, const int *type_id, const float *g_in
 __global__ void qr_estimator_kernel(int n, qrgpu_estimator_desc D, const float *g_in, const unsigned *g_tick, double *st, float *g_out, StageResetArgs SR);
 __global__ void qr_pack_state_kernel(int n, float c0, float c1, float c2, const float *g_in, const float *g_est, const float *g_rpy, float *g_mpc, float *g_fb);
 __global__ void qr_swing_kernel(int n, qrgpu_estimator_desc D, const float *g_in, float *g_cmd, float *g_tgt_world, float *g_qdes);
-__global__ void qr_gait_kernel(int n, qrgpu_gait_desc D, float currentTime, int stop, int fresh, const float *g_contact, float *st, float *g_out, float *g_fe,
-                               StageResetArgs SR);
 __global__ void qr_foothold_kernel(int n, qrgpu_foothold_desc D, const float *g_in, const float *g_gait_state, const float *g_gait_out, float *g_swing);
 __global__ void qr_ground_kernel(int n, int fresh, const float *g_in, double *g_st, float *g_out, float *g_est_in, StageResetArgs SR);
 __global__ void qr_walk_gait_kernel(int n, WalkDesc D, float currentTime, int stop, int fresh, const float *g_contact, float *st, float *g_out, float *g_ratio,
@@ -143,8 +141,10 @@ __global__ void qr_fsm_zero_kernel(int n, const int *g_plan, float *g_des, float
 __global__ void qr_fsm_command_kernel(int n, qrgpu_fsm_desc D, const int *g_plan, const float *g_est_in, const float *g_loco, float *g_st, float *g_cmd,
                                       float *g_out);
 
-// qr_gait_select_kernel.hip: one lane per robot; the open-loop gait generator on the table entry each robot latched at its last reset (the table in
-// device memory, indexed per lane), and the clock that counts from where a mask last said
+// qr_gait_kernel.hip: one lane per robot; the open-loop gait generator on the call's one gait and on the table entry each robot latched at its last
+// reset (the table in device memory, indexed per lane), and the clock that counts from where a mask last said
+__global__ void qr_gait_kernel(int n, qrgpu_gait_desc D, float currentTime, int stop, int fresh, const float *g_contact, float *st, float *g_out, float *g_fe,
+                               StageResetArgs SR);
 __global__ void qr_gait_select_kernel(int n, const qrgpu_gait_desc *g_table, int n_gaits, const float *g_sel, float currentTime, int stop, int fresh,
                                       const float *g_contact, float *st, float *g_out, float *g_fe, float *g_sw, int *g_flags, StageResetArgs SR);
 __global__ void qr_stage_clock_kernel(int n, const int *g_mask, unsigned bits, const int *g_ticks, int *g_origin, int *g_local);

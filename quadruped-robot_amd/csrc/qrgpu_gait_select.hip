@@ -1,6 +1,6 @@
 // ============================================================================
 // libqrgpu.so host side: the open-loop gait generator with the gait chosen per robot and the stage clock that restarts where a mask says
-// (qr_gait_select_kernel.hip), and the default gait table.  Every entry point is "check the arguments, one launch on the context's stream".
+// (qr_gait_kernel.hip), and the default gait table.  Every entry point is "check the arguments, one launch on the context's stream".
 // ============================================================================
 #include <hip/hip_runtime.h>
 #include <cstring>

@@ -1,8 +1,10 @@
 """CPU: csrc/qr_gait.h compiled for the host (tests/stubs/gait_select_host.hip) and run over the mixed schedules of tests/gait_select_ref.py -- 65 robots,
 700 ticks, three selections and two resets of a drawn level per robot, late and early touch-downs, robot_stop from tick 300 in one schedule of three, the
 clock restarted at each reset -- against the numpy restatement, bit for bit: state rows 0-48, the 24 output rows, fe_in rows 42-61, swing_in rows 8-11,
-the flags; every other row keeps its poison.  The clock's origin and local count are held against numpy.  The same stand-alone program is built once
-more with the address and undefined-behaviour sanitizers and run on the same input files: it must run clean and write the same bytes."""
+the flags; every other row keeps its poison.  The clock's origin and local count are held against numpy.  The fixed-gait path, what qr_gait_kernel
+runs per lane, goes through the same program (n_gaits = 0 in its header) over the six configurations of tests/gait_ref.py against gait_ref.run, bit
+for bit, and once more without the optional outputs (n_gaits = -1).  The same stand-alone program is built once more with the address and
+undefined-behaviour sanitizers and run on the same input files: it must run clean and write the same bytes."""
 import ctypes
 import os
 import struct
@@ -11,6 +13,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import gait_ref as GR
 import gait_select_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -112,12 +115,88 @@ def test_clock_against_numpy(host, k):
     assert np.array_equal(got["local"], S["local"])
 
 
-def test_sanitized_build_runs_clean(host):
-    """The same stand-alone program under the address and undefined-behaviour sanitizers, on the same files: no report, the same bytes."""
+@pytest.fixture(scope="module")
+def san_exe(host):
     exe = EXE + "_san"
     _compile(exe, ("-g", "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all", "-Xarch_host", "-fno-omit-frame-pointer"))
+    return exe
+
+
+def _runs_clean(exe, fin, fout, raw):
+    p = subprocess.run([exe, fin, fout], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    assert p.returncode == 0 and not p.stderr, p.stderr.decode()[-2000:]
+    assert open(fout, "rb").read() == raw
+
+
+def test_sanitized_build_runs_clean(host, san_exe):
+    """The same stand-alone program under the address and undefined-behaviour sanitizers, on the same files: no report, the same bytes."""
     for k, run in enumerate(host["runs"]):
-        fout = str(host["tmp"] / ("gs%d.san.out" % k))
-        p = subprocess.run([exe, run["fin"], fout], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
-        assert p.returncode == 0 and not p.stderr, p.stderr.decode()[-2000:]
-        assert open(fout, "rb").read() == run["raw"]
+        _runs_clean(san_exe, run["fin"], str(host["tmp"] / ("gs%d.san.out" % k)), run["raw"])
+
+
+# ----------------------------------------------------------------------------- the fixed-gait path (gait::fixed_update, what qr_gait_kernel runs)
+@pytest.fixture(scope="module")
+def fixed(pkg, host):
+    """name -> the configuration of tests/gait_ref.py, its levels (as constructed at tick 0, LIVE where the configuration resets) and the program's
+    records with the optional outputs (n_gaits word 0) and without (-1); made once per name."""
+    made = {}
+
+    def get(name):
+        if name not in made:
+            c = GR.configuration(pkg, name)
+            level = np.where(c["reset"] != 0, pkg.qrgpu.GAIT_RESET_LIVE, 0).astype(np.int32)
+            level[0] = pkg.qrgpu.GAIT_RESET_CONSTRUCT
+            d = _descs(pkg, [c["cfg"]])
+            run = dict(c=c, level=level, live=pkg.qrgpu.GAIT_RESET_LIVE)
+            for ng in (0, -1):
+                b = struct.pack("<4if", GR.N_ROBOTS, GR.TICKS, ng, ctypes.sizeof(d[0]), GR.DT) + bytes(d) + level.tobytes()
+                b += np.ascontiguousarray(c["time"], "<f4").tobytes() + np.ascontiguousarray(c["stop"], "<i4").tobytes()
+                b += np.ascontiguousarray(c["contact"].transpose(0, 2, 1), "<f4").tobytes()
+                fin = str(host["tmp"] / ("fixed_%s_%d.in" % (name, -ng)))
+                open(fin, "wb").write(b)
+                raw, got = _run(EXE, fin, fin[:-2] + "out", GR.TICKS, GR.N_ROBOTS)
+                run[ng] = dict(fin=fin, raw=raw, got=got)
+            made[name] = run
+        return made[name]
+    return get
+
+
+@pytest.mark.parametrize("name", GR.CONFIGS)
+def test_fixed_gait_against_the_reference_state_machine(fixed, name):
+    """gait::fixed_update on the host against gait_ref.run on every tick of every robot, bit for bit: rows 0-47 of the state, gait_out, rows 42-45 and
+    50-61 of fe_in, the duty factors in rows 46-49; rows 48-51 of the state, the rest of fe_in, swing_in, the flags and the clock keep their start
+    values; without the optional outputs the state evolves the same and the outputs keep their poison."""
+    run = fixed(name)
+    c, level, got, bare = run["c"], run["level"], run[0]["got"], run[-1]["got"]
+    n = GR.N_ROBOTS
+    ref = [GR.run(c["cfg"], c["time"], c["contact"][:, r], c["stop"], c["reset"], want_state=True) for r in range(n)]
+    want = np.stack([w for w, _ in ref], axis=2)                  # [T, 24, n]
+    wst = np.stack([s_ for _, s_ in ref], axis=2)                 # [T, 48, n]
+
+    def bad(a, b):
+        a, b = np.ascontiguousarray(a, np.float32).view(np.uint32), np.ascontiguousarray(b, np.float32).view(np.uint32)
+        return tuple(int(v[0]) for v in np.nonzero(a != b)) if (a != b).any() else None
+
+    fe = got["fe"]
+    assert bad(got["state"][:, :48], wst) is None, (name, "gait_state [tick, row, robot]", bad(got["state"][:, :48], wst))
+    assert bad(got["out"], want) is None, (name, "gait_out", bad(got["out"], want))
+    assert bad(fe[:, 42:46], want[:, 0:4]) is None and bad(fe[:, 50:62], want[:, 4:16]) is None, (name, "fe_in 42-45, 50-61")
+    assert bad(fe[:, 46:50], np.broadcast_to(np.asarray(c["cfg"][4:8], np.float32)[None, :, None], fe[:, 46:50].shape)) is None, (name, "fe_in 46-49")
+    assert bad(bare["state"][:, :48], wst) is None, (name, "gait_state without the optional outputs", bad(bare["state"][:, :48], wst))
+    assert np.all(bare["out"] == POISON) and np.all(bare["fe"] == POISON)
+    assert np.all(fe[:, :42] == POISON) and np.all(fe[:, 62:] == POISON)
+    for g in (got, bare):
+        assert np.all(g["state"][:, 48:] == POISON) and np.all(g["sw"] == POISON)
+        assert np.all(g["flags"] == 0x7fffffff) and np.all(g["origin"] == 0x7fffffff) and np.all(g["local"] == 0x7fffffff)
+    # not vacuous, by the reference alone: an early contact, the hold wherever the gait has one, both LIVE resets, robot_stop, a clock restart
+    assert (want[:, 12:16] == 2).any() and bool((wst[:, 20:24] == 0).any()) == (name != "plain_trot")
+    assert int((level == run["live"]).sum()) == (2 if name == "reset" else 0) and level[0] not in (0, run["live"]) and bool(c["stop"].any()) == (name == "robot_stop")
+    assert np.all(wst[-1, 3] >= 1)
+
+
+def test_fixed_gait_sanitized_build_runs_clean(fixed, host, san_exe):
+    """The fixed-gait runs under the address and undefined-behaviour sanitizers, with and without the optional outputs: no report, the same bytes."""
+    for name in GR.CONFIGS:
+        for ng in (0, -1):
+            run = fixed(name)[ng]
+            _runs_clean(san_exe, run["fin"], run["fin"][:-2] + "san.out", run["raw"])

@@ -69,6 +69,7 @@ def test_gait_against_the_reference_state_machine(gpu_ctx, pkg, name):
     assert np.array_equal(out, want), (name, "gait_out [tick, row, robot]", first_bad(out, want))
     assert np.array_equal(st[:, :48], wst), (name, "gait_state", first_bad(st[:, :48], wst))
     assert np.array_equal(bare[:, :48], wst), (name, "gait_state without the optional outputs", first_bad(bare[:, :48], wst))
+    assert np.isnan(st[-1, 48:]).all() and np.isnan(bare[-1, 48:]).all(), (name, "rows 48-51 of gait_state are the per-robot gait's: not written here")
     assert np.array_equal(fe[:, 42:46], want[:, 0:4]) and np.array_equal(fe[:, 50:54], want[:, 4:8]) and np.array_equal(fe[:, 54:58], want[:, 8:12])
     assert np.array_equal(fe[:, 58:62], want[:, 12:16]) and np.all(fe[:, 46:50] == cfg[4:8][None, :, None])
     assert np.all(fe[:, :42] == -7.0) and np.all(fe[:, 62:] == -7.0)
