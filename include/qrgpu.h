@@ -321,7 +321,9 @@ int qrgpu_tick_batch(qrgpu_ctx *ctx, int n, const int *d_type_id, const float *d
  *                is no status bit for it.
  * Always the serial form on the context's stream, whatever qrgpu_set_tick_pipeline and qrgpu_set_tick_overlap say; no wait, poll or gate of its
  * own, and nothing is read back to the host: which robots are due is known on the device alone (qrgpu_set_stage_reset gives every robot its own
- * clock).  qrgpu_tick_batch remains the tick of the pipelined and overlapped forms. */
+ * clock).  qrgpu_tick_batch remains the tick of the pipelined and overlapped forms.
+ *   idle robot:  under qrgpu_set_mode_route (below, "the mode per robot") a robot that is not on the MPC chain is neither: nothing of it is read or
+ *                written by any launch of the call.  With nothing bound there is no such robot. */
 int qrgpu_tick_cadence_batch(qrgpu_ctx *ctx, int n, const int *d_type_id, const int *d_mpc_updated,
                              const float *d_mpc_state, const float *d_traj, const float *d_gait, const float *d_fb_state,
                              const float *d_wbc_cmd, float *d_prev_ori, float *d_force, float *d_hold,
@@ -1236,8 +1238,9 @@ int  qrgpu_velocity_inputs_batch(qrgpu_ctx *ctx, int n, int terrain, int reset, 
  *   - REPEAT: where the reference sends a command kept from the tick before -- the tick that ends SwitchMode / StandLoop (transitionData.legCommand is
  *     not written, :276-283, :318-325), StandUp -> LOCOMOTION and LOCOMOTION -> STAND_UP (legCommand = data.legCmd) -- it is the column of the previous
  *     tick.  An empty legCommand (the transitions to and from PASSIVE, transitionData.Zero()) is written as zeros.
- *   - Gait and mode per robot are REPORTED in d_fsm_out.  qrgpu_gait_select_update_batch (below) acts on the gait; the MODE stays one per batch: the MPC
- *     chain, the force-balance chain and the walk chain (with qrWalkGaitGenerator for the robots in JOY_WALK) are not chosen per robot.
+ *   - Gait and mode per robot are REPORTED in d_fsm_out.  qrgpu_gait_select_update_batch (below) acts on the gait, and qrgpu_mode_route_batch with
+ *     qrgpu_set_mode_route and qrgpu_mode_command_batch (below) on the MODE, between the MPC chain and the force-balance chain.  The walk chain (with
+ *     qrWalkGaitGenerator for the robots in JOY_WALK) and the position chain are not chosen per robot: such a robot falls back and is flagged.
  * QRGPU_ERR_BAD_ARG (nothing launched, outputs untouched; qrgpu_last_error names the argument): a NULL required array or desc; n < 1, n > max_batch;
  *   a reset other than 0 or 1; stand_up_time, stand_up_total, sit_down_time, time_step, a transition duration or tau_clip not finite or not > 0;
  *   transition_ticks < 1; initial_ctrl_state outside 0..7; n_script < 0 or > QRGPU_FSM_SCRIPT_MAX, n_script > 0 without d_script, a script without
@@ -1345,6 +1348,89 @@ int  qrgpu_gait_select_update_batch(qrgpu_ctx *ctx, int n, const qrgpu_gait_desc
                                     int *d_gait_flags /* [n], may be NULL */);
 int  qrgpu_stage_clock_batch(qrgpu_ctx *ctx, int n, const int *d_mask, unsigned bits, const int *d_ticks, int *d_origin /* [n], memory */,
                              int *d_local /* [n] */);
+
+/* ---- the mode per robot: each robot's solve runs in the chain its state machine chose ----------------------------------------------------------------
+ * qrFSMStateLocomotion::OnEnter sets the LocomotionMode with the gait (QS/fsm/qr_fsm_state_locomotion.cpp:78-158): JOY_TROT is VELOCITY_LOCOMOTION --
+ * TorqueStanceLegController, the velocity case of the swing controller, the force-balance QP, no MPC and no WBC -- and JOY_ADVANCED_TROT is the MPC on
+ * its cadence, the WBC and the hip compensation.  A robot that sits, stands up or holds runs no locomotion controller at all (:162-171).  Three things
+ * are per robot here: which chain a robot is on (the route), the SOLVES of that chain (the binding), and whose motor command it gets (the merge).  The
+ * cheap stage kernels -- one lane per robot, a few microseconds a launch -- still run on every robot in both chains; every one with memory takes the
+ * stage-reset binding, so a robot entering a mode gets its Reset() calls through QRGPU_FSM_ENTERED in both chains' stages.  The caller keeps one set of
+ * arrays per chain where the chains write different things (d_swing_state, d_swing_flags, d_cmd_mem, d_force, d_tau, d_status, d_motor_cmd); the
+ * command, gait, ground, estimator and observe arrays are shared.  The tick of tools/closed_loop.py --fsm-mode:
+ *     episode step, qrgpu_fsm_update_batch, qrgpu_stage_clock_batch, qrgpu_set_stage_reset, qrgpu_mode_route_batch, qrgpu_set_mode_route, plant, observe
+ *     ... qrgpu_command_update_batch, qrgpu_fsm_zero_command_batch, qrgpu_gait_select_update_batch, the MPC chain up to qrgpu_mpc_command_batch, the
+ *     force-balance chain up to qrgpu_stance_tick_batch, qrgpu_mode_command_batch, qrgpu_fsm_command_batch.
+ *
+ * qrgpu_mode_route_batch: one launch on the context's stream, one lane per robot, integer compares.
+ *   desc->chain_of_mode[m] is the chain of LocomotionMode m (QRGPU_MODE_VELOCITY, _POSITION, _WALK, _ADVANCED_TROT), desc->fallback_chain the chain of a
+ *     robot whose mode has none.  qrgpu_mode_route_desc_default: {FORCE_BALANCE, NONE, NONE, MPC}, fallback MPC.
+ *   d_mode_sel [n] float32, like d_gait_sel: with the state machine row 45 of d_fsm_state (d_fsm_state + 45 * n).  It is read at EVERY call: the machine
+ *     latches it at OnEnter, so there is nothing left to latch here.
+ *   d_plan [n] (may be NULL): the state machine's plan of this tick.
+ *   d_chain [n], per robot, in this order:
+ *     d_plan is given and has neither QRGPU_FSM_PLAN_RUN nor QRGPU_FSM_PLAN_PHASE1        QRGPU_CHAIN_NONE, flags 0
+ *     mode -1 ("none yet")                                                                 QRGPU_CHAIN_NONE, flags 0
+ *     mode NaN, not an integer, or outside -1..3                                           fallback_chain, QRGPU_ROUTE_BAD_MODE
+ *     chain_of_mode[mode] == QRGPU_CHAIN_NONE                                              fallback_chain, QRGPU_ROUTE_NO_CHAIN
+ *     otherwise                                                                            chain_of_mode[mode], flags 0
+ *     With the defaults POSITION and WALK take the fourth line: those chains are not closed on the device, so such a robot runs on the MPC chain and is
+ *     flagged -- the rule of the gait table, where the walk parameters run in the open-loop generator: run something and say so.
+ *     Mode -1 is what the machine reports until an OnEnter under JOY_TROT, JOY_ADVANCED_TROT or JOY_WALK has set one; the reference's robot then
+ *     still runs the mode its controller was CONSTRUCTED with, which the machine does not know.  So a robot whose first OnEnter comes under JOY_STAND
+ *     (the "MPC standing" phase of tools/closed_loop.py --fsm) is on no chain and gets zeros until its first gait button: a caller who wants such
+ *     robots held up hands this call a d_mode_sel of its own with the constructed mode in place of -1.  Open.
+ *   d_route_flags [n] (may be NULL) is written at every call, 0 or one bit, never OR-ed.
+ *   d_chain_count [3] (may be NULL): d_chain_count[c] = the number of robots on chain c.  The call zeroes it on the stream; the kernel adds one integer
+ *     per chain and wavefront (ballot, popcount, atomicAdd): the sums do not depend on the order.
+ *   QRGPU_ERR_BAD_ARG (nothing launched, outputs untouched; qrgpu_last_error names the argument): a NULL desc, d_mode_sel or d_chain; n < 1, n >
+ *     max_batch; a table entry or the fallback outside 0..2.
+ *
+ * qrgpu_set_mode_route: binds d_chain [n] (NULL: off).  The pointer is copied into the context and the array is read when the kernels run, exactly like
+ *   qrgpu_set_stage_reset's mask.  While it is set:
+ *   qrgpu_tick_cadence_batch: a robot with d_chain[r] != QRGPU_CHAIN_MPC is idle: the MPC launch, the cadence kernel and the WBC launch read and write
+ *     nothing of it, and its columns of d_force, d_hold, d_tau, d_qdes, d_status and d_prev_ori stay as they were.  A robot on the MPC chain is handled
+ *     exactly as without the binding.  (One launch more in front: due' = d_mpc_updated && on the chain for the MPC launch, skip' = d_mpc_updated || not
+ *     on the chain for the WBC launch, in two arrays of the context.  A batch with nobody on the MPC chain still makes every launch; each ends at once.)
+ *   qrgpu_stance_tick_batch, qrgpu_vmc_force_batch, qrgpu_vmc_force_world_batch: the force-balance QP's workgroup of a robot with d_chain[r] !=
+ *     QRGPU_CHAIN_FORCE_BALANCE returns before its first load: the robot's d_force, d_tau and d_status columns stay as they were.  The update and
+ *     command kernels of the stance tick still run for every robot, so an idle robot's d_motor_cmd column IN THE FORCE-BALANCE CHAIN'S ARRAY is made
+ *     from a stale d_tau; nothing selects it.
+ *   EVERY OTHER ENTRY POINT IGNORES THE BINDING: qrgpu_tick_batch in its serial, pipelined and overlapped forms (they rest on every robot's solve raising
+ *     a flag), qrgpu_mpc_solve_batch, qrgpu_wbc_run_batch, the single-robot calls (qrgpu_mpc_solve1, qrgpu_wbc_run1, qrgpu_vmc_force1,
+ *     qrgpu_vmc_force_world1), the debug and inspection calls (qrgpu_mpc_assemble_batch, qrgpu_fb_debug_batch, qrgpu_wbc_inspect_batch), and every stage kernel (gait, swing, foothold, front-end, stance update and command, estimator, ground, observe, command, data
+ *     flow, state machine, plant, episode).
+ *   What a robot that changes chains carries over: nothing on the force-balance side (the QP has no memory; the stages are reset by
+ *     QRGPU_FSM_ENTERED).  On the MPC side the front-end's reset (MPCStanceLegController::Reset, qr_mpc_stance_leg_controller.cpp:78-92:
+ *     iterationCounter = 0) makes the tick of OnEnter and the 49 that follow due ones (UpdateMPC re-plans on each of the first 50 ticks), so d_hold is
+ *     rewritten before it is read and the WBC, which alone reads d_prev_ori, first runs again 50 ticks later.  It then finds what the robot's last WBC
+ *     pass left there, however long ago: the reference's wbcController is made once with the locomotion state (qr_fsm_state_locomotion.cpp:61) and no
+ *     OnEnter resets it.  The warm-start words of the robot's last solve stay too (speed only).
+ *
+ * qrgpu_mode_command_batch: one launch, one lane per robot.  Robot r's d_motor_cmd [QRGPU_MOTOR_CMD_ROWS][n] column and d_status word (may be NULL) are
+ *   those of its chain: d_cmd_mpc and d_status_mpc (may be NULL: 0) where d_chain[r] == QRGPU_CHAIN_MPC, d_cmd_fb and d_status_fb (may be NULL: 0) where
+ *   it is QRGPU_CHAIN_FORCE_BALANCE; QRGPU_CHAIN_NONE, or any value outside 1..2, gives zeros and status 0.  The copy is bit for bit and a select, not a
+ *   blend: a NaN in the column that is not selected never reaches the output.  d_motor_cmd may be either input, d_status either status input (a lane
+ *   loads both columns before its first store, as in qrgpu_fsm_command_batch), which follows and reads d_motor_cmd as its d_motor_cmd_loco.
+ *   QRGPU_ERR_BAD_ARG (nothing launched; qrgpu_last_error names the argument): a NULL d_chain, d_cmd_mpc, d_cmd_fb or d_motor_cmd; n < 1, n > max_batch. */
+#define QRGPU_CHAIN_NONE           0
+#define QRGPU_CHAIN_MPC            1
+#define QRGPU_CHAIN_FORCE_BALANCE  2
+#define QRGPU_ROUTE_BAD_MODE  0x1
+#define QRGPU_ROUTE_NO_CHAIN  0x2
+struct qrgpu_mode_route_desc {
+    int chain_of_mode[4];             /* QRGPU_CHAIN_* per LocomotionMode (QRGPU_MODE_*) */
+    int fallback_chain;               /* the chain of a robot whose mode has none, or is not a mode */
+};
+typedef struct qrgpu_mode_route_desc qrgpu_mode_route_desc;
+void qrgpu_mode_route_desc_default(qrgpu_mode_route_desc *d);
+int  qrgpu_mode_route_batch(qrgpu_ctx *ctx, int n, const qrgpu_mode_route_desc *desc, const float *d_mode_sel /* [n] */,
+                            const int *d_plan /* [n], may be NULL */, int *d_chain /* [n] */, int *d_route_flags /* [n], may be NULL */,
+                            int *d_chain_count /* [3], may be NULL */);
+int  qrgpu_set_mode_route(qrgpu_ctx *ctx, const int *d_chain /* NULL: off */);
+int  qrgpu_mode_command_batch(qrgpu_ctx *ctx, int n, const int *d_chain, const float *d_cmd_mpc,
+                              const float *d_cmd_fb /* [QRGPU_MOTOR_CMD_ROWS][n] each */, const int *d_status_mpc,
+                              const int *d_status_fb /* may be NULL */, float *d_motor_cmd, int *d_status /* may be NULL */);
 
 /* ---- multi-GPU: all-gather of the per-robot torques over RCCL / xGMI ----------------------------------------
  * One process per GPU, one context per process; rank r of N owns a contiguous shard of the robot population and there is no exchange

@@ -14,5 +14,6 @@ from . import replay                    # noqa: F401
 from . import terrain                   # noqa: F401
 from .qrgpu import (Context, QrgpuError, MissingExtension, lib_path, load_library,   # noqa: F401
                     MPCInterface, WbcLocomotionController, model_desc_struct, status_flags, status_iterations, swing_mode_desc, stance_desc,
-                    pose_plan_desc, plant_params, terrain_desc, plant_body_desc, episode_desc, stage_reset, observe_desc, command_desc, mpc_command_desc, fsm_desc, gait_table_default)
+                    pose_plan_desc, plant_params, terrain_desc, plant_body_desc, episode_desc, stage_reset, observe_desc, command_desc, mpc_command_desc, fsm_desc, gait_table_default,
+                    mode_route_desc)
 from .workload import make_batch, make_batch_sequence, mpc_cfg, model_desc, to_soa, ROBOTS    # noqa: F401

@@ -5,7 +5,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO = os.path.join(HERE, "libqrgpu.so")
-SOURCES = ["qr_mpc_kernel.hip", "qr_mpc_kernel_fl.hip", "qr_wbc_kernel.hip", "qr_wbc_kernel_dbg.hip", "qr_frontend_kernel.hip", "qr_vmc_kernel.hip", "qr_estimator_kernel.hip", "qr_swing_modes_kernel.hip", "qr_stance_kernel.hip", "qr_pose_plan_kernel.hip", "qr_plant_kernel.hip", "qr_plant_body_kernel.hip", "qr_episode_kernel.hip", "qr_observe_kernel.hip", "qr_dataflow_kernel.hip", "qr_cadence_kernel.hip", "qr_fsm_kernel.hip", "qr_gait_kernel.hip", "qr_velocity_flow_kernel.hip", "qrgpu_api.hip", "qrgpu_stages.hip", "qrgpu_dataflow.hip", "qrgpu_fsm.hip", "qrgpu_gait_select.hip", "qrgpu_velocity_flow.hip", "qrgpu_debug.hip", "qrgpu_mpc.hip", "qrgpu_tick.hip", "qrgpu_comm.hip"]
+SOURCES = ["qr_mpc_kernel.hip", "qr_mpc_kernel_fl.hip", "qr_wbc_kernel.hip", "qr_wbc_kernel_dbg.hip", "qr_frontend_kernel.hip", "qr_vmc_kernel.hip", "qr_estimator_kernel.hip", "qr_swing_modes_kernel.hip", "qr_stance_kernel.hip", "qr_pose_plan_kernel.hip", "qr_plant_kernel.hip", "qr_plant_body_kernel.hip", "qr_episode_kernel.hip", "qr_observe_kernel.hip", "qr_dataflow_kernel.hip", "qr_cadence_kernel.hip", "qr_fsm_kernel.hip", "qr_gait_kernel.hip", "qr_velocity_flow_kernel.hip", "qr_mode_route_kernel.hip", "qrgpu_api.hip", "qrgpu_stages.hip", "qrgpu_dataflow.hip", "qrgpu_fsm.hip", "qrgpu_gait_select.hip", "qrgpu_velocity_flow.hip", "qrgpu_mode_route.hip", "qrgpu_debug.hip", "qrgpu_mpc.hip", "qrgpu_tick.hip", "qrgpu_comm.hip"]
 # The fp32 MPC assembly must execute exactly the written fmaf chain (bit-identical to the CPU oracle, see
 # DESIGN.md "bit-exact assembly"): those functions carry `#pragma clang fp contract(off)`; everything else
 # (fp64 sweep / active set / WBC) is free to fuse multiply-adds.  NB plain -ffp-contract=fast would IGNORE those pragmas.
@@ -49,7 +49,7 @@ def build(force=False, verbose=False):
 
 
 # what each translation unit includes beyond itself: an object is rebuilt only when one of these (or the flags) is newer than it
-KERNEL_DEPS = ["qr_device_types.h", "qr_wave_helpers.h", "qr_kernels.h", "qr_rigid_body.h", "qr_wbc_rigid_body.h", "qr_plant_math.h", "qr_plant_quad.h", "qr_plant_body.h", "qr_terrain.h", "qr_episode.h", "qr_observe.h", "qr_dataflow.h", "qr_cadence.h", "qr_fsm.h", "qr_gait.h", "qr_velocity_flow.h", os.path.join("..", "..", "include", "qrgpu.h")]
+KERNEL_DEPS = ["qr_device_types.h", "qr_wave_helpers.h", "qr_kernels.h", "qr_rigid_body.h", "qr_wbc_rigid_body.h", "qr_plant_math.h", "qr_plant_quad.h", "qr_plant_body.h", "qr_terrain.h", "qr_episode.h", "qr_observe.h", "qr_dataflow.h", "qr_cadence.h", "qr_fsm.h", "qr_gait.h", "qr_velocity_flow.h", "qr_mode_route.h", os.path.join("..", "..", "include", "qrgpu.h")]
 HOST_DEPS = KERNEL_DEPS + ["qrgpu_ctx.h", "qr_wbc_model.h"]
 EXTRA_DEPS = {"qr_mpc_kernel_fl.hip": ["qr_mpc_kernel.hip"], "qr_wbc_kernel_dbg.hip": ["qr_wbc_kernel.hip"]}
 

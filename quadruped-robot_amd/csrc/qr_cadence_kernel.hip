@@ -18,7 +18,7 @@ namespace qrgpu {
 __global__ void __launch_bounds__(64) qr_cadence_kernel(int n, CadenceLegs L, const int *__restrict__ g_type, const int *__restrict__ g_due,
                                                         const float *__restrict__ g_mpc_state, const float *__restrict__ g_fb_state,
                                                         const float *__restrict__ g_force, float *__restrict__ g_hold, float *__restrict__ g_tau,
-                                                        int *__restrict__ g_status)
+                                                        int *__restrict__ g_status, const int *__restrict__ g_skip)
 {
     const int i = (int)blockIdx.x * 64 + (int)threadIdx.x;
     if (i >= n) return;
@@ -26,6 +26,8 @@ __global__ void __launch_bounds__(64) qr_cadence_kernel(int n, CadenceLegs L, co
         cadence::hold_from_force((size_t)n, g_mpc_state + (size_t)6 * n + i, g_force + i, g_hold + i);
         return;
     }
+    // (mode route bound: not due and skipped by the WBC launch is a robot on another chain, or on none -- nothing of it is read or written)
+    if (g_skip && g_skip[i] != 0) return;
     // (a type that was never set up: the first valid one, as the MPC and WBC kernels take it; the WBC launch flags the robot)
     int tyid = g_type ? g_type[i] : 0;
     (void)resolve_type(tyid, L.type_ready);

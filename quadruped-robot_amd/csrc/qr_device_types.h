@@ -156,6 +156,9 @@ struct VmcLaunch {
     int n;
     int type_ready;          // bit t: type t was set up (robots naming any other type are flagged QRGPU_ST_BAD_TYPE)
     const float *ratio;      // [8][n] per-leg fMinRatio[4], fMaxRatio[4] of the world-frame overload, or null (the type's scalar ratios)
+    // Mode route (qrgpu_set_mode_route): [n], a robot whose word is not QRGPU_CHAIN_FORCE_BALANCE is left before anything of it is read or
+    // written.  Null: every robot.
+    const int *chain;
 };
 
 // Walk gait generator parameters after the constructor's bookkeeping (qrgpu_walk_gait_desc -> qrgpu_stages.hip)

@@ -131,8 +131,16 @@ struct CadenceLegs {
     float hip_l[QRGPU_MAX_TYPES], upper_l[QRGPU_MAX_TYPES], lower_l[QRGPU_MAX_TYPES];
     int type_ready;       // bit t: type t was set up
 };
+// g_skip (qrgpu_set_mode_route; null: nobody): with it g_due is the masked due', and a robot that is not due and whose word of g_skip is non-zero -- a
+// robot that is not on the MPC chain -- is left alone.
 __global__ void qr_cadence_kernel(int n, CadenceLegs L, const int *g_type, const int *g_due, const float *g_mpc_state, const float *g_fb_state, const float *g_force,
-                                  float *g_hold, float *g_tau, int *g_status);
+                                  float *g_hold, float *g_tau, int *g_status, const int *g_skip);
+
+// qr_mode_route_kernel.hip: one lane per robot; the chain each robot's mode selects, the masks of the cadenced tick under it, the chain's motor command
+__global__ void qr_mode_route_kernel(int n, qrgpu_mode_route_desc D, const float *g_sel, const int *g_plan, int *g_chain, int *g_flags, int *g_count);
+__global__ void qr_mode_masks_kernel(int n, const int *g_updated, const int *g_chain, int *g_due, int *g_skip);
+__global__ void qr_mode_command_kernel(int n, const int *g_chain, const float *g_cmd_mpc, const float *g_cmd_fb, const int *g_st_mpc, const int *g_st_fb,
+                                       float *g_out, int *g_st_out);
 
 // qr_fsm_kernel.hip: one lane per robot; the control state machine: what runs this tick, the zeroed command of a transition, the command sent
 __global__ void qr_fsm_update_kernel(int n, qrgpu_fsm_desc D, int reset, const float *g_msg, const float *g_script, int n_script, const int *g_ticks,

@@ -127,6 +127,8 @@ __global__ void __launch_bounds__(64) qr_vmc_kernel(VmcLaunch P, const int *__re
     const int n = P.n;
     const int rid = xcd_robot_index(blockIdx.x, n);
     if (rid < 0) return;
+    // (mode route bound: a robot on another chain, or on none -- nothing of it is read or written, VmcLaunch::chain)
+    if (P.chain && __builtin_amdgcn_readfirstlane(P.chain[rid]) != QRGPU_CHAIN_FORCE_BALANCE) return;
     int tyid = type_id ? type_id[rid] : 0;
     const bool bad_type = tyid < 0 || tyid >= QRGPU_MAX_TYPES || !((P.type_ready >> (tyid & (QRGPU_MAX_TYPES - 1))) & 1);
     if (bad_type) tyid = __builtin_ctz(P.type_ready | (1 << QRGPU_MAX_TYPES));       // computed with the first valid type, flagged QRGPU_ST_BAD_TYPE

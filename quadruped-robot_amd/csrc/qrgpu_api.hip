@@ -111,6 +111,7 @@ int launch_vmc(qrgpu_ctx *c, int n, const int *d_type_id, const float *d_vmc_in,
     HIPCHK(c, hipSetDevice(c->device));
     VmcLaunch P = c->vmc;
     P.n = n; P.ratio = d_ratio; P.type_ready = ready_mask(c->vmc_ready);
+    P.chain = c->mode_chain;                                         // (qrgpu_set_mode_route; null: every robot)
     hipLaunchKernelGGL(qr_vmc_kernel, dim3(8 * ((n + 7) / 8)), dim3(64), 0, c->stream, P, d_type_id, d_vmc_in, d_q, d_force, d_tau, d_status);
     HIPCHK(c, hipGetLastError());
     return QRGPU_OK;
@@ -226,7 +227,7 @@ void qrgpu_destroy(qrgpu_ctx *c)
     for (int k = 0; k < 2; ++k) if (c->ev_call[k]) hipEventDestroy(c->ev_call[k]);
     if (c->h_stage) (void)hipHostFree(c->h_stage);              // (zero copy: d_in1, d_out1 and d_st1 point into this block)
     else for (void *p : {(void *)c->d_in1, (void *)c->d_out1, (void *)c->d_st1}) (void)hipFree(p);
-    for (void *p : {(void *)c->d_wbc, (void *)c->d_body, (void *)c->d_gait_table, (void *)c->d_cost[0], (void *)c->d_cost[1], (void *)c->d_warm, (void *)c->d_flops, (void *)c->d_main_started, (void *)c->d_ftime,
+    for (void *p : {(void *)c->d_wbc, (void *)c->d_body, (void *)c->d_gait_table, (void *)c->d_mode_masks, (void *)c->d_cost[0], (void *)c->d_cost[1], (void *)c->d_warm, (void *)c->d_flops, (void *)c->d_main_started, (void *)c->d_ftime,
                     (void *)c->d_wbc_finished, (void *)c->d_gate_abort, (void *)c->d_solved, (void *)c->d_wbc_done, (void *)c->d_gather_done, (void *)c->d_tick_done,
                     (void *)c->d_timeline, (void *)c->d_tlr, (void *)c->d_sinv_spill, c->d_dbg_cycles, c->d_dbg_cycles_wbc, (void *)c->d_join_dbg})
         (void)hipFree(p);                                      // (null: a no-op)

@@ -100,6 +100,10 @@ struct qrgpu_ctx {
     bool body_dirty = true;
     // the stage kernels' per-robot reset and clock (qrgpu_set_stage_reset); all zeros while nothing is bound
     qrgpu_stage_reset stage_reset{};
+    // the chain each robot is on (qrgpu_set_mode_route); null while nothing is bound.  d_mode_masks [2][max_batch]: the masked due and skip words
+    // of the cadenced tick under the binding (qr_mode_masks_kernel), allocated at the first such call
+    const int *mode_chain = nullptr;
+    int *d_mode_masks = nullptr;
     // the gait table of qrgpu_gait_select_update_batch: a device copy the kernel's lanes index themselves, allocated at the first call and uploaded
     // when the caller's table differs from the one last uploaded
     qrgpu_gait_desc gait_table_host[QRGPU_MAX_GAITS] = {};

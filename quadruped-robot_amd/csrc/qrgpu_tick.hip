@@ -259,8 +259,18 @@ int qrgpu_tick_cadence_batch(qrgpu_ctx *c, int n, const int *d_type_id, const in
     HIPCHK(c, hipSetDevice(c->device));
     c->last_tick_piped = false;
     const TickArgs a{n, d_type_id, d_mpc_state, d_traj, d_gait, d_fb_state, d_wbc_cmd, d_prev_ori, d_force, d_tau, d_qdes, d_status};
+    // Under qrgpu_set_mode_route only the robots on the MPC chain take part: due' = updated && on_chain goes to the MPC launch, skip' = updated ||
+    // !on_chain to the WBC launch, both written by one small launch in front of the MPC launch; the cadence kernel leaves the others alone too.
+    const int *due = d_mpc_updated, *skip = d_mpc_updated, *idle = nullptr;
+    if (c->mode_chain) {
+        if (!c->d_mode_masks) HIPCHK(c, hipMalloc((void **)&c->d_mode_masks, 2 * sizeof(int) * (size_t)c->max_batch));
+        int *const d_due = c->d_mode_masks, *const d_skip = c->d_mode_masks + c->max_batch;
+        hipLaunchKernelGGL(qr_mode_masks_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, n, d_mpc_updated, c->mode_chain, d_due, d_skip);
+        HIPCHK(c, hipGetLastError());
+        due = d_due; skip = d_skip; idle = d_skip;
+    }
     MpcIO io = mpc_io(d_type_id, d_mpc_state, d_traj, d_gait, d_fb_state + (size_t)13 * n, d_force, d_tau, d_status);
-    io.due = d_mpc_updated;
+    io.due = due;
     MpcOpts mo;
     mo.epilogue = c->epilogue;
     int rc = launch_mpc(c, n, io, mo);
@@ -268,11 +278,11 @@ int qrgpu_tick_cadence_batch(qrgpu_ctx *c, int n, const int *d_type_id, const in
     CadenceLegs L{};
     for (int t = 0; t < QRGPU_MAX_TYPES; ++t) { L.hip_l[t] = c->mpc.type[t].hip_l; L.upper_l[t] = c->mpc.type[t].upper_l; L.lower_l[t] = c->mpc.type[t].lower_l; }
     L.type_ready = ready_mask(c->mpc_ready);
-    hipLaunchKernelGGL(qr_cadence_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, n, L, d_type_id, d_mpc_updated, d_mpc_state, d_fb_state, (const float *)d_force, d_hold,
-                       d_tau, d_status);
+    hipLaunchKernelGGL(qr_cadence_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, n, L, d_type_id, due, d_mpc_state, d_fb_state, (const float *)d_force, d_hold,
+                       d_tau, d_status, idle);
     HIPCHK(c, hipGetLastError());
     WbcOpts o = tick_wbc_opts(c, a, d_force);
-    o.pipe.skip = d_mpc_updated;
+    o.pipe.skip = skip;
     return launch_wbc(c, n, d_type_id, d_fb_state, d_wbc_cmd, d_prev_ori, d_tau, d_qdes, d_status, o);
 }
 

@@ -340,6 +340,22 @@ def fsm_desc(**fields):
     return _set_fields(d, fields)
 
 
+CHAIN_NONE, CHAIN_MPC, CHAIN_FORCE_BALANCE = 0, 1, 2    # qrgpu_mode_route_batch: the chain a robot is on
+ROUTE_BAD_MODE, ROUTE_NO_CHAIN = 0x1, 0x2               # ... and the bits of route_flags
+
+
+class mode_route_desc_struct(C.Structure):
+    _fields_ = [("chain_of_mode", C.c_int * 4), ("fallback_chain", C.c_int)]
+
+
+def mode_route_desc(**fields):
+    """qrgpu_mode_route_desc: the chain of each LocomotionMode -- VELOCITY the force-balance chain, ADVANCED_TROT the MPC chain, POSITION and WALK none
+    (such a robot runs on fallback_chain, the MPC chain, and is flagged) -- with any field overridden (scalars or sequences by name)."""
+    d = mode_route_desc_struct()
+    load_library().qrgpu_mode_route_desc_default(C.byref(d))
+    return _set_fields(d, fields)
+
+
 EPILOGUE_HIP_COMP, EPILOGUE_CLIP = 1, 2
 COMM_ID_BYTES = 128
 
@@ -378,7 +394,8 @@ EXPORTS = ["qrgpu_model_desc_default", "qrgpu_create", "qrgpu_destroy", "qrgpu_s
            "qrgpu_command_desc_default", "qrgpu_command_update_batch", "qrgpu_trot_inputs_batch", "qrgpu_mpc_command_desc_default",
            "qrgpu_mpc_command_batch", "qrgpu_tick_cadence_batch",
            "qrgpu_fsm_desc_default", "qrgpu_fsm_update_batch", "qrgpu_fsm_zero_command_batch", "qrgpu_fsm_command_batch",
-           "qrgpu_gait_table_default", "qrgpu_gait_select_update_batch", "qrgpu_stage_clock_batch", "qrgpu_velocity_inputs_batch"]
+           "qrgpu_gait_table_default", "qrgpu_gait_select_update_batch", "qrgpu_stage_clock_batch", "qrgpu_velocity_inputs_batch",
+           "qrgpu_mode_route_desc_default", "qrgpu_mode_route_batch", "qrgpu_set_mode_route", "qrgpu_mode_command_batch"]
 
 
 def load_library():
@@ -484,6 +501,11 @@ def load_library():
     lib.qrgpu_stage_clock_batch.argtypes = [vp, ip, vp, C.c_uint, vp, vp, vp]
     if hasattr(lib, "qrgpu_velocity_inputs_batch"):        # (an older build named by QRGPU_LIB for an A/B run has no force-balance trot chain)
         lib.qrgpu_velocity_inputs_batch.argtypes = [vp, ip, ip, ip] + [vp] * 10
+    if hasattr(lib, "qrgpu_mode_route_batch"):             # (... and none before the mode per robot knows these)
+        lib.qrgpu_mode_route_desc_default.argtypes = [C.POINTER(mode_route_desc_struct)]; lib.qrgpu_mode_route_desc_default.restype = None
+        lib.qrgpu_mode_route_batch.argtypes = [vp, ip, C.POINTER(mode_route_desc_struct)] + [vp] * 5
+        lib.qrgpu_set_mode_route.argtypes = [vp, vp]
+        lib.qrgpu_mode_command_batch.argtypes = [vp, ip] + [vp] * 7
     lib.qrgpu_vmc_force1.argtypes = [vp, ip, fp, fp, fp, fp, C.POINTER(ip)]
     lib.qrgpu_vmc_force_world1.argtypes = [vp, ip, fp, fp, fp, fp, fp, C.POINTER(ip)]
     lib.qrgpu_mpc_frontend_batch.argtypes = [vp, ip, ip, C.c_float, C.c_float] + [vp] * 6
@@ -1042,6 +1064,29 @@ class Context:
         state.  motor_cmd_loco may be motor_cmd itself."""
         self._chk(self._lib.qrgpu_fsm_command_batch(self._h, n, C.byref(desc), _dp(plan), _dp(est_in), _dp(motor_cmd_loco), _dp(fsm_state), _dp(motor_cmd),
                                                     _dp(fsm_out)))
+
+    def mode_route(self, n, desc, mode_sel, chain, plan=None, route_flags=None, chain_count=None):
+        """The chain each robot is on this tick (desc: mode_route_desc()): chain [n] int32 = CHAIN_NONE, CHAIN_MPC or CHAIN_FORCE_BALANCE from mode_sel [n]
+        float32 (row 45 of fsm_state; read at every call) and plan [n] int32 (optional: a robot whose plan has neither FSM_PLAN_RUN nor FSM_PLAN_PHASE1
+        is on no chain).  A mode that is no mode sets ROUTE_BAD_MODE in route_flags [n] int32, a mode without a chain ROUTE_NO_CHAIN; both run on
+        desc.fallback_chain.  chain_count [3] int32: the robots per chain."""
+        self._chk(self._lib.qrgpu_mode_route_batch(self._h, n, C.byref(desc), _dp(mode_sel), _dp(plan), _dp(chain), _dp(route_flags), _dp(chain_count)))
+
+    def set_mode_route(self, chain):
+        """Bind chain [n] int32 (mode_route's output; read when the kernels run): tick_cadence_batch then solves only the robots on CHAIN_MPC, and
+        stance_tick_batch, vmc_force_batch and vmc_force_world_batch only those on CHAIN_FORCE_BALANCE; every output column of any other robot stays as
+        it was.  Every other call ignores the binding."""
+        self._chk(self._lib.qrgpu_set_mode_route(self._h, _dp(chain)))
+
+    def clear_mode_route(self):
+        self._chk(self._lib.qrgpu_set_mode_route(self._h, None))
+
+    def mode_command(self, n, chain, cmd_mpc, cmd_fb, motor_cmd, status_mpc=None, status_fb=None, status=None):
+        """Every robot's motor_cmd [60][n] column and status word from its own chain: cmd_mpc / status_mpc where chain is CHAIN_MPC, cmd_fb / status_fb
+        where it is CHAIN_FORCE_BALANCE, zeros otherwise; bit for bit.  motor_cmd may be either input.  fsm_command follows and reads motor_cmd as
+        its motor_cmd_loco."""
+        self._chk(self._lib.qrgpu_mode_command_batch(self._h, n, _dp(chain), _dp(cmd_mpc), _dp(cmd_fb), _dp(status_mpc), _dp(status_fb), _dp(motor_cmd),
+                                                     _dp(status)))
 
     def mpc_frontend_batch(self, n, fe_in, fe_state, traj, gait, wbc_cmd=None, mpc_updated=None, num_horizon_l=2, dt_ctrl=0.002, dt_mpc=0.06):
         """SetupCommand + Run + UpdateMPC (without the solve) of n robots: qr_mpc_stance_leg_controller.cpp:158-382."""

@@ -12,6 +12,7 @@ inside the loop.
   python tools/closed_loop.py --trot --cadence [...]                                  the same with the tick on the reference's cadence: MPC or WBC per robot
   python tools/closed_loop.py --fsm [--ticks 3000] [--cmd-vx 0.15] [--fsm-speed 1]    a robot's whole life cycle: sit, stand up, MPC standing, trot, fall, again
   python tools/closed_loop.py --fsm --fsm-gait [...]                                  the same with every robot on the gait its state machine chose
+  python tools/closed_loop.py --fsm-mode [--fsm-trot-every 3] [...]                   the same with every robot's solve in the chain its state machine chose
   python tools/closed_loop.py --fb-trot [--cmd-vx 0.15] [--cmd-yaw 0.1] [--episodes] [--terrain ...]   the force-balance trot, every stage on the device
 
 The robots are dropped from z = 0.30 onto joint PD at the stand pose (400 ticks of 1 ms), shoved by up to 0.3 m/s in x and y, and handed to
@@ -64,6 +65,14 @@ tick's 0.002 x --fsm-speed and transition_ticks 500 / --fsm-speed: at speed 1 th
 --fsm-gait (implies --fsm) lets the gait follow the machine: the gait call becomes qrgpu_gait_select_update_batch on row 44 of fsm_state over the default
 gait table, with swing_in given (rows 8-11: the swingDuration of each robot's gait), and the binding's clock comes from qrgpu_stage_clock_batch, so it
 counts from the robot's last OnEnter or spawn.  Without the flag the launches and the output are what they were.
+--fsm-mode (implies --fsm --fsm-gait --cadence) lets the MODE follow the machine too.  One tick: episode step, fsm update, stage clock and binding,
+qrgpu_mode_route_batch on row 45 of fsm_state and the plan, qrgpu_set_mode_route, plant, observe, ground (its output kept), estimator, pack, command update
+(the rows of both chains: fe_in, fh_in, stance_cmd), zero command, gait select, the MPC chain up to qrgpu_mpc_command_batch and the force-balance chain up to
+qrgpu_stance_tick_batch, each into arrays of its own, qrgpu_mode_command_batch, fsm command.  Under the binding the cadenced tick solves only the robots on the
+MPC chain and the force-balance QP only those on its own; a robot that sits, stands up or holds is solved by neither.  Every --fsm-trot-every-th robot (default:
+every third) presses X a third time four ticks after the second, inside the gait transition, so that OnEnter finds it in JOY_TROT: mode VELOCITY, the `trot`
+gait, the force-balance chain.  The script is one for the batch; the robots that do not press on read it on a clock shifted past its third entry
+(qrgpu_stage_clock_batch with a mask nobody raises subtracts a per-robot origin).  Without the flag the launches and the output are what they were.
 
 --fb-trot (implies --estimator and --body; not with --trot, --cadence or --fsm) runs the reference's force-balance trot -- JOY_TROT:
 LocomotionMode::VELOCITY_LOCOMOTION with TorqueStanceLegController and the velocity case of the swing controller -- closed on the device.  Per tick, with
@@ -83,6 +92,10 @@ the stage-reset binding also clears the swing-command entries of a respawned rob
                 row 48 of gait_state), standing_robot_ticks (robots x ticks in LOCOMOTION under JOY_STAND, the "MPC standing" phase, warm-up included),
                 standing_swing_legs_commanded (legs that carried a swing command in them) beside standing_swing_legs_nominal_without (the legs the one
                 advanced_trot desc of --fsm schedules to swing in the same robot-ticks, on its clock from the spawn, holds ignored): reported, not judged
+  fsm_mode, chain_share (--fsm-mode; share of robots x timed ticks on no chain, the MPC chain, the force-balance chain, from the counters the route writes
+                per tick), route_flagged (share whose route word carries a flag), solved_share (share that was due AND on the MPC chain: the solves that
+                ran), tick_flagged_share_mpc / vmc_flagged_share_force_balance and swing_legs_commanded_mpc / _force_balance (the trot's figures over the
+                robot-ticks of each chain, warm-up included): reported, not judged
   ticks_per_s   closed-loop control ticks per second: every robot advances one tick per (plant step + controller tick)
   trot, cmd_vx, cmd_yaw, speed_along_command_mean (world x over the last 100 ticks, m/s, robots not respawned in them: speed_robots), yaw_rate_mean,
                 tick_flagged_share (share of ticks x robots whose tick status word carries a flag), swing_legs_commanded (legs x ticks x robots that
@@ -146,10 +159,16 @@ def main():
     ap.add_argument("--fsm", action="store_true", help="the control state machine decides what every robot runs: sit, stand up, stand, trot (implies --trot --episodes)")
     ap.add_argument("--fsm-speed", type=float, default=1.0, metavar="S", help="(--fsm) run the stand-up and the transitions S times faster")
     ap.add_argument("--fsm-gait", action="store_true", help="(implies --fsm) every robot on the gait its state machine chose, the stages' clock counted from its last OnEnter or spawn")
+    ap.add_argument("--fsm-mode", action="store_true", help="(implies --fsm --fsm-gait --cadence) every robot's solve in the chain its state machine chose: JOY_TROT robots on the force-balance chain, the others on the MPC chain")
+    ap.add_argument("--fsm-trot-every", type=int, default=3, metavar="K", help="(--fsm-mode) every K-th robot presses on to JOY_TROT; 0 = nobody")
     ap.add_argument("--fb-trot", action="store_true", help="the force-balance trot (JOY_TROT, mode VELOCITY) closed on the device: command, gait, velocity inputs, swing, stance tick (implies --estimator --body)")
     ap.add_argument("--profile", action="store_true", help="the run a profiler traces: fewer ticks, nothing else changed")
     a = ap.parse_args()
+    a.fsm_gait = a.fsm_gait or a.fsm_mode
+    a.cadence = a.cadence or a.fsm_mode
     a.fsm = a.fsm or a.fsm_gait
+    if a.fsm_trot_every < 0:
+        ap.error("--fsm-trot-every is a count")
     if a.fb_trot and (a.trot or a.cadence or a.fsm):
         ap.error("--fb-trot excludes --trot, --cadence and --fsm")
     a.trot = a.trot or a.fsm
@@ -258,12 +277,39 @@ def main():
         first_press = up + max(4, int(100 / a.fsm_speed))
         press = np.array([[first_press, q.JOY_BTN_X, 0.0, 0.0, 0.0],
                           [first_press + max(20, int(800 / a.fsm_speed)), q.JOY_BTN_X, a.cmd_yaw / fdesc.max_yawrate, 0.0, a.cmd_vx / fdesc.max_velx]], np.float32).T.copy()
+        if a.fsm_mode:  # a third X four ticks later, inside the gait transition: JOY_ADVANCED_TROT -> JOY_TROT before OnEnter reads it.  The script is one for
+                        # the batch, keyed on a tick count per robot: the robots that do not press on read the first two entries SCRIPT_SHIFT ticks later, on a
+                        # clock shifted by as much (script_ticks below), and never meet the third
+            SCRIPT_SHIFT = 1 << 20
+            third = press[:, 1].copy(); third[0] += 4
+            late = press.copy(); late[0] += SCRIPT_SHIFT
+            press = np.concatenate([press, third[:, None], late], axis=1).copy()
         d.update(fsm_state=ctx.alloc((q.FSM_STATE_ROWS, n)), plan=ctx.alloc((n,), np.int32), stage_mask=ctx.alloc((n,), np.int32), script=ctx.alloc(press.shape).upload(press),
                  fsm_log=ctx.alloc((ticks + 20, q.FSM_OUT_ROWS, n)).zero(), plan_log=ctx.alloc((ticks + 20, n), np.int32).zero())
     if a.fsm_gait:      # the gait table, the clock's memory and its output, the flags, every tick's index in force (row 48 of gait_state)
         gtable = pkg.workload.gait_table()
         d.update(clock_origin=ctx.alloc((n,), np.int32).zero(), clock_local=ctx.alloc((n,), np.int32).zero(), gait_flags=ctx.alloc((n,), np.int32),
                  gait_log=ctx.alloc((ticks + 20, n)).zero())
+    if a.fsm_mode:      # the route, the force-balance chain's stages and the arrays the two chains do not share: swing memory and flags, swing-command entries,
+                        # force, torque, status, motor command.  The command, gait, ground, estimator and observe arrays are shared
+        q, W = pkg.qrgpu, pkg.workload
+        ttype = dict(flat=0, gap=0, stairs=2, plane=3, rough=4)[kind]
+        rdesc = pkg.mode_route_desc()
+        fb_sdesc, stdesc = pkg.swing_mode_desc(q.MODE_VELOCITY, terrain=ttype), pkg.stance_desc(q.MODE_VELOCITY, terrain=ttype)
+        svcfg = W.swing_velocity_cfg("a1", stance_duration=float(pkg.gait_table_default()[q.FSM_GAIT_TROT][0]))
+        ctx.vmc_setup_packed(0, W.vmc_cfg("a1"), pkg.model_desc("a1")[:3])
+        scmd = np.zeros((28, n), np.float32); scmd[9] = HEIGHT; scmd[15] = HEIGHT
+        presses_on = (np.arange(n) % a.fsm_trot_every == a.fsm_trot_every - 1) if a.fsm_trot_every else np.zeros(n, bool)
+        d.update(chain_log=ctx.alloc((ticks + 20, n), np.int32).zero(), count_log=ctx.alloc((ticks + 20, 3), np.int32).zero(),
+                 route_log=ctx.alloc((ticks + 20, n), np.int32).zero(), script_origin=ctx.alloc((n,), np.int32).upload(np.where(presses_on, 0, -SCRIPT_SHIFT).astype(np.int32)),
+                 script_ticks=ctx.alloc((n,), np.int32).zero(), nobody=ctx.alloc((n,), np.int32).zero(),
+                 cmd_mpc=ctx.alloc((60, n)).zero(), cmd_fb=ctx.alloc((60, n)).zero(), stance_cmd=ctx.alloc((28, n)).upload(scmd), gout=ctx.alloc((32, n)),
+                 fb_swing_state=ctx.alloc((q.SWING_STATE_FLOATS, n)), fb_swing_flags=ctx.alloc((n,), np.int32), sv=ctx.alloc((53, n)).zero(),
+                 sv_out=ctx.alloc((48, n)).zero(), fb_cmd_mem=ctx.alloc((1, n), np.int32).zero(), swing_flag=ctx.alloc((4, n)).zero(),
+                 stance_state=ctx.alloc((q.STANCE_STATE_FLOATS, n)), vmc_in=ctx.alloc((37, n)), ratio=ctx.alloc((8, n)), stance_out=ctx.alloc((33, n)),
+                 fb_force=ctx.alloc((12, n)).zero(), fb_tau=ctx.alloc((12, n)).zero(), mpc_status=ctx.alloc((n,), np.int32).zero(),
+                 fb_status=ctx.alloc((n,), np.int32).zero())
+        d["tau"].zero()
 
     def plant(par, **out):
         if a.body:
@@ -304,13 +350,20 @@ def main():
                                        height=d["height"], plant_status=d["status_log"].row(done[0] - 1) if done[0] else None, tick_status=None,
                                        prev_ori=d["prev"], motor_cmd=d["cmd"], done_list=d["done_list"], done_count=d["done_count"])
             if a.fsm:                         # JoyCallback, the change request, RunFSM up to the decision: the joy rows, the plan, the stages' reset mask
-                ctx.fsm_update(n, fdesc, d["fsm_state"], d["joy"], d["plan"], stage_mask=d["stage_mask"], script=d["script"], n_script=2, ticks=d["ep_state"],
-                               done=d["done_log"].row(done[0]), bits=pkg.qrgpu.EP_REASONS, reset=int(done[0] == 0))
+                if a.fsm_mode:                # the script's clock per robot: the episode's tick count, shifted for the robots that do not press on
+                    ctx.stage_clock(n, d["nobody"], 1, d["ep_state"], d["script_origin"], d["script_ticks"])
+                ctx.fsm_update(n, fdesc, d["fsm_state"], d["joy"], d["plan"], stage_mask=d["stage_mask"], script=d["script"], n_script=press.shape[1],
+                               ticks=d["script_ticks"] if a.fsm_mode else d["ep_state"], done=d["done_log"].row(done[0]), bits=pkg.qrgpu.EP_REASONS,
+                               reset=int(done[0] == 0))
                 if a.fsm_gait:                # the stages' clock counts from the robot's last OnEnter or spawn, not from the spawn alone
                     ctx.stage_clock(n, d["stage_mask"], pkg.qrgpu.EP_REASONS | pkg.qrgpu.FSM_ENTERED, d["ep_state"], d["clock_origin"], d["clock_local"])
                     ctx.set_stage_reset(mask=d["stage_mask"], bits=pkg.qrgpu.EP_REASONS | pkg.qrgpu.FSM_ENTERED, ticks=d["clock_local"])
                 else:
                     ctx.set_stage_reset(mask=d["stage_mask"], bits=pkg.qrgpu.EP_REASONS | pkg.qrgpu.FSM_ENTERED, ticks=d["ep_state"])
+                if a.fsm_mode:                # the chain each robot is on this tick, from the mode OnEnter latched (row 45 of fsm_state) and this tick's plan
+                    ctx.mode_route(n, rdesc, d["fsm_state"].row(45), d["chain_log"].row(done[0]), plan=d["plan"], route_flags=d["route_log"].row(done[0]),
+                                   chain_count=d["count_log"].row(done[0]))
+                    ctx.set_mode_route(d["chain_log"].row(done[0]))
             elif a.estimator and a.episodes:  # the observe, ground and estimator stages restart a robot this episode step respawned
                 ctx.set_stage_reset(mask=d["done_log"].row(done[0]), ticks=d["ep_state"])
             plant(params, plant_out=d["out"], mpc_state=d["mpc"], status=d["status_log"].row(done[0]) if a.body else d["plant_status"],
@@ -319,7 +372,7 @@ def main():
                 first = done[0] == 0
                 ctx.observe_batch(n, odesc, d["est_in"], d["obs"], d["est_in"], d["rpy"], ground_in=d["gin"], tick=d["stamp"], est_out_prev=d["est_out"],
                                   reset=first, step=done[0])
-                ctx.ground_update_batch(n, d["gin"], d["gst"], d["gout"] if a.fb_trot else None, d["est_in"], reset=first)
+                ctx.ground_update_batch(n, d["gin"], d["gst"], d["gout"] if a.fb_trot or a.fsm_mode else None, d["est_in"], reset=first)
                 ctx.estimator_update_batch(n, ecfg, d["est_in"], d["stamp"], d["est_state"], d["est_out"])
                 if not a.fb_trot:             # (the force-balance chain reads est_in / est_out themselves: packed once after the loop, for the report)
                     ctx.pack_state_batch(n, com, d["est_in"], d["est_out"], d["rpy"], d["mpc_est"], d["fb_est"])
@@ -344,9 +397,10 @@ def main():
             if a.trot:                        # qrLocomotionController::Update / GetAction, qrFSMStateLocomotion::Run, in the reference's order
                 k = done[0] - 1
                 t = float(np.float32(k) * np.float32(0.002))                   # (under --episodes the gait runs on the binding's per-robot clock)
-                ctx.command_update(n, cdesc, d["joy"], d["cmd_state"], state_des=d["state_des"], fe_in=d["fe_in"], fh_in=d["fh_in"], reset=int(first))
+                fb_rows = dict(stance_cmd=d["stance_cmd"]) if a.fsm_mode else {}  # (the force-balance chain's copy of the command: rows 0-6 of stance_cmd)
+                ctx.command_update(n, cdesc, d["joy"], d["cmd_state"], state_des=d["state_des"], fe_in=d["fe_in"], fh_in=d["fh_in"], reset=int(first), **fb_rows)
                 if a.fsm:                     # SwitchMode / StandLoop: the robots in phase 1 run the chain on a zeroed command
-                    ctx.fsm_zero_command(n, d["plan"], state_des=d["state_des"], fe_in=d["fe_in"], fh_in=d["fh_in"])
+                    ctx.fsm_zero_command(n, d["plan"], state_des=d["state_des"], fe_in=d["fe_in"], fh_in=d["fh_in"], **fb_rows)
                 if a.fsm_gait:                # the gait OnEnter chose (row 44 of fsm_state), latched at the robot's reset; its swingDuration into swing_in
                     ctx.gait_select_update_batch(n, gtable, d["fsm_state"].row(44), t, d["est_in"].row(13), d["gait_state"], d["gait_out"], d["fe_in"],
                                                  swing_in=d["swing_in"], flags=d["gait_flags"], reset=int(first))
@@ -360,13 +414,25 @@ def main():
                 ctx.footholds_batch(n, fcfg, d["fh_in"], d["swing_in"], gait_state=d["gait_state"], gait_out=d["gait_out"])
                 ctx.swing_targets_batch(n, ecfg, d["swing_in"], wbc_cmd=d["wcmd"], foot_target_world=d["fe_in"].row(26), qdes=d["qdes"])
                 ctx.mpc_frontend_batch(n, d["fe_in"], d["fe_state"], d["traj"], d["gait"], d["wcmd"], d["updated"])
-                if a.cadence:
+                if a.cadence:                 # (--fsm-mode: the status words of the robots on the chain land in an array that is not cleared in between)
                     ctx.tick_cadence_batch(n, d["updated"], d["mpc_est"], d["traj"], d["gait"], d["fb_est"], d["wcmd"], d["prev"], d["force"], d["hold"], d["tau"],
-                                           d["tick_log"].row(k))
+                                           d["mpc_status"] if a.fsm_mode else d["tick_log"].row(k))
                     ctx.copy_rows(d["due_log"].row(k), d["updated"], n)        # the report's log: who was solved this tick
                 else:
                     ctx.tick_batch(n, d["mpc_est"], d["traj"], d["gait"], d["fb_est"], d["wcmd"], d["prev"], d["force"], d["tau"], d["tick_log"].row(k))
-                ctx.mpc_command(n, mdesc, d["tau"], d["qdes"], d["swing_in"], d["gait_out"], d["gait_state"], d["cmd_mem"], d["cmd"], reset=int(first))
+                ctx.mpc_command(n, mdesc, d["tau"], d["qdes"], d["swing_in"], d["gait_out"], d["gait_state"], d["cmd_mem"], d["cmd_mpc" if a.fsm_mode else "cmd"],
+                                reset=int(first))
+                if a.fsm_mode:                # the force-balance chain into its own arrays, then every robot's column and status word from its own chain
+                    ctx.velocity_inputs(n, d["est_in"], d["est_out"], d["gait_out"], d["gait_state"], d["state_des"], ground_out=d["gout"], swing_vel_in=d["sv"],
+                                        est_in_next=d["est_in"], cmd_mem=d["fb_cmd_mem"], swing_flag=d["swing_flag"], terrain=ttype, reset=int(first))
+                    ctx.swing_update_batch(n, fb_sdesc, d["est_in"], d["est_out"], d["gait_out"], d["fb_swing_state"], d["fb_swing_flags"], swing_vel_in=d["sv"],
+                                           reset=2 if first else 0)
+                    ctx.swing_velocity_batch(n, ecfg, svcfg, d["sv"], d["sv_out"])
+                    ctx.stance_tick_batch(n, stdesc, d["est_in"], d["est_out"], d["gout"], d["rpy"], d["gait_out"], d["stance_cmd"], d["stance_state"], d["vmc_in"],
+                                          d["fb_force"], d["fb_tau"], d["cmd_fb"], gait_state=d["gait_state"], ratio=d["ratio"], stance_out=d["stance_out"],
+                                          status=d["fb_status"], swing_q=d["sv_out"].row(24), swing_flag=d["swing_flag"], current_time=t, reset=first)
+                    ctx.mode_command(n, d["chain_log"].row(k), d["cmd_mpc"], d["cmd_fb"], d["cmd"], status_mpc=d["mpc_status"], status_fb=d["fb_status"],
+                                     status=d["tick_log"].row(k))
                 if a.fsm:                     # the rest of RunFSM: the chain's column passed on, replaced by a stand-up, blend or hold, or repeated
                     ctx.fsm_command(n, fdesc, d["plan"], d["est_in"], d["cmd"], d["fsm_state"], d["cmd"], fsm_out=d["fsm_log"].row(k))
                     ctx.copy_rows(d["plan_log"].row(k), d["plan"], n, np.int32)
@@ -483,6 +549,26 @@ def main():
         res.update(fsm_gait=True, gait_share={nm: float((index == e).mean()) for e, nm in enumerate(names)}, standing_robot_ticks=int(standing.sum()),
                    standing_swing_legs_commanded=int((swing & standing[:, None, :]).sum()),
                    standing_swing_legs_nominal_without=int((nominal & standing[:, None, :]).sum()), gait_flags_seen=int(np.bitwise_or.reduce(d["gait_flags"].download())))
+    if a.fsm_mode:    # who ran on which chain, who was solved, and the trot's figures per chain: reported, not judged
+        q = pkg.qrgpu
+        chain = d["chain_log"].download()                                  # [tick][robot]
+        counts = d["count_log"].download()[20:20 + ticks].astype(np.float64)
+        on_mpc, on_fb = chain == q.CHAIN_MPC, chain == q.CHAIN_FORCE_BALANCE
+        due = d["due_log"].download() != 0
+        flagged = pkg.status_flags(tick_log) != 0                           # (the merged status words: each robot's own chain's)
+        kd_abad = d["kd_log"].download()[:, 0::3]
+        swing_fb = (kd_abad != 0) & on_fb[:, None, :]                       # (a force-balance stance leg carries no gains)
+        swing_mpc = swing & on_mpc[:, None, :]
+        share = lambda x, m: float(x[m].mean()) if m.any() else None
+        res.update(fsm_mode=True, fsm_trot_every=a.fsm_trot_every, script_ticks=[int(x) for x in press[0, :3]],
+                   chain_share={nm: float(counts[:, c].sum() / (n * ticks)) for c, nm in enumerate(("none", "mpc", "force_balance"))},
+                   route_flagged=float((d["route_log"].download()[20:20 + ticks] != 0).mean()),
+                   solved_share=float((due & on_mpc)[20:20 + ticks].mean()),
+                   tick_flagged_share_mpc=share(flagged, on_mpc), vmc_flagged_share_force_balance=share(flagged, on_fb),
+                   swing_legs_commanded_mpc=int(swing_mpc.sum()), swing_legs_commanded_force_balance=int(swing_fb.sum()),
+                   swing_legs_commanded_per_robot_tick_mpc=float(swing_mpc.sum() / max(1, on_mpc.sum())),
+                   swing_legs_commanded_per_robot_tick_force_balance=float(swing_fb.sum() / max(1, on_fb.sum())),
+                   fb_swing_flags_seen=int(np.bitwise_or.reduce(d["fb_swing_flags"].download())))
     print(json.dumps(res))
     ctx.close()
 
