@@ -8,8 +8,10 @@
 // not unrolled, before the inward pass, where the fewest values are live: a surface sample is sixteen loads and their weights, and four of them
 // live at once do not fit beside the state.  What the loop leaves: the foot force and the knee force (they enter the knee link's external force)
 // and the corners' wrench on the base, which is summed over the quad and joins the push.
-// The step body is the terrain kernel's, written a third time (profiles/terrain_isa_compare.txt: a body shared through a template moved the
-// flat kernel's register allocation); what the three share by call is qr_plant_quad.h, qr_plant_math.h, qr_terrain.h.
+// What the tick has in common with the terrain kernel's -- state in, command read, motor law, integrator, state check, push read, plant_out,
+// terrain_out -- is the named pieces of qr_plant_quad.h; what stands in this kernel is its own (the stops, the four-point loop,
+// forward_dynamics_body, the second LDS column, g_bout, the hit flags) and the state write and the mpc_state / est_in writes, which are the
+// terrain kernel's text: called as pieces they measured 120 ns a launch over the kernel as it was.
 // ============================================================================
 #include <hip/hip_runtime.h>
 #include "qr_device_types.h"
@@ -70,22 +72,13 @@ __global__ void __launch_bounds__(64) qr_plant_step_body_kernel(int n, qrgpu_pla
     const qrgpu_plant_body_desc &B = bodies[w.K - types];          // the type's body: the slot of its model constants
     const size_t N = (size_t)n;
     const int i = w.robot, leg = w.leg, j = 3 * leg;
-    // the state: read once
-    real qw = ROW(g_state, 0), qx = ROW(g_state, 1), qy = ROW(g_state, 2), qz = ROW(g_state, 3);
-    unit_quat(qw, qx, qy, qz, w.flags);
-    v3 pos = mk(ROW(g_state, 4), ROW(g_state, 5), ROW(g_state, 6));
+    real qw, qx, qy, qz, q0, q1, q2, qd0, qd1, qd2;
+    v3 pos;
     sv6 v0;
-    v0.a = mk(ROW(g_state, 7), ROW(g_state, 8), ROW(g_state, 9));
-    v0.l = mk(ROW(g_state, 10), ROW(g_state, 11), ROW(g_state, 12));
-    real q0 = ROW(g_state, 13 + j), q1 = ROW(g_state, 14 + j), q2 = ROW(g_state, 15 + j);
-    real qd0 = ROW(g_state, 25 + j), qd1 = ROW(g_state, 26 + j), qd2 = ROW(g_state, 27 + j);
+    state_in(g_state, N, i, j, w.flags, qw, qx, qy, qz, pos, v0, q0, q1, q2, qd0, qd1, qd2);
     const real h = (real)P.dt / (real)P.substeps;
     const real ck = P.contact_k, ca = P.contact_a, mu = P.mu, v_eps = P.v_eps, ground_z = P.ground_z, tau_max = P.tau_max;
-
-    // the robot's field (an id outside the stack: field 0, flagged) and the wrench on its base, world frame: force at the base origin, moment
-    int fid = g_field ? g_field[i] : 0;
-    if (fid < 0 || fid >= T.n_fields) { fid = 0; w.flags |= QRGPU_PL_BAD_FIELD; }
-    const float *field = g_height + (size_t)fid * ((size_t)T.nx * (size_t)T.ny);
+    const float *field = field_in(T, g_height, g_field, i, w.flags);
     const real gx0 = T.x0, gy0 = T.y0, cell = T.cell;
     bool off_field = false;
 
@@ -103,18 +96,12 @@ __global__ void __launch_bounds__(64) qr_plant_step_body_kernel(int n, qrgpu_pla
 #pragma unroll 1
     for (int s = 0; s < P.substeps; ++s) {
         const frame3 R = quat_to_rot(qw, qx, qy, qz);
-        // The motor command of this leg's joints (p, Kp, d, Kd, tua) and the push are read again at every sub-step, through pointers the compiler cannot
-        // see through: held in registers across the inward pass, their 21 doubles were what spilled.  They are inputs, not the state.
+        // The motor command of this leg's joints and the push are read again at every sub-step, through pointers the compiler cannot see through:
+        // held in registers across the inward pass, their 21 doubles were what spilled.  They are inputs, not the state.
         const float *cmd = g_cmd, *push = g_push;
         asm volatile("" : "+s"(cmd), "+s"(push));
-        const real cp0 = ROW(cmd, j), cp1 = ROW(cmd, j + 1), cp2 = ROW(cmd, j + 2);
-        const real kp0 = ROW(cmd, 12 + j), kp1 = ROW(cmd, 13 + j), kp2 = ROW(cmd, 14 + j);
-        const real cd0 = ROW(cmd, 24 + j), cd1 = ROW(cmd, 25 + j), cd2 = ROW(cmd, 26 + j);
-        const real kd0 = ROW(cmd, 36 + j), kd1 = ROW(cmd, 37 + j), kd2 = ROW(cmd, 38 + j);
-        const real ff0 = ROW(cmd, 48 + j), ff1 = ROW(cmd, 49 + j), ff2 = ROW(cmd, 50 + j);
-        real tau0 = clip(kp0 * (cp0 - q0) + kd0 * (cd0 - qd0) + ff0, tau_max);
-        real tau1 = clip(kp1 * (cp1 - q1) + kd1 * (cd1 - qd1) + ff1, tau_max);
-        real tau2 = clip(kp2 * (cp2 - q2) + kd2 * (cd2 - qd2) + ff2, tau_max);
+        real tau0, tau1, tau2;
+        motor_law(cmd_in(cmd, N, i, j), q0, q1, q2, qd0, qd1, qd2, tau_max, tau0, tau1, tau2);
         KEEP(QR_PB_OUT_TAU) = (float)tau0; KEEP(QR_PB_OUT_TAU + 1) = (float)tau1; KEEP(QR_PB_OUT_TAU + 2) = (float)tau2;
         // the stops: added after the motor's clip
         const real tl0 = limit_torque(q0, qd0, B.q_lo[0], B.q_hi[0], B.limit_k, B.limit_a);
@@ -147,31 +134,15 @@ __global__ void __launch_bounds__(64) qr_plant_step_body_kernel(int n, qrgpu_pla
             else KEEP(QR_PB_OUT_FN + k - QR_PB_BOTTOM) = (float)fnk;
         }
         // the base wrench: the push in the base frame of this sub-step and the eight corners' forces
-        v3 push_f = mk(0, 0, 0), push_m = mk(0, 0, 0);
-        if (push) { push_f = mk(ROW(push, 0), ROW(push, 1), ROW(push, 2)); push_m = mk(ROW(push, 3), ROW(push, 4), ROW(push, 5)); }
+        v3 push_f, push_m;
+        push_in(push, N, i, push_f, push_m);
         sv6 wrench; wrench.a = mulT(R, push_m); wrench.l = mulT(R, push_f);
         wrench = wrench + quad_sum(corners);
         forward_dynamics_body(K, leg, st, R, v0, qd0, qd1, qd2, tau0, tau1, tau2, f_b, fk_b, wrench, afb, qdd0, qdd1, qdd2);
-        acc = (afb.l + cross(v0.a, v0.l)) + mulT(R, mk(0, 0, QR_PL_GRAVITY));      // what an accelerometer at the base origin reads over this sub-step
-        // semi-implicit Euler: rates first, then positions with the new rates
-        v0 = v0 + h * afb;
-        qd0 += h * qdd0; qd1 += h * qdd1; qd2 += h * qdd2;
-        q0 += h * qd0; q1 += h * qd1; q2 += h * qd2;
-        pos = pos + h * mul(R, v0.l);
-        // quat <- normalise(quat (x) exp(h omega_body))
-        const v3 hw = h * v0.a;
-        const real th = sqrt(dot(hw, hw));
-        const real cw = cos(0.5 * th), sc = th < 1e-8 ? 0.5 : sin(0.5 * th) / th;
-        const v3 e = sc * hw, qv = mk(qx, qy, qz);
-        const real nw = qw * cw - dot(qv, e);
-        const v3 nv = (qw * e + cw * qv) + cross(qv, e);
-        qw = nw; qx = nv.x; qy = nv.y; qz = nv.z;
-        const real inv = 1.0 / sqrt(qw * qw + qx * qx + qy * qy + qz * qz);
-        qw *= inv; qx *= inv; qy *= inv; qz *= inv;
+        acc = accelerometer(R, v0, afb);
+        integrate(R, h, afb, qdd0, qdd1, qdd2, qw, qx, qy, qz, pos, v0, q0, q1, q2, qd0, qd1, qd2);
     }
-    const int bad = !(isfinite(qw) && isfinite(qx) && isfinite(qy) && isfinite(qz) && finite3(pos) && finite3(v0.a) && finite3(v0.l) && isfinite(q0) && isfinite(q1) &&
-                      isfinite(q2) && isfinite(qd0) && isfinite(qd1) && isfinite(qd2));
-    if (quad_or(bad)) w.flags |= QRGPU_PL_NONFINITE;
+    state_check(w.flags, qw, qx, qy, qz, pos, v0, q0, q1, q2, qd0, qd1, qd2);
     if (quad_or(off_field)) w.flags |= QRGPU_PL_OFF_FIELD;
     const int any = quad_or(hits);
     if (any & QR_PB_HIT_TRUNK) w.flags |= QRGPU_PL_TRUNK_CONTACT;
@@ -202,21 +173,10 @@ __global__ void __launch_bounds__(64) qr_plant_step_body_kernel(int n, qrgpu_pla
     leg_start(K, leg, st, q0, q1, q2, qd0, qd1, qd2, v0, foot_b, foot_vel);
     const v3 foot_w = pos + mul(R, foot_b);
     const float contact = (hits & QR_PB_HIT_FOOT) ? 1.f : 0.f;
-    if (g_tout) {      // the ground under the foot of the state just written
-        const terrain::Sample g = terrain::sample(field, T.nx, T.ny, gx0, gy0, cell, foot_w.x, foot_w.y);
-        const v3 nrm = terrain::normal_of(g.zx, g.zy);
-        ROW(g_tout, leg) = (float)(g.z + ground_z);
-        ROW(g_tout, 4 + j) = (float)nrm.x; ROW(g_tout, 5 + j) = (float)nrm.y; ROW(g_tout, 6 + j) = (float)nrm.z;
-    }
-    if (g_out) {
-        ROW(g_out, j) = KEEP(QR_PB_OUT_FORCE); ROW(g_out, j + 1) = KEEP(QR_PB_OUT_FORCE + 1); ROW(g_out, j + 2) = KEEP(QR_PB_OUT_FORCE + 2);
-        ROW(g_out, 12 + j) = (float)foot_w.x; ROW(g_out, 13 + j) = (float)foot_w.y; ROW(g_out, 14 + j) = (float)foot_w.z;
-        ROW(g_out, 24 + leg) = contact;
-        ROW(g_out, 28 + j) = KEEP(QR_PB_OUT_TAU); ROW(g_out, 29 + j) = KEEP(QR_PB_OUT_TAU + 1); ROW(g_out, 30 + j) = KEEP(QR_PB_OUT_TAU + 2);      // the motor's torque; the stops' are g_bout's
-        ROW(g_out, 46 + j) = (float)qdd0; ROW(g_out, 47 + j) = (float)qdd1; ROW(g_out, 48 + j) = (float)qdd2;
-        if (leg == 0) { ROW(g_out, 40) = (float)afb.a.x; ROW(g_out, 41) = (float)afb.a.y; ROW(g_out, 42) = (float)afb.a.z; }
-        if (leg == 1) { ROW(g_out, 43) = (float)afb.l.x; ROW(g_out, 44) = (float)afb.l.y; ROW(g_out, 45) = (float)afb.l.z; }
-    }
+    ground_out(g_tout, N, i, leg, field, T, ground_z, foot_w);
+    // the foot's force and the motor's torque come from the column; the stops' torques are g_bout's
+    plant_out(g_out, N, i, leg, KEEP(QR_PB_OUT_FORCE), KEEP(QR_PB_OUT_FORCE + 1), KEEP(QR_PB_OUT_FORCE + 2), foot_w, contact, KEEP(QR_PB_OUT_TAU), KEEP(QR_PB_OUT_TAU + 1),
+              KEEP(QR_PB_OUT_TAU + 2), afb, qdd0, qdd1, qdd2);
     if (g_mpc) {      // the ground truth in qrgpu_pack_state_batch's conventions
         const v3 r = mul(R, foot_b - mk(P.com_offset[0], P.com_offset[1], P.com_offset[2]));
         ROW(g_mpc, 13 + j) = (float)r.x; ROW(g_mpc, 14 + j) = (float)r.y; ROW(g_mpc, 15 + j) = (float)r.z;
